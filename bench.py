@@ -14,7 +14,8 @@ other decomposition of north_star: ONE pair of `--frames` x N frames whose outpu
 (`predict_frame_sharded`: every rank reads its own fl-1 frames of temporal halo, ONE all-reduce of Q_per_ch + range flag, pooling on every rank).
 value = Mpixels/s (test+ref) = 2*W*H*frames of a step / median step seconds.
 
-  python bench.py [--gpus N --steps K --warmup W --pairs-per-gpu P --shard pairs|frames --config 1|2|3 --collective auto|off|force]
+  python bench.py [--gpus N --steps K --warmup W --pairs-per-gpu P --shard pairs|frames --config 1|2|3 --collective auto|off|force
+                  --dump-outputs DIR]
   (N>1: launched by torch.distributed.run)
 
 ONE JSON line on rank 0's stdout and nothing else (file descriptor 1 is pointed at stderr while the process runs: librccl prints a banner).
@@ -89,7 +90,13 @@ def main():
     ap.add_argument("--config", type=int, default=None, choices=[1, 2, 3],
                     help="BASELINE.json configs[] index: 1 = 1920x1080 x60 standard_fhd, 2 = 3840x2160 x60 standard_4k (the default "
                          "arguments), 3 = 3840x2160 x120 foveated with moving gaze on standard_hdr_pq (adds `roofline_fov`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy: jod.npy (float64 "
+                         "[pairs], every rank's pairs in rank order; frame sharding: [1]) and q_per_ch.npy (float32 [pairs, bands, 2, "
+                         "frames]).  The synthetic inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # stdout carries ONE JSON line and nothing else: librccl prints a version banner on the C stdout of rank 0 when a communicator is
     # created (5 lines, flushed at exit), other libraries may follow.  File descriptor 1 is pointed at stderr for the life of the
     # process and the line is written to the saved descriptor at the end.
@@ -200,6 +207,7 @@ def main():
                                                       else ("one rank: skipped" if world == 1 else "%d ranks" % world)))
 
     jods_rowlen = []            # length of a result row (Q_per_ch | flag | JOD), noted by the first step
+    last = {}                   # what the latest step returned (host arrays; kept by reference, copied once after the timed steps)
     pin = {}
 
     def rows_to_host(g):
@@ -224,7 +232,8 @@ def main():
         if frames_mode:
             from fovvideovdp_amd.sharding import predict_frame_sharded
             vs = fv.fvvdp_video_source_array(pairs[0][0], pairs[0][1], fps, dim_order="BCFHW", display_photometry=m.display_photometry)
-            q, _ = predict_frame_sharded(m, vs, rank, world, fixation_point=gaze, force_collective=force_collective)
+            q, st = predict_frame_sharded(m, vs, rank, world, fixation_point=gaze, force_collective=force_collective)
+            last["jod"], last["q_per_ch"] = q, st["Q_per_ch"]
             return [float(q)]
         # queue every pair without host synchronisation, then the one collective of the path (all-reduce of a zero buffer in which
         # this rank filled its own rows; one rank: nothing), ONE device -> host copy of [pairs, Q_per_ch | range flag | JOD]
@@ -232,7 +241,9 @@ def main():
         rows = outs[0][1]["result_buffer"].unsqueeze(0) if K == 1 else torch.stack([st["result_buffer"] for (_, st) in outs])
         if not jods_rowlen:
             jods_rowlen.append(rows.shape[1])
-        return rows_to_host(gather_pair_results(rows, rank, world, force_collective=force_collective))[:, -1].tolist()
+        host = rows_to_host(gather_pair_results(rows, rank, world, force_collective=force_collective))
+        last["rows"] = host
+        return host[:, -1].tolist()
 
     def step_reference_call():
         q, _ = m.predict(pairs[0][0], pairs[0][1], dim_order="BCFHW", frames_per_second=fps, fixation_point=gaze)
@@ -258,6 +269,9 @@ def main():
         stamps.append(time.perf_counter())       # every step ends in its own host synchronisation (the result copy)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        from fovvideovdp_amd.fvvdp import band_frequencies
+        dump_outputs(args.dump_outputs, last, band_frequencies(W, H, m.pix_per_deg)[0], n_clip)
     # max over ranks of the timed region and of every single step (a step ends in the collective, so the ranks leave it together)
     tall = torch.tensor([dt] + [b - a for a, b in zip(stamps[:-1], stamps[1:])], dtype=torch.float64, device=dev)
     if dist is not None:
@@ -618,6 +632,21 @@ def main():
     if dist is not None:
         dist.barrier()             # rank 0 ran the per-kernel timing, the PCIe leg and the CPU baseline alone: leave together
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, last, n_bands, n_frames):
+    """--dump-outputs: the last timed step's results as .npy files (a few KB per pair, far below 64 MB)"""
+    if "rows" in last:          # pair sharding: one row per pair, [Q_per_ch (bands x 2 x frames) | range flag (int32 bits) | JOD]
+        rows = np.array(last["rows"].numpy(), dtype=np.float32)       # a copy: the step's page-locked buffer is reused
+        nq = n_bands * 2 * n_frames
+        assert rows.shape[1] == nq + 2, rows.shape
+        jod, q = rows[:, -1], rows[:, :nq].reshape(-1, n_bands, 2, n_frames)
+    else:                       # frame sharding: one pair, the same result on every rank
+        jod = np.asarray([float(last["jod"])])
+        q = np.asarray(last["q_per_ch"], dtype=np.float32)[None]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "jod.npy"), np.asarray(jod, dtype=np.float64))
+    np.save(os.path.join(out_dir, "q_per_ch.npy"), np.ascontiguousarray(q, dtype=np.float32))
 
 
 def measure_traffic_live():

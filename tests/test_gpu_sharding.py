@@ -200,6 +200,24 @@ def test_bench_one_rank_takes_the_same_step_path():
     _check_bench_line(out, dims, "nccl", world=1)
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
+    """`--dump-outputs DIR`: the JODs and Q_per_ch of the last timed step as .npy files -- the JODs of the JSON line, bit for bit, and
+    the Q_per_ch of single predict() calls on the same synthetic pairs."""
+    import fovvideovdp_amd as fv
+    from fovvideovdp_amd.synth import synth_video_pair
+    d = tmp_path / "dump"
+    out, (W, H, N, K) = _run_bench("nccl", 1, extra=("--collective", "off", "--dump-outputs", str(d)), dims=(960, 540, 20, 2))
+    jod, q = np.load(d / "jod.npy"), np.load(d / "q_per_ch.npy")
+    assert jod.dtype == np.float64 and q.dtype == np.float32 and jod.shape == (K,) and q.shape[0] == K
+    assert [float(j).hex() for j in jod] == out["jod_exact"]
+    m = fv.fvvdp(display_name="standard_4k")
+    for p in range(K):
+        t, r = synth_video_pair(N, H, W, device="cuda", pair=p)
+        _, st = m.predict(t, r, frames_per_second=30)
+        assert np.array_equal(q[p], st["Q_per_ch"]), p
+
+
 @pytest.mark.timeout(900)
 def test_rccl_executes_on_one_rank_through_the_step_path():
     """RCCL on hardware through the product's own step.  bench.py launched the way the driver launches a multi-rank
@@ -246,40 +264,60 @@ def test_bench_one_rank_without_a_communicator_falls_back_and_says_so():
     _check_bench_line(out, dims, "no_such_backend", world=1)
 
 
+# A multi-rank test runs every rank as its own process with the GPU open, next to the pytest process itself: four ranks keep a
+# test within the GPU box's limit of six such processes at a time.
+MAX_RANKS_ON_ONE_BOX = 4
+
+
 @pytest.mark.timeout(900)
-def test_bench_eight_ranks_dry_run_under_gloo():
-    """The 8-rank launch of the round-end scaling run, dry: 8 gloo ranks sharing this box's GPU(s) at reduced size, one pair each."""
-    out, dims = _run_bench("gloo", 8, dims=(480, 270, 12, 1))
-    _check_bench_line(out, dims, "gloo", world=8)
+def test_bench_four_ranks_dry_run_under_gloo():
+    """The multi-rank launch of the round-end scaling run, dry: 4 gloo ranks sharing this box's GPU(s) at reduced size, two pairs
+    each -- the 8 pairs (and 8 JODs in the line) of an 8-rank run with one pair per rank."""
+    world = MAX_RANKS_ON_ONE_BOX
+    out, dims = _run_bench("gloo", world, dims=(480, 270, 12, 2))
+    _check_bench_line(out, dims, "gloo", world=world)
 
 
 @pytest.mark.timeout(600)
-def test_bench_frame_sharded_under_gloo():
+def test_bench_frame_sharded_under_gloo(tmp_path):
     """`--shard frames`: ONE pair of --frames x N frames, every rank evaluates its own output frames (+ fl-1 frames of halo) and one
-    all-reduce of Q_per_ch completes the clip on every rank.  JOD equal to the unsharded call on the same clip."""
+    all-reduce of Q_per_ch completes the clip on every rank.  JOD equal to the unsharded call on the same clip; the Q_per_ch that
+    `--dump-outputs` writes equal, bit for bit, to the two ranks' frame ranges evaluated here."""
     import fovvideovdp_amd as fv
     from fovvideovdp_amd.synth import synth_video_pair
     W, H, N = 960, 540, 12
-    out, _ = _run_bench("gloo", 2, extra=("--shard", "frames"), dims=(W, H, N, 1))
+    d = tmp_path / "dump"
+    out, _ = _run_bench("gloo", 2, extra=("--shard", "frames", "--dump-outputs", str(d)), dims=(W, H, N, 1))
     assert out["config"]["shard"] == "frames" and out["step_path"].startswith("predict_frame_sharded") and out["scaling"] == "weak"
     assert "one pair of %d frames" % (2 * N) in out["config"]["parallelism"]
     px = 2.0 * W * H * N * 2
     assert abs(out["value"] - px / (out["ms_per_step"] * 1e-3) / 1e6) <= 2e-3 * out["value"]
     t, r = synth_video_pair(2 * N, H, W, device="cuda")
-    q, _ = fv.fvvdp(display_name="standard_4k").predict(t, r, frames_per_second=30)
+    m = fv.fvvdp(display_name="standard_4k")
+    q, st = m.predict(t, r, frames_per_second=30)
     assert len(out["jod"]) == 1 and abs(float(q) - out["jod"][0]) < 2e-6
+    jod, qd = np.load(d / "jod.npy"), np.load(d / "q_per_ch.npy")
+    assert [float(j).hex() for j in jod] == out["jod_exact"] and qd.shape == (1,) + st["Q_per_ch"].shape
+    # bit for bit: every rank's output frames, computed here with the same frame ranges, side by side
+    from fovvideovdp_amd.sharding import shard_range
+    vs = fv.fvvdp_video_source_array(t, r, 30, display_photometry=m.display_photometry)
+    parts = [m.predict_video_source(vs, frame_range=shard_range(2 * N, k, 2), pool=False)[1]["Q_per_ch"] for k in range(2)]
+    assert np.array_equal(qd[0], np.concatenate(parts, axis=2))
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="the RCCL run needs two GPUs (the driver's multi-GPU box)")
 def test_bench_multi_rank_step_under_rccl():
-    """The same launch with backend nccl (= RCCL over xGMI), one GPU per rank: init with device_id, the all-reduce of the
-    device buffer, the barrier before destroy_process_group.  Skipped on single-GPU boxes."""
-    out, dims = _run_bench("nccl", 2)
-    _check_bench_line(out, dims, "nccl")
+    """The same launch with backend nccl (= RCCL over xGMI), one GPU per rank, as many ranks as the box has GPUs (up to 2): init
+    with device_id, the all-reduce of the device buffer, the barrier before destroy_process_group.  RCCL refuses two ranks on one
+    device, so a single-GPU box runs ONE rank through torch.distributed.run with `--collective force`: the communicator and the
+    step's all-reduce are still RCCL's, and the line must say so."""
+    world = min(2, torch.cuda.device_count())
+    extra = () if world > 1 else ("--collective", "force")
+    out, dims = _run_bench("nccl", world, extra=extra, torchrun=True)
+    _check_bench_line(out, dims, "nccl", world=world)
 
 
-def _worker8(rank, world, port, out_dir):
+def _worker_frames(rank, world, port, out_dir):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -292,36 +330,38 @@ def _worker8(rank, world, port, out_dir):
         dev = torch.device("cuda", rank % torch.cuda.device_count())
         m = fv.fvvdp(display_name="standard_fhd", device=dev)
         res = {}
-        for n in (5, 19):                                        # 5 frames over 8 ranks: three ranks have an empty shard
+        for n in (2, 19):                                        # 2 frames over 4 ranks: two ranks have an empty shard
             test, ref = synth_video_pair(n, 54, 96, device=dev)
             vs = fv.fvvdp_video_source_array(test, ref, FPS, display_photometry=m.display_photometry)
             jod, st = predict_frame_sharded(m, vs, rank, world)
             res["jod%d" % n], res["Q%d" % n] = float(jod), st["Q_per_ch"]
             res["share%d" % n] = np.asarray(shard_range(n, rank, world))
-        np.savez(os.path.join(out_dir, f"r8_{rank}.npz"), **res)
+        np.savez(os.path.join(out_dir, f"rf_{rank}.npz"), **res)
     finally:
         dist.barrier()
         dist.destroy_process_group()
 
 
 @pytest.mark.timeout(600)
-def test_eight_ranks_frame_sharding_with_empty_shards(tmp_path):
-    """World 8 (the node the path is meant for) as 8 gloo ranks sharing this box's GPU(s): a 5-frame clip leaves three ranks without
-    a frame -- they still take part in both collectives and return the same result -- and a 19-frame clip gives shares of 3 and 2."""
+def test_four_ranks_frame_sharding_with_empty_shards(tmp_path):
+    """World 4 as 4 gloo ranks sharing this box's GPU(s): a 2-frame clip leaves two ranks without a frame -- they still take part
+    in both collectives and return the same result -- and a 19-frame clip gives shares of 5 and 4."""
     import torch.multiprocessing as mp
     import fovvideovdp_amd as fv
     from fovvideovdp_amd.synth import synth_video_pair
-    world = 8
-    mp.spawn(_worker8, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
-    res = [np.load(os.path.join(str(tmp_path), f"r8_{k}.npz")) for k in range(world)]
+    world = MAX_RANKS_ON_ONE_BOX
+    mp.spawn(_worker_frames, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    res = [np.load(os.path.join(str(tmp_path), f"rf_{k}.npz")) for k in range(world)]
     m = fv.fvvdp(display_name="standard_fhd")
-    for n in (5, 19):
+    for n in (2, 19):
         test, ref = synth_video_pair(n, 54, 96, device="cuda")
         q, st = m.predict(test, ref, frames_per_second=FPS)
         shares = [tuple(int(v) for v in res[k]["share%d" % n]) for k in range(world)]
         assert shares[0][0] == 0 and shares[-1][1] == n and all(a[1] == b[0] for a, b in zip(shares[:-1], shares[1:]))
-        if n == 5:
-            assert sum(1 for (a, b) in shares if a == b) == 3
+        if n == 2:
+            assert sum(1 for (a, b) in shares if a == b) == 2
+        else:
+            assert sorted(set(b - a for (a, b) in shares)) == [4, 5]
         for k in range(world):
             assert np.array_equal(res[k]["Q%d" % n], st["Q_per_ch"]), (n, k)
             assert abs(float(res[k]["jod%d" % n]) - float(q)) < 2e-6

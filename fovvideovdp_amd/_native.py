@@ -97,15 +97,26 @@ SYMBOLS = {
     "fvvdp_ctx_call_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
 }
 
+# include/fvvdp_hip_images.h: batched still images (bound by lib() as well; SYMBOLS stays the ABI of fvvdp_hip.h)
+IMAGE_SYMBOLS = {
+    "fvvdp_images_channels": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
+                                        C.c_size_t, C.POINTER(Eotf), C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p]),
+    "fvvdp_images_forward_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                            C.POINTER(Geom), C.POINTER(BandMaps), C.POINTER(PoolParams), C.c_void_p, C.c_void_p]),
+    "fvvdp_pool_jod_columns": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PoolParams), C.c_void_p,
+                                         C.c_void_p]),
+}
+IMAGES_MAX_PAIRS_PER_LAUNCH = 128        # FVVDP_IMAGES_MAX_PAIRS_PER_LAUNCH
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Five translation units -- the band /
-    pooling / side-metric kernels with the C ABI, and the temporal kernels once per sample type (temporal_launch.hip with
-    -DK1_PART=0..3) -- are compiled concurrently and linked into one shared library."""
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Six translation units -- the band /
+    pooling / side-metric kernels with the C ABI, the temporal kernels once per sample type (temporal_launch.hip with
+    -DK1_PART=0..3) and the batched still-image ingest (still_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
-    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, "fvvdp_hip.h")]
+    deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -118,6 +129,8 @@ def build(force=False, verbose=False):
     units = [(SRC_PATH, [], os.path.join(objdir, "fvvdp_hip.o"))]
     units += [(os.path.join(csrc, "temporal_launch.hip"), ["-DK1_PART=%d" % k], os.path.join(objdir, "temporal_part%d.o" % k))
               for k in range(4)]
+    # the batched still-image ingest: per-pixel arithmetic identical to the single-image kernel (see still_launch.hip)
+    units += [(os.path.join(csrc, "still_launch.hip"), ["-fno-slp-vectorize"], os.path.join(objdir, "still_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -142,7 +155,7 @@ def lib():
             raise RuntimeError("libfvvdp_hip.so is not built (%s): run `python -c 'import __graft_entry__ as g; g.build()'`. "
                                "There is no CPU fallback for the hot path." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

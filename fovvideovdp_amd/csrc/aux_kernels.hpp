@@ -44,23 +44,26 @@ struct PoolArgs {
 
 __device__ __forceinline__ float pool_pow(float x, float p) { return p == 1.0f ? x : powf(x, p); }
 
+// frame f pooled over bands and temporal channels, raised to beta_t (the term of the frame sum)
+__device__ __forceinline__ float pool_frame(const PoolArgs& a, const int f) {
+    float qt = 0.0f;
+    for (int c = 0; c < a.n_ch; ++c) {
+        const float wc = (a.n_ch == 2 && c == 1) ? a.w_transient : 1.0f;
+        float qs = 0.0f;
+        for (int b = 0; b < a.n_bands; ++b)
+            qs += pool_pow(fabsf(a.Q[((size_t)b * 2 + c) * a.q_stride + f] * wc), a.beta_sch);
+        qs = pool_pow(qs, 1.0f / a.beta_sch);
+        qt += pool_pow(qs, a.beta_tch);
+    }
+    qt = pool_pow(qt, 1.0f / a.beta_tch);
+    return pool_pow(qt, a.beta_t);
+}
+
 // by the first 256 threads of a workgroup of `nthreads` >= 256 threads (all of them reach the barriers); s_part: 256 doubles
 __device__ __forceinline__ void pool_jod_body(const PoolArgs& a, double* s_part, const int tid) {
     double acc = 0.0;
     if (tid < 256) {
-        for (int f = tid; f < a.n_frames; f += 256) {
-            float qt = 0.0f;
-            for (int c = 0; c < a.n_ch; ++c) {
-                const float wc = (a.n_ch == 2 && c == 1) ? a.w_transient : 1.0f;
-                float qs = 0.0f;
-                for (int b = 0; b < a.n_bands; ++b)
-                    qs += pool_pow(fabsf(a.Q[((size_t)b * 2 + c) * a.q_stride + f] * wc), a.beta_sch);
-                qs = pool_pow(qs, 1.0f / a.beta_sch);
-                qt += pool_pow(qs, a.beta_tch);
-            }
-            qt = pool_pow(qt, 1.0f / a.beta_tch);
-            acc += (double)pool_pow(qt, a.beta_t);
-        }
+        for (int f = tid; f < a.n_frames; f += 256) acc += (double)pool_frame(a, f);
         s_part[tid] = acc;
     }
     __syncthreads();
@@ -79,6 +82,23 @@ __device__ __forceinline__ void pool_jod_body(const PoolArgs& a, double* s_part,
 __global__ __launch_bounds__(256) void pool_jod_kernel(const PoolArgs a) {
     __shared__ double s_part[256];
     pool_jod_body(a, s_part, (int)threadIdx.x);
+}
+
+// JOD of every column of Q_per_ch on its own: for column j exactly what pool_jod_body does for n_frames == 1 (one frame,
+// the frame sum over one term, normalised by 1), so d_jod[j] is bit-identical to fvvdp_pool_jod on that single column.
+// One thread per column.
+struct PoolColsArgs {
+    PoolArgs p;             // n_frames unused; Q points at column 0
+    int n_cols;
+};
+
+__global__ __launch_bounds__(256) void pool_jod_cols_kernel(const PoolColsArgs a) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.n_cols) return;
+    const double acc = 0.0 + (double)pool_frame(a.p, j);
+    const float q_all = pool_pow((float)(acc / (double)1), 1.0f / a.p.beta_t);
+    const float sgn = a.p.jod_a < 0.0f ? -1.0f : 1.0f;
+    a.p.out[j] = sgn * powf(powf(fabsf(a.p.jod_a), 1.0f / a.p.beta_jod) * q_all, a.p.beta_jod) + 10.0f;
 }
 
 // Heat-map reconstruction, one level: out = expand(coarse) + (D0 + w*D1)/m   [then ^beta_jod * |jod_a| on level 0]

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "fvvdp_hip.h"
+#include "fvvdp_hip_images.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // errors
@@ -48,6 +49,7 @@ extern "C" const char* fvvdp_last_error(void) { return g_err; }
 #include "band_kernel.hpp"
 #include "band2_kernel.hpp"
 #include "aux_kernels.hpp"
+#include "still_kernels.hpp"
 #include "psnr_kernel.hpp"
 #include "resize_kernels.hpp"
 
@@ -1249,10 +1251,14 @@ static int check_pool_params(const fvvdp_pool_params* prm) {
 }
 
 // slot0: first level-0 frame slot of the batch (fvvdp_temporal_channels wrote slots [slot0, slot0 + n)); the levels below are
-// scratch of the pass itself and always use slots [0, n)
+// scratch of the pass itself and always use slots [0, n).
+// plan_n: the number of frames the work decomposition (chunk heights, and with them the grouping of the float partial sums
+// behind Q) is chosen for.  0 = n (video and predict(): the fastest plan for this launch); the batched image path passes a
+// constant so that a pair's result does not depend on the size of its batch.
 static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_stride, int q_col0, const float* h_fixation,
                               const fvvdp_geom* geom, const fvvdp_band_maps* maps, const fvvdp_pool_params* pool,
-                              float* d_jod, void* stream) {
+                              float* d_jod, void* stream, int plan_n = 0) {
+    if (plan_n < 1) plan_n = n;
     if (!c || !d_Q) return fail(FVVDP_EINVAL, "null argument");
     if (slot0 < 0 || n < 1 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n, c->max_frames);
     if (pool) {
@@ -1303,14 +1309,14 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             a.wc = c->lw[b + 2];
             a.hc = c->lh[b + 2];
             a.n_strips = band2_strips(a.wb);
-            chunking2(a.hc, a.n_strips, n, c->wave_capacity2, c->env.band2_kr, a.n_chunks, a.kr);
+            chunking2(a.hc, a.n_strips, plan_n, c->wave_capacity2, c->env.band2_kr, a.n_chunks, a.kr);
             a.n_big = a.n_chunks;
             a.kr2 = a.kr;
             a.n_frames = n;
             {
                 // a launch of several rounds of tall chunks: the last chunk of every frame is cut into four and dispatched after
                 // all tall ones (band2_kernel's two phases)
-                const long long waves = (long long)n * a.n_strips * a.n_chunks;
+                const long long waves = (long long)plan_n * a.n_strips * a.n_chunks;
                 int kr2 = (waves >= 2 * c->wave_capacity2 && a.n_chunks >= 3 && a.kr >= 16) ? (a.kr + 3) / 4 : 0;
                 if (c->env.band2_kr2 >= 0) kr2 = c->env.band2_kr2;                  // tuning override (FVVDP_BAND2_KR2); 0 = uniform chunks
                 if (kr2 >= 1 && kr2 < a.kr && a.n_chunks >= 2) {
@@ -1394,7 +1400,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
         a.wc = c->lw[b + 1];
         a.hc = c->lh[b + 1];
         a.n_strips = band_strips(a.wc);
-        chunking(a.hc, a.n_strips, n, c->wave_capacity, c->env.band_cr, a.n_chunks, a.cr);
+        chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, c->env.band_cr, a.n_chunks, a.cr);
         a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
         a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
         a.csf_y = c->csf_y;
@@ -1815,6 +1821,94 @@ extern "C" int fvvdp_heatmap_colorize(fvvdp_ctx* c, int n, const float* d_dmap, 
     hipLaunchKernelGGL(colour_map_kernel, grid, dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// batched still images (include/fvvdp_hip_images.h)
+// ------------------------------------------------------------------------------------------------------------
+extern "C" int fvvdp_images_channels(fvvdp_ctx* c, const void* const* h_test_ptrs, const void* const* h_ref_ptrs, int n,
+                                     int dtype, int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y,
+                                     int slot0, int32_t* d_oob_flags, void* stream) {
+    if (!c || !h_test_ptrs || !h_ref_ptrs || !eotf) return fail(FVVDP_EINVAL, "null argument");
+    if (c->P != 2) return fail(FVVDP_EINVAL, "fvvdp_images_channels needs a still-image context (planes == 2)");
+    if (dtype < FVVDP_U8 || dtype > FVVDP_F32) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 is currently supported");
+    if (C != 1 && C != 3) return fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
+    if (C == 3 && !h_rgb2y) return fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
+    if (n < 1 || slot0 < 0 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n, c->max_frames);
+    if (eotf->kind == FVVDP_EOTF_LUT && (dtype == FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
+    if (eotf->kind != FVVDP_EOTF_LUT && dtype == FVVDP_U8) return fail(FVVDP_EINVAL, "uint8 sources need FVVDP_EOTF_LUT (uint16: table or closed form)");
+    if (eotf->kind == FVVDP_EOTF_NONE) return fail(FVVDP_EINVAL, "images need a display model (kind != FVVDP_EOTF_NONE)");
+    const int HW = c->W * c->H;
+    if (C == 3 && chan_stride < (size_t)HW) return fail(FVVDP_EINVAL, "chan_stride %zu is below the image size %d", chan_stride, HW);
+    const size_t es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
+    // PX = 4 when every group of four pixels is one naturally aligned load per channel
+    bool vec = HW % 4 == 0 && (C == 1 || chan_stride % 4 == 0);
+    for (int k = 0; k < n; ++k) {
+        if (!h_test_ptrs[k] || !h_ref_ptrs[k]) return fail(FVVDP_EINVAL, "null image pointer at pair %d", k);
+        if ((reinterpret_cast<uintptr_t>(h_test_ptrs[k]) | reinterpret_cast<uintptr_t>(h_ref_ptrs[k])) % es != 0)
+            return fail(FVVDP_EINVAL, "image pointers must be aligned to their element size (pair %d)", k);
+        if ((reinterpret_cast<uintptr_t>(h_test_ptrs[k]) | reinterpret_cast<uintptr_t>(h_ref_ptrs[k])) % (4 * es) != 0) vec = false;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    static const float taps[2] = {1.0f, 1.0f};
+    luminance_slots(c, slot0, n);
+    luminance_range(c, eotf, C, h_rgb2y, taps, 1);
+    Timed tm(c, 0, st);
+    StillArgs a;
+    memset(&a, 0, sizeof(a));
+    a.chan_stride = chan_stride;
+    a.C = C;
+    a.HW = HW;
+    a.e = make_eotf(eotf);
+    if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
+    for (int k0 = 0; k0 < n; k0 += STILL_MAX_SLOTS) {           // the pointer table of one launch holds 128 pairs
+        const int nk = (n - k0) < STILL_MAX_SLOTS ? (n - k0) : STILL_MAX_SLOTS;
+        for (int k = 0; k < nk; ++k) {
+            a.test[k] = h_test_ptrs[k0 + k];
+            a.ref[k] = h_ref_ptrs[k0 + k];
+        }
+        a.out = level_addr(c, 0, slot0 + k0);
+        a.oob = d_oob_flags ? d_oob_flags + k0 : nullptr;
+        still_launch(dtype, vec ? 4 : 1, a, nk, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_pool_jod_columns(const float* d_Q, int n_bands, int n_channels, int n_cols, int q_stride,
+                                      const fvvdp_pool_params* prm, float* d_jod, void* stream) {
+    if (!d_Q || !prm || !d_jod) return fail(FVVDP_EINVAL, "null argument");
+    if (n_bands < 1 || n_bands > FVVDP_MAX_BANDS || n_cols < 1 || q_stride < n_cols) return fail(FVVDP_EINVAL, "bad Q_per_ch shape");
+    if (n_channels != 1 && n_channels != 2) return fail(FVVDP_EINVAL, "n_channels must be 1 (image) or 2 (video)");
+    {
+        int rc = check_pool_params(prm);
+        if (rc != FVVDP_OK) return rc;
+    }
+    PoolColsArgs a;
+    fill_pool_args(a.p, d_Q, n_bands, n_channels, 1, q_stride, prm, d_jod);
+    a.n_cols = n_cols;
+    hipLaunchKernelGGL(pool_jod_cols_kernel, dim3((n_cols + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    HIP_TRY(hipGetLastError());
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_images_forward_pool(fvvdp_ctx* c, int n, float* d_Q, int q_stride, int q_col0, const float* h_fixation,
+                                         const fvvdp_geom* geom, const fvvdp_band_maps* maps, const fvvdp_pool_params* pool,
+                                         float* d_jod, void* stream) {
+    if (!c || !d_Q || !pool || !d_jod) return fail(FVVDP_EINVAL, "null argument");
+    if (c->P != 2) return fail(FVVDP_EINVAL, "fvvdp_images_forward_pool needs a still-image context (planes == 2)");
+    if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
+    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    {
+        int rc = check_pool_params(pool);
+        if (rc != FVVDP_OK) return rc;
+    }
+    // work decomposition planned for FVVDP_IMAGES_PLAN_N slots whatever n is: a pair's Q does not depend on its batch
+    int rc = bands_forward_core(c, 0, n, d_Q, q_stride, q_col0, h_fixation, geom, maps, nullptr, nullptr, stream,
+                                FVVDP_IMAGES_PLAN_N);
+    if (rc != FVVDP_OK) return rc;
+    Timed tm(c, 1 + c->n_bands, reinterpret_cast<hipStream_t>(stream));
+    return fvvdp_pool_jod_columns(d_Q + q_col0, c->n_bands, 2, n, q_stride, pool, d_jod, stream);
 }
 
 extern "C" int fvvdp_ctx_timing_enable(fvvdp_ctx* c, int on) {

@@ -19,7 +19,7 @@ from . import _native as nat
 from . import utils
 from .display_model import (code_value_tables, fvvdp_display_geometry, fvvdp_display_photometry, native_eotf,
                             native_geometry)
-from .video_source import fvvdp_video_source_array
+from .video_source import fvvdp_video_source_array, reshuffle_dims
 from .video_source_yuv import fvvdp_video_source_yuv_frames
 
 
@@ -78,6 +78,52 @@ def window_frame_indices(N, fl, temp_padding):
     else:
         raise RuntimeError('Unknown padding method "{}"'.format(temp_padding))
     return np.asarray(first + list(range(1, N)), dtype=np.int32)
+
+
+def _refuse_grad(a):
+    if isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("Gradients through the metric are not supported on the HIP path (forward-only kernels); "
+                           "detach the inputs or wrap the call in torch.no_grad()")
+
+
+def _image_stack(test, reference, dim_order):
+    """Stacked image pairs in `dim_order` (a B axis; F absent or of size 1) -> (test, reference) tensors [B, C, H, W] (views
+    where possible; numpy uint16 carried as int16 like fvvdp_video_source_array)."""
+    if tuple(test.shape) != tuple(reference.shape):
+        raise RuntimeError('Test and reference image/video tensors must be exactly the same shape')
+    d = dim_order.upper()
+    if len(d) != len(test.shape):
+        raise RuntimeError('Input tensor much have exactly as many dimensions as there are characters in the "dims" parameter')
+    if len(set(d)) != len(d) or set(d) - set("BCFHW") or "H" not in d or "W" not in d:
+        raise RuntimeError('dim_order must be made of distinct letters of "BCFHW" and contain H and W, got "%s"' % dim_order)
+    if "B" not in d:
+        raise RuntimeError('predict_images needs a B axis (the image pairs) in dim_order, got "%s"' % dim_order)
+    t = fvvdp_video_source_array._as_tensor(test)
+    r = fvvdp_video_source_array._as_tensor(reference)
+    if "F" in d:
+        if t.shape[d.index("F")] != 1:
+            raise RuntimeError("still images only: the F axis must have size 1 (use predict() for video)")
+        t, r = t.select(d.index("F"), 0), r.select(d.index("F"), 0)
+        d = d.replace("F", "")
+    t, r = reshuffle_dims(t, d, "BCHW"), reshuffle_dims(r, d, "BCHW")
+    if t.shape[0] < 1:
+        raise RuntimeError("no image pairs")
+    if t.shape[1] != 1 and t.shape[1] != 3:
+        raise RuntimeError('The content must have either 1 or 3 colour channels.')
+    return t, r
+
+
+def _image_pair(test, reference, dim_order):
+    """One image pair in `dim_order` (B and F absent or of size 1) -> (test, reference) [C, H, W]."""
+    d = dim_order.upper()
+    if tuple(test.shape) != tuple(reference.shape):
+        raise RuntimeError('Test and reference image/video tensors must be exactly the same shape')
+    if "B" not in d:
+        test, reference, d = test[None], reference[None], "B" + d
+    t, r = _image_stack(test, reference, d)
+    if t.shape[0] != 1:
+        raise RuntimeError("predict_image_pairs takes one image pair per list entry (B must be 1)")
+    return t[0], r[0]
 
 
 class _Context:
@@ -226,10 +272,223 @@ class fvvdp:
         return [self.predict(t, r, dim_order=dim_order, frames_per_second=frames_per_second, fixation_point=fixation_point,
                              sync=False) for (t, r) in pairs]
 
+    # ---- batched still images (extension; include/fvvdp_hip_images.h) ------------------------------------------------
+    def predict_images(self, test, reference, dim_order="BCHW", fixation_point=None, sync=True):
+        """Extension: scores B still-image pairs in one pass.  `test` and `reference` are stacked arrays or tensors (host or
+        device) whose `dim_order` has a B axis and no F axis (or F == 1).  Returns (Q_JOD, stats): Q_JOD a [B] device tensor,
+        stats['Q_per_ch'] [B, bands, 2, 1] (numpy; with `sync=False` a device tensor that `fvvdp.finish(stats)` completes),
+        stats['range_flags'] one out-of-range flag per pair, stats['heatmap'] [B, ch, 1, H, W] fp16 when the metric makes heat
+        maps.  `fixation_point`: [x, y] or [B, 2] for a foveated metric.  Pair k's result does not depend on the batch."""
+        self._check_device()
+        _refuse_grad(test)
+        _refuse_grad(reference)
+        t, r = _image_stack(test, reference, dim_order)
+        B = t.shape[0]
+        # the whole stack on the device once, as contiguous [B][C][H][W] (no copy for a resident contiguous stack)
+        self.last_h2d_bytes = sum(a.numel() * a.element_size() for a in (t, r) if a.device != self.device)
+        if t.dtype != r.dtype:
+            t, r = self._to_unit_float(t), self._to_unit_float(r)
+        t, r = t.to(self.device).contiguous(), r.to(self.device).contiguous()
+        fix = None
+        if self.foveated:
+            fix = self._fixation(fixation_point, t.shape[3], t.shape[2], B)
+        with torch.cuda.device(self.device):
+            return self._predict_image_group([t[k] for k in range(B)], [r[k] for k in range(B)], fix, sync)
+
+    def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
+        """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
+        or with them of size 1).  The pairs are grouped by (shape, dtypes) and every group is scored in batches by
+        predict_images' path, reading device-resident images where they lie.  Returns [(Q_JOD, stats)] in input order, each
+        shaped as predict() shapes the result of that pair (Q_JOD 0-d, Q_per_ch [bands, 2, 1]); with `sync=True`
+        stats['out_of_range'] tells whether a sample of the pair lay outside [0, 1].  Foveated metric: `fixation_points` is
+        None (every pair: its image centre, as predict()) or one [x, y] (or None) per pair, in that pair's pixels."""
+        self._check_device()
+        items = []
+        for t, r in pairs:
+            t, r = _image_pair(t, r, dim_order)
+            _refuse_grad(t)
+            _refuse_grad(r)
+            items.append((t, r))
+        if fixation_points is not None and len(fixation_points) != len(items):
+            raise RuntimeError("fixation_points must hold one [x, y] (or None) per image pair")
+        groups = {}
+        for i, (t, r) in enumerate(items):
+            groups.setdefault((tuple(t.shape), t.dtype, r.dtype), []).append(i)
+        out = [None] * len(items)
+        with torch.cuda.device(self.device):
+            for idx in groups.values():
+                fix = None
+                if self.foveated:
+                    H, W = items[idx[0]][0].shape[1:]
+                    fix = np.concatenate([self._fixation(None if fixation_points is None else fixation_points[i], W, H, 1)
+                                          for i in idx])
+                q, st = self._predict_image_group([items[i][0] for i in idx], [items[i][1] for i in idx], fix, sync,
+                                                  labels=idx)
+                for j, i in enumerate(idx):
+                    s = {k: v for k, v in st.items() if k not in ("Q_per_ch", "range_flags", "heatmap", "result_buffer")}
+                    s['N_frames'] = 1
+                    if sync:
+                        s['Q_per_ch'] = np.ascontiguousarray(st['Q_per_ch'][j])
+                        s['out_of_range'] = bool(st['range_flags'][j])
+                    else:                            # as predict(..., sync=False): fvvdp.finish(s) completes it
+                        s['Q_per_ch'] = st['Q_per_ch'][j]
+                        s['range_flag'] = st['range_flags'][j:j + 1]
+                    if 'heatmap' in st:
+                        s['heatmap'] = st['heatmap'][j:j + 1]
+                    out[i] = (q[j], s)
+        return out
+
+    def _check_device(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("fovvideovdp_amd needs an AMD GPU (torch device 'cuda'); there is no CPU fallback")
+
+    def _image_eotf(self, dt):
+        """(sample type code, fvvdp_eotf) of the display model for samples of torch dtype `dt` (the choice _make_feeder makes
+        for a still image)."""
+        if dt is torch.uint8:
+            dtype, nbits = nat.FVVDP_U8, 8
+        elif dt is torch.int16:
+            dtype, nbits = nat.FVVDP_U16, 16
+        elif dt is torch.float32:
+            dtype, nbits = nat.FVVDP_F32, 0
+        else:
+            raise RuntimeError("Only uint8, uint16 and float32 is currently supported")
+        use_closed = dtype == nat.FVVDP_F32 or (dtype == nat.FVVDP_U16 and not getattr(self, "exact_uint16", False))
+        desc = native_eotf(self.display_photometry) if use_closed else None
+        e = nat.Eotf()
+        if desc is None:
+            if dtype == nat.FVVDP_F32:
+                raise RuntimeError("predict_images needs a display model with a closed form for float input "
+                                   "(a user photometry class works with predict())")
+            lut = self._code_lut(self.display_photometry, nbits)
+            e.kind, e.d_lut = nat.EOTF_LUT, lut.data_ptr()
+            e.L_min, e.L_max = self._lut_dev.table_range(lut)
+        else:
+            e.kind = desc[0]
+            e.Y_peak = desc[1].get("Y_peak", 0.0)
+            e.Y_black = desc[1].get("Y_black", 0.0)
+            e.gamma = desc[1].get("gamma", 1.0)
+            e.L_min = desc[1].get("L_min", 0.0)
+            e.L_max = desc[1].get("L_max", 0.0)
+        return dtype, e
+
+    def _predict_image_group(self, ts, rs, fix, sync, labels=None):
+        """Pairs of one shape ([C, H, W] tensors, host or device) -> (Q_JOD [n], stats).  Batches of up to _batch_size pairs:
+        per batch one ingest launch (fvvdp_images_channels), the pyramid launches, one finalisation and one pooling launch
+        (fvvdp_images_forward_pool); one device->host copy at the end when `sync`.  `fix`: [n, 2] gaze per pair (foveated
+        metric; None = the image centre).  `labels`: the number the out-of-range warning gives each pair (default: its index)."""
+        C_ch, height, width = ts[0].shape
+        B = len(ts)
+        if C_ch != 1 and C_ch != 3:
+            raise RuntimeError('The content must have either 1 or 3 colour channels.')
+        n_bands, rho_band = band_frequencies(width, height, self.pix_per_deg)
+        if n_bands < 1:
+            raise RuntimeError("Frame %dx%d is too small for this display (no band-pass level)" % (width, height))
+        if self.foveated and fix is None:
+            fix = self._fixation(None, width, height, B)
+        if self.do_heatmap and not sync:
+            raise RuntimeError("sync=False is not available together with heat-map output")
+        # every image on the device as one contiguous [C][H][W] array: resident contiguous images are read where they lie
+        dev = self.device
+        mixed = ts[0].dtype != rs[0].dtype
+        placed = []
+        for a in list(ts) + list(rs):
+            a = self._to_unit_float(a) if mixed else a.to(dev)
+            placed.append(a.contiguous())
+        td, rd = placed[:B], placed[B:]
+        dtype, e = self._image_eotf(td[0].dtype)
+        if e.kind == nat.EOTF_ABSOLUTE and dtype == nat.FVVDP_F32:
+            lo = torch.stack([torch.maximum(a.max(), b.max()) for a, b in zip(td, rd)]).max()
+            if float(lo) < 1:
+                logging.warning('Pixel values are very low. Perhaps images are not scaled in the absolute units of cd/m^2.')
+        w = self._rgb2y()
+        batch = self._batch_size(width, height, 2, B)
+        heatmap = None
+        if self.do_heatmap:
+            batch = max(1, min(batch, int(2e9 // (width * height * 4 * 12))))
+            heatmap = self._host_buffer([1, 1 if self.heatmap == "raw" else 3, B, height, width])
+        ctx = self._context(width, height, n_bands, 2, batch, rho_band)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nq = n_bands * 2 * B
+        res = torch.zeros(nq + 2 * B, dtype=torch.float32, device=dev)       # Q_per_ch | range flags (int32 bits) | JOD
+        Q = res[:nq].view(n_bands, 2, B)
+        flags = res[nq:nq + B].view(torch.int32)
+        jod = res[nq + B:]
+        pp = nat.PoolParams(self.beta_sch, self.beta_tch, self.beta_t, self.w_transient, self.jod_a,
+                            float(10.0 ** self.log_jod_exp))
+        lib = nat.lib()
+        for b0 in range(0, B, batch):
+            nb = min(batch, B - b0)
+            tp = (C.c_void_p * nb)(*[a.data_ptr() for a in td[b0:b0 + nb]])
+            rp = (C.c_void_p * nb)(*[a.data_ptr() for a in rd[b0:b0 + nb]])
+            nat.check(lib.fvvdp_images_channels(ctx.handle, tp, rp, nb, dtype, C_ch, height * width, C.byref(e), nat.fptr(w), 0,
+                                                C.c_void_p(flags.data_ptr() + 4 * b0), stream))
+            maps_arr, dmaps = None, None
+            if self.do_heatmap:
+                maps_arr = (nat.BandMaps * n_bands)()
+                dmaps = []
+                w_l, h_l = width, height
+                for b in range(n_bands):
+                    dmaps.append(torch.empty((nb, 2, h_l, w_l), dtype=torch.float32, device=dev))
+                    maps_arr[b].d_D = dmaps[b].data_ptr()
+                    w_l, h_l = (w_l + 1) // 2, (h_l + 1) // 2
+            fx, g = None, None
+            if self.foveated:
+                fxa = np.ascontiguousarray(fix[b0:b0 + nb], dtype=np.float32)
+                if native_geometry(self.display_geometry) is not None:
+                    g = C.byref(self._geom_struct())
+                else:
+                    self._set_view_maps(ctx, n_bands, width, height)
+                    fxa = self._gaze_view_dirs(fxa, width, height)
+                fx = nat.fptr(fxa)
+            nat.check(lib.fvvdp_images_forward_pool(ctx.handle, nb, C.c_void_p(Q.data_ptr()), B, b0, fx, g, maps_arr,
+                                                    C.byref(pp), C.c_void_p(jod.data_ptr() + 4 * b0), stream))
+            if self.do_heatmap:
+                self._heatmap_batch(ctx, nb, dmaps, 2, width, height, stream, heatmap, b0)
+        stats = {}
+        if sync:
+            res_h = self._to_host(res)
+            if self.do_heatmap and self._copy_stream is not None:
+                self._copy_stream.synchronize()
+            stats['Q_per_ch'] = np.ascontiguousarray(res_h[:nq].view(n_bands, 2, B).numpy().transpose(2, 0, 1))[..., None]
+            stats['range_flags'] = res_h[nq:nq + B].view(torch.int32).numpy() != 0
+            for k in np.nonzero(stats['range_flags'])[0]:
+                logging.warning("Pixel outside the valid range 0-1 (image pair %d)" % int(k if labels is None else labels[k]))
+        else:
+            stats['Q_per_ch'] = Q.permute(2, 0, 1).unsqueeze(-1)
+            stats['range_flags'] = flags
+            stats['result_buffer'] = res
+        stats['rho_band'] = rho_band
+        stats['frames_per_second'] = 0
+        stats['width'] = width
+        stats['height'] = height
+        if self.do_heatmap:
+            stats['heatmap'] = heatmap[0].permute(1, 0, 2, 3).unsqueeze(2)     # [B, ch, 1, H, W]
+        return jod, stats
+
+    def _rgb2y(self):
+        key = ("rgb2y", self.color_space)
+        if key not in self._filters:
+            cs = utils.config_files.load("color_spaces.json")
+            if self.color_space not in cs:
+                raise RuntimeError("Unknown color space: \"" + self.color_space + "\"")
+            self._filters[key] = np.asarray(cs[self.color_space]['RGB2Y'], dtype=np.float32)
+        return self._filters[key]
+
     @staticmethod
     def finish(stats):
         """Completes a `sync=False` result in place: device -> host copy of Q_per_ch (one synchronisation) and the
         reference's out-of-range warning."""
+        if isinstance(stats.get('Q_per_ch'), torch.Tensor) and 'range_flags' in stats:       # predict_images(..., sync=False)
+            flags = stats.pop('range_flags')
+            stats.pop('result_buffer', None)
+            q = stats['Q_per_ch']
+            both = torch.cat([q.reshape(-1), flags.view(torch.float32)]).cpu()
+            stats['Q_per_ch'] = both[:q.numel()].view(q.shape).numpy()
+            stats['range_flags'] = both[q.numel():].view(torch.int32).numpy() != 0
+            for k in np.nonzero(stats['range_flags'])[0]:
+                logging.warning("Pixel outside the valid range 0-1 (image pair %d)" % int(k))
+            return stats
         if isinstance(stats.get('Q_per_ch'), torch.Tensor):
             flag = stats.pop('range_flag', None)
             stats.pop('result_buffer', None)

@@ -1372,9 +1372,11 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
                 a.tickets = tickets ? c->d_ticket : nullptr;
                 const int n_wg = tickets ? ((n_items + n_items / 8 + 7) / 8 * 8) : n_items;
                 const dim3 grid2((unsigned int)n_wg), block2(64 * wpb);
-                if (c->env.debug_variant)                // tests: which variant was launched
-                    fprintf(stderr, "fvvdp: levels %d+%d: band2_kernel<%d, %s>, luminance range %s [%g, %g], widest plane range %g, %d waves per workgroup\n",
-                                 b, b + 1, c->P, inrange ? "true" : "false", c->lum_state == 1 ? "known" : "unknown", c->lum_lo, c->lum_hi, c->lum_width, wpb);
+                if (c->env.debug_variant)                // tests: which variant was launched, and its plan (strips, chunk heights in level-C rows)
+                    fprintf(stderr, "fvvdp: levels %d+%d: band2_kernel<%d, %s>, luminance range %s [%g, %g], widest plane range %g, %d waves per workgroup"
+                                    ", n_strips %d, kr %d, kr2 %d, n_big %d, n_chunks %d, tickets %s\n",
+                                 b, b + 1, c->P, inrange ? "true" : "false", c->lum_state == 1 ? "known" : "unknown", c->lum_lo, c->lum_hi, c->lum_width, wpb,
+                                 a.n_strips, a.kr, a.kr2, a.n_big, a.n_chunks, tickets ? "on" : "off");
                 if (c->P == 4) {
                     if (inrange) hipLaunchKernelGGL((band2_kernel<4, true>), grid2, block2, 0, st, a);
                     else hipLaunchKernelGGL((band2_kernel<4, false>), grid2, block2, 0, st, a);

@@ -9,7 +9,9 @@ Parity status: PINNED.  `tools/gen_golden.py` imports the real reference in the 
 stage captures under `tests/golden/`; `tests/test_oracle_golden.py` checks this file against them (<=1e-6
 relative per stage, 1e-5 on JOD) together with the README known answer 8.693 JOD (README.md:138).
 
-All arithmetic is float32 unless stated; quirks of the reference that change numbers are reproduced on purpose:
+All arithmetic is float32 unless stated.  `Oracle(..., dtype=np.float64)` (and the `dtype=` argument of the functions below)
+runs the same expressions in float64 end to end -- display model, CSF tables, pyramid taps and all -- as a high-precision yardstick
+for the GPU kernels; the float32 default is unchanged bit for bit.  Quirks of the reference that change numbers are reproduced on purpose:
   * `gausspyr_reduce` picks the right-edge fix-up of the horizontal pass by the parity of the ROW count
     (pyfvvdp/fvvdp_lpyr_dec.py:202),
   * `+1e-6` in the LUT interpolation denominator (pyfvvdp/interp.py:16),
@@ -38,14 +40,15 @@ def cache_key(omega, sigma, k_cm):
     return ("o%g_s%g_cm%f" % (omega, sigma, k_cm)).replace("-", "n").replace(".", "_")
 
 
-def load_lut(omega, sigma, k_cm):
+def load_lut(omega, sigma, k_cm, dtype=_F):
     """pyfvvdp/fvvdp.py:505-518 (the .mat content is shipped as fovvideovdp_amd/data/csf_lut.npz)."""
+    F = dtype
     z = np.load(os.path.join(_DATA, "csf_lut.npz"))
     key = cache_key(omega, sigma, k_cm)
     names = [n for n in z.files if n.startswith(key + "/")]
     if not names:
         raise RuntimeError("Error: cache file for %s not found" % key)
-    return {n.split("/", 1)[1]: z[n].astype(_F) for n in names}
+    return {n.split("/", 1)[1]: z[n].astype(F) for n in names}
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -54,12 +57,15 @@ def load_lut(omega, sigma, k_cm):
 class Photometry:
     """fvvdp_display_photo_eotf, pyfvvdp/fvvdp_display_model.py:114-176 (+ loader :52-98)."""
 
-    def __init__(self, Y_peak, contrast=1000, EOTF="sRGB", gamma=2.2, E_ambient=0, k_refl=0.005):
+    dtype = _F                 # working precision of forward()
+
+    def __init__(self, Y_peak, contrast=1000, EOTF="sRGB", gamma=2.2, E_ambient=0, k_refl=0.005, dtype=_F):
         self.Y_peak, self.contrast, self.EOTF = Y_peak, contrast, EOTF
+        self.dtype = dtype
         self.gamma, self.E_ambient, self.k_refl = gamma, E_ambient, k_refl
 
     @classmethod
-    def load(cls, display_name, models=None):
+    def load(cls, display_name, models=None, dtype=_F):
         models = models if models is not None else load_defaults()["display_models.json"]
         if display_name not in models:
             raise RuntimeError('Unknown display model: "' + display_name + '"')
@@ -72,7 +78,7 @@ class Photometry:
         else:
             contrast = 500
         return cls(Y_peak, contrast=contrast, EOTF=m.get("EOTF", "sRGB"), gamma=m.get("gamma", 2.2),
-                   E_ambient=m.get("E_ambient", 0), k_refl=m.get("k_refl", 0.005))
+                   E_ambient=m.get("E_ambient", 0), k_refl=m.get("k_refl", 0.005), dtype=dtype)
 
     def get_black_level(self):
         """:172-176"""
@@ -80,50 +86,56 @@ class Photometry:
 
     def forward(self, V):
         """:147-165.  Returns (L, out_of_range_flag)."""
-        V = np.asarray(V, dtype=_F)
+        F = self.dtype
+        V = np.asarray(V, dtype=F)
         oob = False
         if self.EOTF != "linear" and (np.any(V > 1) or np.any(V < 0)):
             oob = True
-            V = np.clip(V, _F(0.0), _F(1.0))
+            V = np.clip(V, F(0.0), F(1.0))
         Yb = self.get_black_level()
         if self.EOTF == "sRGB":
-            L = _F(self.Y_peak - Yb) * srgb2lin(V) + _F(Yb)
+            L = F(self.Y_peak - Yb) * srgb2lin(V, F) + F(Yb)
         elif self.EOTF == "gamma":
-            L = _F(self.Y_peak - Yb) * np.power(V, _F(self.gamma)) + _F(Yb)
+            L = F(self.Y_peak - Yb) * np.power(V, F(self.gamma)) + F(Yb)
         elif self.EOTF == "PQ":
-            L = np.clip(pq2lin(V), _F(0.005), _F(self.Y_peak)) + _F(Yb)
+            L = np.clip(pq2lin(V, F), F(0.005), F(self.Y_peak)) + F(Yb)
         elif self.EOTF == "linear":
-            L = np.clip(V, _F(0.005), _F(self.Y_peak)) + _F(Yb)
+            L = np.clip(V, F(0.005), F(self.Y_peak)) + F(Yb)
         else:
             raise RuntimeError("Unknown EOTF '%s'" % self.EOTF)
-        return L.astype(_F), oob
+        return L.astype(F), oob
 
 
-def srgb2lin(p):
+def srgb2lin(p, dtype=_F):
     """pyfvvdp/fvvdp_display_model.py:17-19"""
-    p = np.asarray(p, dtype=_F)
+    F = dtype
+    p = np.asarray(p, dtype=F)
     with np.errstate(invalid="ignore"):
-        hi = np.power((p + _F(0.055)) / _F(1.055), _F(2.4))
-    return np.where(p > _F(0.04045), hi, p / _F(12.92)).astype(_F)
+        hi = np.power((p + F(0.055)) / F(1.055), F(2.4))
+    return np.where(p > F(0.04045), hi, p / F(12.92)).astype(F)
 
 
-def pq2lin(V):
+def pq2lin(V, dtype=_F):
     """pyfvvdp/fvvdp_display_model.py:100-112"""
-    V = np.asarray(V, dtype=_F)
+    F = dtype
+    V = np.asarray(V, dtype=F)
     n, m = 0.15930175781250000, 78.843750000000000
     c1, c2, c3 = 0.83593750000000000, 18.851562500000000, 18.687500000000000
-    im_t = np.power(V, _F(1 / m))
-    L = _F(10000) * np.power(np.maximum(im_t - _F(c1), _F(0)) / (_F(c2) - _F(c3) * im_t), _F(1 / n))
-    return L.astype(_F)
+    im_t = np.power(V, F(1 / m))
+    L = F(10000) * np.power(np.maximum(im_t - F(c1), F(0)) / (F(c2) - F(c3) * im_t), F(1 / n))
+    return L.astype(F)
 
 
 # --------------------------------------------------------------------------------------------------------
 # display geometry  (pyfvvdp/fvvdp_display_model.py:383-568)
 # --------------------------------------------------------------------------------------------------------
 class Geometry:
+    dtype = _F                 # working precision of pix2view_direction / resolution_magnification
+
     def __init__(self, resolution, distance_m=None, distance_display_heights=None, fov_horizontal=None,
-                 fov_vertical=None, fov_diagonal=None, diagonal_size_inches=None):
+                 fov_vertical=None, fov_diagonal=None, diagonal_size_inches=None, dtype=_F):
         """:385-436"""
+        self.dtype = dtype
         self.resolution = resolution
         ar = resolution[0] / resolution[1]
         self.display_size_m = None
@@ -158,7 +170,7 @@ class Geometry:
         self.ppd_centre = 1 / (2 * math.degrees(math.atan(0.5 * self.display_size_m[0] / resolution[0] / self.distance_m)))
 
     @classmethod
-    def load(cls, display_name, models=None):
+    def load(cls, display_name, models=None, dtype=_F):
         """:539-568"""
         models = models if models is not None else load_defaults()["display_models.json"]
         if display_name not in models:
@@ -175,19 +187,20 @@ class Geometry:
             diag = m["diagonal_size_meters"] / 0.0254
         else:
             diag = m.get("diagonal_size_inches")
-        return cls((W, H), distance_m=distance_m, fov_diagonal=m.get("fov_diagonal"), diagonal_size_inches=diag)
+        return cls((W, H), distance_m=distance_m, fov_diagonal=m.get("fov_diagonal"), diagonal_size_inches=diag, dtype=dtype)
 
     def get_ppd(self):
         return self.ppd_centre
 
     def pix2view_direction(self, res, x_pix, y_pix):
         """:498-510  (fp32 like the reference when fed fp32 pixel coordinates)."""
-        x_rel = np.asarray(x_pix, dtype=_F) + _F(-res[0] / 2)
-        y_rel = np.asarray(y_pix, dtype=_F) + _F(-res[1] / 2)
-        x_m = x_rel * _F(self.display_size_m[0]) / _F(res[0])
-        y_m = -y_rel * _F(self.display_size_m[1]) / _F(res[1])
-        vx = np.rad2deg(np.arctan(x_m / _F(self.distance_m))).astype(_F)
-        vy = np.rad2deg(np.arctan(y_m / _F(self.distance_m))).astype(_F)
+        F = self.dtype
+        x_rel = np.asarray(x_pix, dtype=F) + F(-res[0] / 2)
+        y_rel = np.asarray(y_pix, dtype=F) + F(-res[1] / 2)
+        x_m = x_rel * F(self.display_size_m[0]) / F(res[0])
+        y_m = -y_rel * F(self.display_size_m[1]) / F(res[1])
+        vx = np.rad2deg(np.arctan(x_m / F(self.distance_m))).astype(F)
+        vy = np.rad2deg(np.arctan(y_m / F(self.distance_m))).astype(F)
         return vx, vy
 
     exact_geometry = False     # checker switch, see resolution_magnification
@@ -200,17 +213,18 @@ class Geometry:
         (tests only) evaluates the same expression in fp64 -- the value the fp32 expression scatters around -- so that
         an implementation that does not reproduce the reference's rounding noise bit for bit can still be pinned
         tightly."""
+        F = self.dtype
         if self.exact_geometry:
             va64 = np.minimum(np.sqrt(vx.astype(np.float64) ** 2 + vy.astype(np.float64) ** 2), 89.9)
             d64 = (1 / self.ppd_centre) / 2
-            return ((np.tan(np.deg2rad(va64 + d64)) - np.tan(np.deg2rad(va64))) / math.tan(math.radians(d64))).astype(_F)
-        va = np.sqrt(vx * vx + vy * vy).astype(_F)
-        va = np.minimum(va, _F(89.9))
+            return ((np.tan(np.deg2rad(va64 + d64)) - np.tan(np.deg2rad(va64))) / math.tan(math.radians(d64))).astype(F)
+        va = np.sqrt(vx * vx + vy * vy).astype(F)
+        va = np.minimum(va, F(89.9))
         delta = (1 / self.ppd_centre) / 2
         tan_delta = math.tan(math.radians(delta))
-        tan_a = np.tan(np.deg2rad(va)).astype(_F)
-        ppd = _F(self.ppd_centre) * (np.tan(np.deg2rad(va + _F(delta))).astype(_F) - tan_a) / _F(tan_delta)
-        return (ppd / _F(self.ppd_centre)).astype(_F)
+        tan_a = np.tan(np.deg2rad(va)).astype(F)
+        ppd = F(self.ppd_centre) * (np.tan(np.deg2rad(va + F(delta))).astype(F) - tan_a) / F(tan_delta)
+        return (ppd / F(self.ppd_centre)).astype(F)
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -226,68 +240,71 @@ def reshuffle_dims(T, in_dims, out_dims="BCFHW"):
     return Tp.reshape(out_sh)
 
 
-def frame_to_unit(arr_bcfhw, f):
+def frame_to_unit(arr_bcfhw, f, dtype=_F):
     """Integer/float unpacking of frame f -> fp32 in [0,1]  (pyfvvdp/video_source.py:184-200)."""
+    F = dtype
     fr = arr_bcfhw[:, :, f:f + 1]
     if fr.dtype == np.float32:
-        return fr.astype(_F)
+        return fr.astype(F)
     if fr.dtype == np.uint16:          # the reference carries it as int16 and masks; same value
-        return fr.astype(_F) / _F(65535)
+        return fr.astype(F) / F(65535)
     if fr.dtype == np.int16:
-        return (fr.astype(np.int32) & 0xFFFF).astype(_F) / _F(65535)
+        return (fr.astype(np.int32) & 0xFFFF).astype(F) / F(65535)
     if fr.dtype == np.uint8:
-        return fr.astype(_F) / _F(255)
+        return fr.astype(F) / F(255)
     raise RuntimeError("Only uint8, uint16 and float32 is currently supported")
 
 
-def frame_luminance(arr_bcfhw, f, photometry, rgb2y):
+def frame_luminance(arr_bcfhw, f, photometry, rgb2y, dtype=_F):
     """_get_frame: unpack -> photometry -> luminance  (pyfvvdp/video_source.py:180-208).  Returns ([H,W], oob)."""
-    V = frame_to_unit(arr_bcfhw, f)
+    F = dtype
+    V = frame_to_unit(arr_bcfhw, f, F)
     L, oob = photometry.forward(V)
     if L.shape[1] == 3:
-        L = L[:, 0:1] * _F(rgb2y[0]) + L[:, 1:2] * _F(rgb2y[1]) + L[:, 2:3] * _F(rgb2y[2])
-    return L[0, 0, 0].astype(_F), oob
+        L = L[:, 0:1] * F(rgb2y[0]) + L[:, 1:2] * F(rgb2y[1]) + L[:, 2:3] * F(rgb2y[2])
+    return L[0, 0, 0].astype(F), oob
 
 
-def torch_interpolate(img, out_h, out_w, mode):
+def torch_interpolate(img, out_h, out_w, mode, dtype=_F):
     """torch.nn.functional.interpolate(img[None], size=(out_h, out_w), mode=mode) for img [C,H,W] fp32 with the defaults the reference
     uses (align_corners=False, no antialiasing; pyfvvdp/video_source_file.py:240-242) -- a restatement of ATen's index arithmetic
     (aten/src/ATen/native/UpSample.h: area_pixel_compute_scale / _source_index, nearest_neighbor_compute_source_index,
     guard_index_and_lambda, get_cubic_upsample_coefficients with A = -0.75; adaptive average pooling for 'area')."""
-    img = np.asarray(img, dtype=_F)
+    F = dtype
+    img = np.asarray(img, dtype=F)
     C, H, W = img.shape
-    sy, sx = _F(H) / _F(out_h), _F(W) / _F(out_w)
-    oy, ox = np.arange(out_h, dtype=_F), np.arange(out_w, dtype=_F)
+    sy, sx = F(H) / F(out_h), F(W) / F(out_w)
+    oy, ox = np.arange(out_h, dtype=F), np.arange(out_w, dtype=F)
     if mode == "nearest":
         iy = np.minimum(np.floor(oy * sy).astype(np.int64), H - 1)
         ix = np.minimum(np.floor(ox * sx).astype(np.int64), W - 1)
-        return img[:, iy][:, :, ix].astype(_F)
+        return img[:, iy][:, :, ix].astype(F)
     if mode == "bilinear":
         def axis(o, s, n):
-            src = np.maximum(s * (o + _F(0.5)) - _F(0.5), _F(0)).astype(_F)
+            src = np.maximum(s * (o + F(0.5)) - F(0.5), F(0)).astype(F)
             i0 = np.minimum(src.astype(np.int64), n - 1)
             i1 = i0 + (i0 < n - 1)
-            l1 = np.clip(src - i0.astype(_F), 0, 1).astype(_F)
-            return i0, i1, (_F(1) - l1).astype(_F), l1
+            l1 = np.clip(src - i0.astype(F), 0, 1).astype(F)
+            return i0, i1, (F(1) - l1).astype(F), l1
         y0, y1, ly0, ly1 = axis(oy, sy, H)
         x0, x1, lx0, lx1 = axis(ox, sx, W)
         ly0, ly1 = ly0[None, :, None], ly1[None, :, None]
         top = lx0 * img[:, y0][:, :, x0] + lx1 * img[:, y0][:, :, x1]
         bot = lx0 * img[:, y1][:, :, x0] + lx1 * img[:, y1][:, :, x1]
-        return (ly0 * top + ly1 * bot).astype(_F)
+        return (ly0 * top + ly1 * bot).astype(F)
     if mode == "bicubic":
-        A = _F(-0.75)
+        A = F(-0.75)
 
         def coeffs(t):
-            cc1 = lambda x: ((A + _F(2)) * x - (A + _F(3))) * x * x + _F(1)
-            cc2 = lambda x: ((A * x - _F(5) * A) * x + _F(8) * A) * x - _F(4) * A
-            return [cc2(t + _F(1)), cc1(t), cc1(_F(1) - t), cc2(_F(2) - t)]
+            cc1 = lambda x: ((A + F(2)) * x - (A + F(3))) * x * x + F(1)
+            cc2 = lambda x: ((A * x - F(5) * A) * x + F(8) * A) * x - F(4) * A
+            return [cc2(t + F(1)), cc1(t), cc1(F(1) - t), cc2(F(2) - t)]
 
         def axis(o, s, n):
-            src = (s * (o + _F(0.5)) - _F(0.5)).astype(_F)             # cubic: the coordinate is NOT clamped, every tap index is
+            src = (s * (o + F(0.5)) - F(0.5)).astype(F)             # cubic: the coordinate is NOT clamped, every tap index is
             fl = np.floor(src)
             idx = [np.clip(fl.astype(np.int64) - 1 + k, 0, n - 1) for k in range(4)]
-            return idx, [c.astype(_F) for c in coeffs((src - fl).astype(_F))]
+            return idx, [c.astype(F) for c in coeffs((src - fl).astype(F))]
         ys, cy = axis(oy, sy, H)
         xs, cx = axis(ox, sx, W)
         out = None
@@ -296,53 +313,54 @@ def torch_interpolate(img, out_h, out_w, mode):
             row = ((rows[:, :, xs[0]] * cx[0] + rows[:, :, xs[1]] * cx[1]) + rows[:, :, xs[2]] * cx[2]) + rows[:, :, xs[3]] * cx[3]
             term = row * cy[k][None, :, None]
             out = term if out is None else out + term
-        return out.astype(_F)
+        return out.astype(F)
     if mode == "area":
         def win(o, n_in, n_out):
-            return (int(np.floor(_F(o * n_in) / _F(n_out))), int(np.ceil(_F((o + 1) * n_in) / _F(n_out))))
-        out = np.empty((C, out_h, out_w), dtype=_F)
+            return (int(np.floor(F(o * n_in) / F(n_out))), int(np.ceil(F((o + 1) * n_in) / F(n_out))))
+        out = np.empty((C, out_h, out_w), dtype=F)
         wy = [win(o, H, out_h) for o in range(out_h)]
         wx = [win(o, W, out_w) for o in range(out_w)]
         for j, (a0, a1) in enumerate(wy):
             for i, (b0, b1) in enumerate(wx):
-                out[:, j, i] = img[:, a0:a1, b0:b1].sum(axis=(1, 2), dtype=_F) / _F((a1 - a0) * (b1 - b0))
+                out[:, j, i] = img[:, a0:a1, b0:b1].sum(axis=(1, 2), dtype=F) / F((a1 - a0) * (b1 - b0))
         return out
     raise RuntimeError("Unknown resize method '%s'" % mode)
 
 
-def yuv_unpack(frame, W, H, bit_depth, chroma_ss, color_space, resize_fn=None, resize_hw=None):
+def yuv_unpack(frame, W, H, bit_depth, chroma_ss, color_space, resize_fn=None, resize_hw=None, dtype=_F):
     """video_reader_yuv_pytorch.unpack + _fixed2float_upscale, pyfvvdp/video_source_file.py:219-276.
     frame: 1-D uint8/uint16 (Y plane, U plane, V plane) -> RGB [H,W,3] fp32 in [0,1]; with resize_fn / resize_hw = (height, width):
     resized in RGB before the clip (:238-244)."""
+    F = dtype
     ypx = W * H
     uvh, uvw = (H // 2, W // 2) if chroma_ss == "420" else (H, W)
-    x = frame.astype(_F)
+    x = frame.astype(F)
     sc = 2 ** (bit_depth - 8)
-    Y = np.clip(_F(1 / (sc * 219)) * x[:ypx] - _F(16 / 219), 0, 1).reshape(H, W).astype(_F)                # :246-251
-    uv = np.clip(_F(1 / (sc * 224)) * x[ypx:] - _F(128 / 224), _F(-0.5), _F(0.5)).reshape(2, uvh, uvw).astype(_F)  # :253-258
+    Y = np.clip(F(1 / (sc * 219)) * x[:ypx] - F(16 / 219), 0, 1).reshape(H, W).astype(F)                # :246-251
+    uv = np.clip(F(1 / (sc * 224)) * x[ypx:] - F(128 / 224), F(-0.5), F(0.5)).reshape(2, uvh, uvw).astype(F)  # :253-258
     if chroma_ss == "420":                                                                             # :260-262
         # torch interpolate(scale_factor=2, mode='bilinear', align_corners=False): src = (dst+0.5)/2-0.5, clamped at 0
         def axis(n_out, n_in):
-            src = np.maximum((np.arange(n_out, dtype=_F) + _F(0.5)) * _F(0.5) - _F(0.5), _F(0))
+            src = np.maximum((np.arange(n_out, dtype=F) + F(0.5)) * F(0.5) - F(0.5), F(0))
             i0 = src.astype(np.int64)
             i1 = np.minimum(i0 + 1, n_in - 1)
-            f = (src - i0.astype(_F)).astype(_F)
+            f = (src - i0.astype(F)).astype(F)
             return i0, i1, f
         y0, y1, fy = axis(H, uvh)
         x0, x1, fx = axis(W, uvw)
         fy, fx = fy[None, :, None], fx[None, None, :]
-        top = (_F(1) - fx) * uv[:, y0][:, :, x0] + fx * uv[:, y0][:, :, x1]
-        bot = (_F(1) - fx) * uv[:, y1][:, :, x0] + fx * uv[:, y1][:, :, x1]
-        uv = ((_F(1) - fy) * top + fy * bot).astype(_F)
+        top = (F(1) - fx) * uv[:, y0][:, :, x0] + fx * uv[:, y0][:, :, x1]
+        bot = (F(1) - fx) * uv[:, y1][:, :, x0] + fx * uv[:, y1][:, :, x1]
+        uv = ((F(1) - fy) * top + fy * bot).astype(F)
     Yuv = np.stack((Y, uv[0], uv[1]), axis=-1)
     if color_space == "bt2020nc":                                                                      # :225-235
-        M = np.array([[1, 0, 1.47460], [1, -0.16455, -0.57135], [1, 1.88140, 0]], dtype=_F)
+        M = np.array([[1, 0, 1.47460], [1, -0.16455, -0.57135], [1, 1.88140, 0]], dtype=F)
     else:
-        M = np.array([[1, 0, 1.402], [1, -0.344136, -0.714136], [1, 1.772, 0]], dtype=_F)
-    RGB = (Yuv @ M.T).astype(_F)                                                                       # :237
+        M = np.array([[1, 0, 1.402], [1, -0.344136, -0.714136], [1, 1.772, 0]], dtype=F)
+    RGB = (Yuv @ M.T).astype(F)                                                                       # :237
     if resize_fn is not None and tuple(resize_hw) != (H, W):                                           # :238-243
-        RGB = torch_interpolate(RGB.transpose(2, 0, 1), resize_hw[0], resize_hw[1], resize_fn).transpose(1, 2, 0)
-    return np.clip(RGB, 0, 1).astype(_F)                                                                # :244
+        RGB = torch_interpolate(RGB.transpose(2, 0, 1), resize_hw[0], resize_hw[1], resize_fn, F).transpose(1, 2, 0)
+    return np.clip(RGB, 0, 1).astype(F)                                                                # :244
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -353,27 +371,28 @@ def filter_len(fps):
     return int(np.ceil(250.0 / (1000.0 / fps)))
 
 
-def temporal_filters(fps, sustained_sigma=0.5, sustained_beta=0.06, fl=None):
-    """pyfvvdp/fvvdp.py:609-630.  Returns F[2, fl] fp32."""
+def temporal_filters(fps, sustained_sigma=0.5, sustained_beta=0.06, fl=None, dtype=_F):
+    """pyfvvdp/fvvdp.py:609-630.  Returns F[2, fl] (fp32 by default)."""
+    F = dtype
     fl = filter_len(fps) if fl is None else fl
-    t = np.linspace(0.0, fl / fps, fl, dtype=np.float64).astype(_F)   # torch.linspace(fp32)
+    t = np.linspace(0.0, fl / fps, fl, dtype=np.float64).astype(F)   # torch.linspace(fp32)
     # torch computes start + i*step in fp32; reproduce that rather than numpy's fp64 path
-    step = _F((_F(fl / fps) - _F(0.0)) / _F(fl - 1)) if fl > 1 else _F(0)
+    step = F((F(fl / fps) - F(0.0)) / F(fl - 1)) if fl > 1 else F(0)
     half = fl // 2
     idx = np.arange(fl)
-    t_lo = (_F(0.0) + step * idx.astype(_F)).astype(_F)
-    t_hi = (_F(fl / fps) - step * (fl - 1 - idx).astype(_F)).astype(_F)
-    t = np.where(idx < half, t_lo, t_hi).astype(_F)
-    F = np.zeros((2, fl), dtype=_F)
-    sigma, beta = _F(sustained_sigma), _F(sustained_beta)
-    e = -np.power(np.log(t + _F(1e-4)) - np.log(beta), _F(2.0)) / (_F(2.0) * (sigma ** _F(2.0)))
-    F[0] = np.exp(e.astype(_F))
-    F[0] = F[0] / np.sum(F[0], dtype=_F)
+    t_lo = (F(0.0) + step * idx.astype(F)).astype(F)
+    t_hi = (F(fl / fps) - step * (fl - 1 - idx).astype(F)).astype(F)
+    t = np.where(idx < half, t_lo, t_hi).astype(F)
+    taps = np.zeros((2, fl), dtype=F)
+    sigma, beta = F(sustained_sigma), F(sustained_beta)
+    e = -np.power(np.log(t + F(1e-4)) - np.log(beta), F(2.0)) / (F(2.0) * (sigma ** F(2.0)))
+    taps[0] = np.exp(e.astype(F))
+    taps[0] = taps[0] / np.sum(taps[0], dtype=F)
     k2 = 0.062170507756932
-    Fdiff = F[0, 1:] - F[0, :-1]
-    F[1, :-1] = _F(k2) * (Fdiff / (t[1] - t[0]))
-    F[1, -1] = 0
-    return F
+    Fdiff = taps[0, 1:] - taps[0, :-1]
+    taps[1, :-1] = F(k2) * (Fdiff / (t[1] - t[0]))
+    taps[1, -1] = 0
+    return taps
 
 
 def window_frame_indices(N, fl, temp_padding):
@@ -403,14 +422,15 @@ def window_frame_indices(N, fl, temp_padding):
     return idx
 
 
-def temporal_channels(win_T, win_R, F):
-    """R[2cc+s] = sum_k win[s][k] * F[cc][fl-1-k]   (pyfvvdp/fvvdp.py:294-300).  win_*: [fl,H,W] oldest first."""
+def temporal_channels(win_T, win_R, taps, dtype=_F):
+    """R[2cc+s] = sum_k win[s][k] * taps[cc][fl-1-k]   (pyfvvdp/fvvdp.py:294-300).  win_*: [fl,H,W] oldest first."""
+    F = dtype
     H, W = win_T.shape[-2:]
-    R = np.zeros((4, H, W), dtype=_F)
+    R = np.zeros((4, H, W), dtype=F)
     for cc in range(2):
-        corr = F[cc][::-1].reshape(-1, 1, 1).astype(_F)
-        R[2 * cc + 0] = np.sum(win_T * corr, axis=0, dtype=_F)
-        R[2 * cc + 1] = np.sum(win_R * corr, axis=0, dtype=_F)
+        corr = taps[cc][::-1].reshape(-1, 1, 1).astype(F)
+        R[2 * cc + 0] = np.sum(win_T * corr, axis=0, dtype=F)
+        R[2 * cc + 1] = np.sum(win_R * corr, axis=0, dtype=F)
     return R
 
 
@@ -431,20 +451,22 @@ def band_frequencies(W, H, ppd):
 _K = np.array([0.25 - 0.4 / 2.0, 0.25, 0.4, 0.25, 0.25 - 0.4 / 2.0]).astype(_F)   # :176 built in fp32 by torch.tensor
 
 
-def _k():
-    # torch.tensor([...python floats...], dtype=float32): each entry rounded from fp64
-    return np.array([0.25 - 0.4 / 2.0, 0.25, 0.4, 0.25, 0.25 - 0.4 / 2.0], dtype=np.float64).astype(_F)
+def _k(dtype=_F):
+    # torch.tensor([...python floats...], dtype=float32): each entry rounded from fp64 (kept exact in float64 mode)
+    F = dtype
+    return np.array([0.25 - 0.4 / 2.0, 0.25, 0.4, 0.25, 0.25 - 0.4 / 2.0], dtype=np.float64).astype(F)
 
 
-def gausspyr_reduce(x):
+def gausspyr_reduce(x, dtype=_F):
     """pyfvvdp/fvvdp_lpyr_dec.py:183-207.  x: [P,H,W] fp32 -> [P,ceil(H/2),ceil(W/2)]."""
-    K = _k()
+    F = dtype
+    K = _k(F)
     P, H, W = x.shape
     Ho, Wo = (H + 1) // 2, (W + 1) // 2
     # vertical: zero-padded 5-tap, stride 2  (:188)
-    xp = np.zeros((P, H + 4 + 1, W), dtype=_F)
+    xp = np.zeros((P, H + 4 + 1, W), dtype=F)
     xp[:, 2:2 + H] = x
-    ya = np.zeros((P, Ho, W), dtype=_F)
+    ya = np.zeros((P, Ho, W), dtype=F)
     for k in range(5):
         ya += K[k] * xp[:, k:k + 2 * Ho:2]
     ya[:, 0] += x[:, 0] * K[1] + x[:, 1] * K[0]                     # :191
@@ -453,9 +475,9 @@ def gausspyr_reduce(x):
     else:
         ya[:, -1] += x[:, -1] * K[4]
     # horizontal on the result (:198)
-    yp = np.zeros((P, Ho, W + 4 + 1), dtype=_F)
+    yp = np.zeros((P, Ho, W + 4 + 1), dtype=F)
     yp[:, :, 2:2 + W] = ya
-    y = np.zeros((P, Ho, Wo), dtype=_F)
+    y = np.zeros((P, Ho, Wo), dtype=F)
     for k in range(5):
         y += K[k] * yp[:, :, k:k + 2 * Wo:2]
     y[:, :, 0] += ya[:, :, 0] * K[1] + ya[:, :, 1] * K[0]           # :201
@@ -466,13 +488,14 @@ def gausspyr_reduce(x):
     return y
 
 
-def _expand_axis(x, n_out, axis):
+def _expand_axis(x, n_out, axis, dtype=_F):
     """One axis of gausspyr_expand: zero-stuff, edge pad, valid conv with 2K (:126-142, :225-233).
 
     Closed form: even i -> 2K0*x[c-1] + 2K2*x[c] + 2K4*x[c+1] (c=i/2), odd i -> 2K1*x[(i-1)/2] + 2K3*x[(i+1)/2],
     neighbour indices clamped to the valid range.
     """
-    K2 = (_k() * _F(2)).astype(_F)
+    F = dtype
+    K2 = (_k(F) * F(2)).astype(F)
     x = np.moveaxis(x, axis, -1)
     n = x.shape[-1]
     i = np.arange(n_out)
@@ -481,37 +504,40 @@ def _expand_axis(x, n_out, axis):
     c0 = np.clip(c, 0, n - 1)
     even = (K2[0] * x[..., cm] + K2[2] * x[..., c0]) + K2[4] * x[..., cp]
     odd = K2[1] * x[..., c0] + K2[3] * x[..., cp]
-    out = np.where((i % 2) == 0, even, odd).astype(_F)
+    out = np.where((i % 2) == 0, even, odd).astype(F)
     return np.moveaxis(out, -1, axis)
 
 
-def gausspyr_expand(x, sz):
+def gausspyr_expand(x, sz, dtype=_F):
     """pyfvvdp/fvvdp_lpyr_dec.py:219-235: vertical first, then horizontal."""
-    return _expand_axis(_expand_axis(x, sz[0], -2), sz[1], -1)
+    F = dtype
+    return _expand_axis(_expand_axis(x, sz[0], -2, F), sz[1], -1, F)
 
 
-def gaussian_pyramid(image, levels):
+def gaussian_pyramid(image, levels, dtype=_F):
     """pyfvvdp/fvvdp_lpyr_dec.py:144-158"""
+    F = dtype
     res = [image]
     for _ in range(1, levels):
-        res.append(gausspyr_reduce(res[-1]))
+        res.append(gausspyr_reduce(res[-1], F))
     return res
 
 
-def contrast_pyr_decompose(image, height):
+def contrast_pyr_decompose(image, height, dtype=_F):
     """fvvdp_contrast_pyr.decompose  pyfvvdp/fvvdp_lpyr_dec.py:248-273.  image: [P,H,W].
 
     Returns (contrast bands (list of [P,h,w], base band last), L_bkg bands (list of [h,w])).
     """
-    gpyr = gaussian_pyramid(image, height + 1)
+    F = dtype
+    gpyr = gaussian_pyramid(image, height + 1, F)
     lpyr, lbkg = [], []
     for i in range(len(gpyr) - 1):
-        ex = gausspyr_expand(gpyr[i + 1], gpyr[i].shape[-2:])
+        ex = gausspyr_expand(gpyr[i + 1], gpyr[i].shape[-2:], F)
         layer = gpyr[i] - ex
-        L_bkg = np.maximum(ex[1], _F(0.1))                                   # :265 plane 1 = reference(-sustained)
-        contrast = np.minimum(layer / L_bkg[None], _F(1000.0))               # :266
-        lpyr.append(contrast.astype(_F))
-        lbkg.append(L_bkg.astype(_F))
+        L_bkg = np.maximum(ex[1], F(0.1))                                   # :265 plane 1 = reference(-sustained)
+        contrast = np.minimum(layer / L_bkg[None], F(1000.0))               # :266
+        lpyr.append(contrast.astype(F))
+        lbkg.append(L_bkg.astype(F))
     lpyr.append(gpyr[-1])
     return lpyr, lbkg
 
@@ -519,78 +545,84 @@ def contrast_pyr_decompose(image, height):
 # --------------------------------------------------------------------------------------------------------
 # CSF LUT interpolation  (pyfvvdp/interp.py, pyfvvdp/fvvdp.py:520-537)
 # --------------------------------------------------------------------------------------------------------
-def get_interpolants_v1(x_q, x):
+def get_interpolants_v1(x_q, x, dtype=_F):
     """pyfvvdp/interp.py:11-20"""
+    F = dtype
     imax = np.searchsorted(x, x_q, side="left")          # torch.bucketize(right=False): first x[i] >= q
     imax = np.minimum(imax, x.shape[0] - 1)
     imin = np.clip(imax - 1, 0, x.shape[0] - 1)
-    ifrc = (x_q - x[imin]) / (x[imax] - x[imin] + _F(0.000001))
-    ifrc = np.where(imax == imin, _F(0), ifrc)
-    ifrc = np.where(ifrc < 0, _F(0), ifrc).astype(_F)
+    ifrc = (x_q - x[imin]) / (x[imax] - x[imin] + F(0.000001))
+    ifrc = np.where(imax == imin, F(0), ifrc)
+    ifrc = np.where(ifrc < 0, F(0), ifrc).astype(F)
     return imin, imax, ifrc
 
 
-def interp3(x, y, z, v, x_q, y_q, z_q):
+def interp3(x, y, z, v, x_q, y_q, z_q, dtype=_F):
     """pyfvvdp/interp.py:43-59  (v indexed [y, x, z])."""
+    F = dtype
     shp = x_q.shape
     x_q, y_q, z_q = x_q.ravel(), y_q.ravel(), z_q.ravel()
-    imin, imax, ifrc = get_interpolants_v1(x_q, x)
-    jmin, jmax, jfrc = get_interpolants_v1(y_q, y)
-    kmin, kmax, kfrc = get_interpolants_v1(z_q, z)
-    one = _F(1.0)
+    imin, imax, ifrc = get_interpolants_v1(x_q, x, F)
+    jmin, jmax, jfrc = get_interpolants_v1(y_q, y, F)
+    kmin, kmax, kfrc = get_interpolants_v1(z_q, z, F)
+    one = F(1.0)
     filtered = (
         ((v[jmin, imin, kmin] * (one - ifrc) + v[jmin, imax, kmin] * ifrc) * (one - jfrc) +
          (v[jmax, imin, kmin] * (one - ifrc) + v[jmax, imax, kmin] * ifrc) * jfrc) * (one - kfrc) +
         ((v[jmin, imin, kmax] * (one - ifrc) + v[jmin, imax, kmax] * ifrc) * (one - jfrc) +
          (v[jmax, imin, kmax] * (one - ifrc) + v[jmax, imax, kmax] * ifrc) * jfrc) * kfrc)
-    return filtered.reshape(shp).astype(_F)
+    return filtered.reshape(shp).astype(F)
 
 
-def cached_sensitivity(lut, rho, L_bkg, ecc):
+def cached_sensitivity(lut, rho, L_bkg, ecc, dtype=_F):
     """pyfvvdp/fvvdp.py:520-537.  rho, L_bkg, ecc broadcastable fp32 arrays -> S."""
-    rho, L_bkg, ecc = np.broadcast_arrays(np.asarray(rho, _F), np.asarray(L_bkg, _F), np.asarray(ecc, _F))
-    rho_q = np.log2(np.clip(rho, lut["rho"][0], lut["rho"][-1])).astype(_F)
-    Y_q = np.log2(np.clip(L_bkg, lut["Y"][0], lut["Y"][-1])).astype(_F)
-    ecc_q = np.sqrt(np.clip(ecc, lut["ecc"][0], lut["ecc"][-1])).astype(_F)
-    interpolated = interp3(lut["rho_log"], lut["Y_log"], lut["ecc_sqrt"], lut["S_log"], rho_q, Y_q, ecc_q)
-    return np.power(_F(2.0), interpolated).astype(_F)
+    F = dtype
+    rho, L_bkg, ecc = np.broadcast_arrays(np.asarray(rho, F), np.asarray(L_bkg, F), np.asarray(ecc, F))
+    rho_q = np.log2(np.clip(rho, lut["rho"][0], lut["rho"][-1])).astype(F)
+    Y_q = np.log2(np.clip(L_bkg, lut["Y"][0], lut["Y"][-1])).astype(F)
+    ecc_q = np.sqrt(np.clip(ecc, lut["ecc"][0], lut["ecc"][-1])).astype(F)
+    interpolated = interp3(lut["rho_log"], lut["Y_log"], lut["ecc_sqrt"], lut["S_log"], rho_q, Y_q, ecc_q, F)
+    return np.power(F(2.0), interpolated).astype(F)
 
 
 # --------------------------------------------------------------------------------------------------------
 # masking, pooling, JOD  (pyfvvdp/fvvdp.py:337-357, 574-607)
 # --------------------------------------------------------------------------------------------------------
-def apply_masking_model(T, R, N, cc, prm):
+def apply_masking_model(T, R, N, cc, prm, dtype=_F):
     """pyfvvdp/fvvdp.py:574-596 with phase_uncertainty :550-556 (pu_dilate=0) and mask_func_perc_norm2 :569-572."""
-    p = _F(prm["mask_p"])
-    q = _F(prm["mask_q_sust"] if cc == 0 else prm["mask_q_trans"])
+    F = dtype
+    p = F(prm["mask_p"])
+    q = F(prm["mask_q_sust"] if cc == 0 else prm["mask_q_trans"])
     T = T / N
     R = R / N
-    k = np.power(_F(10.0), _F(prm["mask_c"]))
+    k = np.power(F(10.0), F(prm["mask_c"]))
     M = np.minimum(np.abs(T), np.abs(R)) * k
-    D = np.power(np.abs(T - R), p) / (_F(1.0) + np.power(M, q))
-    return np.minimum(D, _F(1e4)).astype(_F)
+    D = np.power(np.abs(T - R), p) / (F(1.0) + np.power(M, q))
+    return np.minimum(D, F(1e4)).astype(F)
 
 
-def lp_norm(x, p, axis=0, normalize=True):
+def lp_norm(x, p, axis=0, normalize=True, dtype=_F):
     """pyfvvdp/fvvdp.py:598-607 (torch.norm accumulates wider than fp32 on CPU; fp64 here)."""
+    F = dtype
     N = x.shape[axis] if normalize else 1.0
     s = np.sum(np.power(np.abs(x.astype(np.float64)), p), axis=axis, keepdims=True)
-    return (np.power(s, 1.0 / p) / (float(N) ** (1.0 / p))).astype(_F)
+    return (np.power(s, 1.0 / p) / (float(N) ** (1.0 / p))).astype(F)
 
 
-def do_pooling_and_jods(Q_per_ch, prm):
+def do_pooling_and_jods(Q_per_ch, prm, dtype=_F):
     """pyfvvdp/fvvdp.py:337-357.  Q_per_ch: [height, 2, N]."""
+    F = dtype
     if Q_per_ch.shape[1] == 2:
-        w = np.array([1.0, prm["w_transient"]], dtype=_F).reshape(1, 2, 1)
+        w = np.array([1.0, prm["w_transient"]], dtype=F).reshape(1, 2, 1)
     else:
-        w = _F(1)
-    Q_sc = lp_norm(Q_per_ch * w, prm["beta_sch"], 0, False)
-    Q_tc = lp_norm(Q_sc, prm["beta_tch"], 1, False)
-    Q = float(lp_norm(Q_tc, prm["beta_t"], 2, True).squeeze())
+        w = F(1)
+    Q_sc = lp_norm(Q_per_ch * w, prm["beta_sch"], 0, False, F)
+    Q_tc = lp_norm(Q_sc, prm["beta_tch"], 1, False, F)
+    Q = float(lp_norm(Q_tc, prm["beta_t"], 2, True, F).squeeze())
     beta_jod = 10.0 ** prm["log_jod_exp"]
     a = prm["jod_a"]
     sign = -1 if a < 0 else 1
-    return _F(sign * ((abs(a) ** (1.0 / beta_jod)) * _F(Q)) ** beta_jod + 10.0)
+    return F(sign * ((abs(a) ** (1.0 / beta_jod)) * F(Q)) ** beta_jod + 10.0)
 
 
 # --------------------------------------------------------------------------------------------------------
@@ -638,44 +670,46 @@ class Oracle:
     """Mirror of `class fvvdp` restricted to the live branch (local_adapt=gpyr, contrast=weber, pu_dilate=0)."""
 
     def __init__(self, display_name="standard_4k", photometry=None, geometry=None, color_space="sRGB",
-                 foveated=False, temp_padding="replicate", heatmap=None):
+                 foveated=False, temp_padding="replicate", heatmap=None, dtype=_F):
         if heatmap not in (None, "raw"):
             raise RuntimeError("the oracle restates the 'raw' difference map only (the colouring is a function of it and the context frame)")
         self.heatmap = heatmap
+        self.dtype = dtype             # working precision: np.float32 (the reference's) or np.float64 (a high-precision yardstick)
         d = load_defaults()
         self.prm = d["fvvdp_parameters.json"]
-        self.photometry = photometry if photometry is not None else Photometry.load(display_name, d["display_models.json"])
-        self.geometry = geometry if geometry is not None else Geometry.load(display_name, d["display_models.json"])
+        self.photometry = photometry if photometry is not None else Photometry.load(display_name, d["display_models.json"], dtype)
+        self.geometry = geometry if geometry is not None else Geometry.load(display_name, d["display_models.json"], dtype)
         if color_space not in d["color_spaces.json"]:
             raise RuntimeError('Unknown color space: "' + color_space + '"')
         self.rgb2y = d["color_spaces.json"][color_space]["RGB2Y"]
         self.foveated = foveated
         self.temp_padding = temp_padding
         self.ppd = self.geometry.get_ppd()
-        self.lut = [load_lut(om, self.prm["csf_sigma"], self.prm["k_cm"]) for om in (0, 5)]
+        self.lut = [load_lut(om, self.prm["csf_sigma"], self.prm["k_cm"], dtype) for om in (0, 5)]
         self.capture = None            # optional dict of lists filled with stage outputs
 
     # -- foveated maps, pyfvvdp/fvvdp.py:416-437 ----------------------------------------------------------
     def _fov_maps(self, w_band, h_band, w_frame, h_frame, fix):
-        xv = np.linspace(0.5, w_band - 0.5, w_band).astype(_F)
-        yv = np.linspace(0.5, h_band - 0.5, h_band).astype(_F)
+        F = self.dtype
+        xv = np.linspace(0.5, w_band - 0.5, w_band).astype(F)
+        yv = np.linspace(0.5, h_band - 0.5, h_band).astype(F)
         xx, yy = np.meshgrid(xv, yv, indexing="xy")
         vx, vy = self.geometry.pix2view_direction((w_band, h_band), xx, yy)
-        gx, gy = self.geometry.pix2view_direction((w_frame, h_frame), _F(fix[0]) + _F(0.5), _F(fix[1]) + _F(0.5))
-        ecc = np.sqrt((vx - gx) ** 2 + (vy - gy) ** 2).astype(_F)
+        gx, gy = self.geometry.pix2view_direction((w_frame, h_frame), F(fix[0]) + F(0.5), F(fix[1]) + F(0.5))
+        ecc = np.sqrt((vx - gx) ** 2 + (vy - gy) ** 2).astype(F)
         res_mag = self.geometry.resolution_magnification(vx, vy)
         return ecc, res_mag
 
     def process_frame(self, ff, R, height, rho_band, temp_ch, fixation, frame_size):
         """process_block_of_frames, pyfvvdp/fvvdp.py:359-478.  R: [P,H,W].  Returns Q[height,2]."""
-        prm = self.prm
-        bands, lbkg = contrast_pyr_decompose(R, height)
-        Q = np.zeros((height, 2), dtype=_F)
+        prm, F = self.prm, self.dtype
+        bands, lbkg = contrast_pyr_decompose(R, height, F)
+        Q = np.zeros((height, 2), dtype=F)
         dmap_bands = [None] * height
-        sens = _F(10.0 ** (prm["sensitivity_correction"] / 20.0))
+        sens = F(10.0 ** (prm["sensitivity_correction"] / 20.0))
         for cc in range(temp_ch):
             for bb in range(height):
-                m = _F(1.0 if bb == 0 else 2.0)                       # get_band, fvvdp_lpyr_dec.py:57-63
+                m = F(1.0 if bb == 0 else 2.0)                       # get_band, fvvdp_lpyr_dec.py:57-63
                 T_f = bands[bb][2 * cc + 0] * m
                 R_f = bands[bb][2 * cc + 1] * m
                 L_bkg = lbkg[bb]
@@ -684,29 +718,29 @@ class Oracle:
                     fix = fixation[ff] if np.ndim(fixation) == 2 else fixation
                     ecc, res_mag = self._fov_maps(w, h, frame_size[1], frame_size[0], fix)
                 else:
-                    res_mag = np.ones((h, w), dtype=_F)
-                    ecc = np.zeros((h, w), dtype=_F)
-                rho = (_F(rho_band[bb]) * res_mag).astype(_F)         # fvvdp.py:442 (numpy fp64 scalar * fp32 tensor -> fp32)
-                S_raw = cached_sensitivity(self.lut[cc], rho, L_bkg, ecc)
+                    res_mag = np.ones((h, w), dtype=F)
+                    ecc = np.zeros((h, w), dtype=F)
+                rho = (F(rho_band[bb]) * res_mag).astype(F)         # fvvdp.py:442 (numpy fp64 scalar * fp32 tensor -> fp32)
+                S_raw = cached_sensitivity(self.lut[cc], rho, L_bkg, ecc, F)
                 S = S_raw * sens                                      # fvvdp.py:447
-                N_nCSF = (_F(1.0) / S).astype(_F)                     # fvvdp.py:451
-                D = apply_masking_model(T_f, R_f, N_nCSF, cc, prm)
+                N_nCSF = (F(1.0) / S).astype(F)                     # fvvdp.py:451
+                D = apply_masking_model(T_f, R_f, N_nCSF, cc, prm, F)
                 if self.capture is not None:
                     self.capture.setdefault("S", []).append(S_raw)
                     self.capture.setdefault("D", []).append(D)
-                Q[bb, cc] = lp_norm(D.ravel(), prm["beta"], 0, True)[0]
+                Q[bb, cc] = lp_norm(D.ravel(), prm["beta"], 0, True, F)[0]
                 if self.heatmap is not None:                          # fvvdp.py:458-462 with set_band / get_band, fvvdp_lpyr_dec.py:57-71
                     if cc == 0:
-                        dmap_bands[bb] = (D / m).astype(_F)
+                        dmap_bands[bb] = (D / m).astype(F)
                     else:
-                        dmap_bands[bb] = ((dmap_bands[bb] * m + _F([1.0, prm["w_transient"]][cc]) * D) / m).astype(_F)
+                        dmap_bands[bb] = ((dmap_bands[bb] * m + F([1.0, prm["w_transient"]][cc]) * D) / m).astype(F)
         if self.heatmap is not None:
             # heatmap_pyr.reconstruct (fvvdp_lpyr_dec.py:96-103) from the base band of a decomposed zero image, then fvvdp.py:468-470
             img = np.zeros_like(bands[height][0])
             for i in reversed(range(height)):
-                img = (gausspyr_expand(img, dmap_bands[i].shape) + dmap_bands[i]).astype(_F)
+                img = (gausspyr_expand(img, dmap_bands[i].shape, F) + dmap_bands[i]).astype(F)
             beta_jod = np.float64(10.0) ** prm["log_jod_exp"]
-            self.last_dmap = (np.power(img, _F(beta_jod)) * _F(abs(prm["jod_a"]))).astype(_F).astype(np.float16)
+            self.last_dmap = (np.power(img, F(beta_jod)) * F(abs(prm["jod_a"]))).astype(F).astype(np.float16)
         if self.capture is not None:
             self.capture.setdefault("bands", []).append(bands)
             self.capture.setdefault("L_bkg", []).append(lbkg)
@@ -721,7 +755,7 @@ class Oracle:
         rhw = None if full_screen_resize is None else (int(resize_resolution[1]), int(resize_resolution[0]))
 
         def to_rgb(arr):
-            vid = np.stack([yuv_unpack(arr[f], W, H, bit_depth, chroma_ss, color_space, full_screen_resize, rhw)
+            vid = np.stack([yuv_unpack(arr[f], W, H, bit_depth, chroma_ss, color_space, full_screen_resize, rhw, self.dtype)
                             for f in range(arr.shape[0])], 0)
             return np.ascontiguousarray(vid.transpose(3, 0, 1, 2)[None])           # [1,3,N,H,W] fp32
         return self.predict(to_rgb(np.asarray(test_yuv)), to_rgb(np.asarray(ref_yuv)), "BCFHW", frames_per_second,
@@ -733,6 +767,7 @@ class Oracle:
         `frames` (optional iterable) restricts the OUTPUT frames that are evaluated (used for bounded CPU
         timing); pooling then runs over those frames only.
         """
+        F = self.dtype
         test = reshuffle_dims(np.asarray(test), dim_order)
         ref = reshuffle_dims(np.asarray(ref), dim_order)
         if test.shape != ref.shape:
@@ -753,36 +788,36 @@ class Oracle:
         def lum(arr, tag, f):
             nonlocal oob
             if (tag, f) not in lum_cache:
-                L, o = frame_luminance(arr, f, self.photometry, self.rgb2y)
+                L, o = frame_luminance(arr, f, self.photometry, self.rgb2y, F)
                 oob = oob or o
                 lum_cache[(tag, f)] = L
             return lum_cache[(tag, f)]
 
         out_frames = list(range(N)) if frames is None else list(frames)
-        Q_per_ch = np.zeros((height, 2, len(out_frames)), dtype=_F)
+        Q_per_ch = np.zeros((height, 2, len(out_frames)), dtype=F)
         heat = np.zeros((1, 1, len(out_frames), H, W), dtype=np.float16) if self.heatmap is not None else None
         if is_image:
             temp_ch = 1
         else:
             temp_ch = 2
             fl = filter_len(frames_per_second)
-            F = temporal_filters(frames_per_second, self.prm["sustained_sigma"], self.prm["sustained_beta"], fl)
+            taps = temporal_filters(frames_per_second, self.prm["sustained_sigma"], self.prm["sustained_beta"], fl, F)
             widx = window_frame_indices(N, fl, self.temp_padding)
-            self.F = F
+            self.F = taps
         for oi, ff in enumerate(out_frames):
             if is_image:
                 R = np.stack([lum(test, "t", 0), lum(ref, "r", 0)], 0)
             else:
                 win_T = np.stack([lum(test, "t", int(j)) for j in widx[ff]], 0)
                 win_R = np.stack([lum(ref, "r", int(j)) for j in widx[ff]], 0)
-                R = temporal_channels(win_T, win_R, F)
+                R = temporal_channels(win_T, win_R, taps, F)
                 keep = set(int(j) for j in widx[min(ff + 1, N - 1)])
                 for key in [k for k in lum_cache if k[1] not in keep]:
                     del lum_cache[key]
             Q_per_ch[:, :, oi] = self.process_frame(ff, R, height, rho_band, temp_ch, fixation_point, (H, W))
             if heat is not None:
                 heat[0, 0, oi] = self.last_dmap
-        jod = do_pooling_and_jods(Q_per_ch, self.prm)
+        jod = do_pooling_and_jods(Q_per_ch, self.prm, F)
         stats = {"Q_per_ch": Q_per_ch, "rho_band": rho_band, "frames_per_second": frames_per_second,
                  "width": W, "height": H, "N_frames": N, "oob": oob}
         if heat is not None:

@@ -19,5 +19,5 @@ for k in 0 1 2 3; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=$C/exports.map $R/build_variants/obj/$NAME.main.o $PARTS -o $R/build_variants/$NAME.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=$C/exports.map $R/build_variants/obj/$NAME.main.o $PARTS $C/_build/still_launch.o -o $R/build_variants/$NAME.so
 echo built $R/build_variants/$NAME.so

@@ -15,10 +15,13 @@ other decomposition of north_star: ONE pair of `--frames` x N frames whose outpu
 value = Mpixels/s (test+ref) = 2*W*H*frames of a step / median step seconds.
 
   python bench.py [--gpus N --steps K --warmup W --pairs-per-gpu P --shard pairs|frames --config 1|2|3 --collective auto|off|force
-                  --dump-outputs DIR]
+                  --dump-outputs DIR --full]
   (N>1: launched by torch.distributed.run)
 
 ONE JSON line on rank 0's stdout and nothing else (file descriptor 1 is pointed at stderr while the process runs: librccl prints a banner).
+A plain run does only what the headline needs: set-up, the warm-up and timed steps, `--dump-outputs`, the line.  `--full` adds, after
+the timed steps, every other figure and check: `predict_call_ms`, `collective`, the per-kernel rooflines and `level0_alloc`,
+`value_h2d_inclusive`, `cpu_baseline` and `jod_delta_vs_reference` (null or absent in a plain run).  What they are:
 `roofline`: the dominant kernel (two-level pyramid kernel, levels 0+1), timed per launch with HIP events inside the library on the kernels'
 stream (median/min/max over >= 10 launches); `roofline.frac_rocprof_avg`: the same bytes over the rocprofv3 AVERAGE duration of the kernel
 in a kernel trace run from here (cold launches included); `roofline.frac_bmin`: SURVEY 8(d)'s conservative figure (level 0 read once, over the
@@ -94,6 +97,11 @@ def main():
                     help="after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy: jod.npy (float64 "
                          "[pairs], every rank's pairs in rank order; frame sharding: [1]) and q_per_ch.npy (float32 [pairs, bands, 2, "
                          "frames]).  The synthetic inputs depend on the arguments only, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline: the reference-style predict() "
+                         "call, the collective alone, the per-kernel rooflines (with rocprofv3 passes unless --no-measure-traffic), the "
+                         "host-array call, the CPU baseline and the JOD delta against the committed golden.  Off: the line carries the "
+                         "headline, the step timing and the JODs only")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -284,7 +292,7 @@ def main():
     # the collective alone (every rank takes part): the step's all-reduce on a buffer of the step's size, back to back, host clock
     # around a synchronised loop -> what one all-reduce adds to a step (launch + RCCL + the stream hand-over torch does around it)
     coll = None
-    if dist is not None:
+    if dist is not None and args.full:
         nrow = int(jods_rowlen[0]) if jods_rowlen else 14 * n_clip + 1
         cbuf = torch.zeros((world * (1 if frames_mode else K), nrow), dtype=torch.float32, device=dev)
         for _ in range(5):
@@ -303,7 +311,7 @@ def main():
                 "world_size": world}
     # the reference-style synchronous call next to the step path, once (one rank, one pair): the same kernels, the same single sync
     predict_ms = None
-    if world == 1 and K == 1 and not frames_mode:
+    if args.full and world == 1 and K == 1 and not frames_mode:
         # (the legs between the timed region and here leave the GPU idle for a few milliseconds; the launches after an idle gap run on clocks
         # that are still coming up -- profiles/r05_power.md -- and until round 6 this figure, taken on five such calls, read 0.4 ms above
         # the step although a back-to-back comparison shows none: tools/experiments/gpu_predict_overhead.py.  Warm up, then time.)
@@ -322,7 +330,7 @@ def main():
     roof = None
     extra = {}
     test, ref = pairs[0]
-    if rank == 0:
+    if rank == 0 and args.full:
         # the per-kernel leg launches the same kernels on the same context (same HBM scratch, same placement) as the timed steps
         if frames_mode:
             test, ref = test[:, :, :N], ref[:, :, :N]
@@ -526,7 +534,7 @@ def main():
                                           "bytes; kernels_back_to_back_ms: the sum of the isolated kernel medians of one pair"}
 
     # ---- the same call on pageable host arrays (PCIe-inclusive; reported beside `value`, never as `value`) ----
-    if rank == 0 and world == 1 and not args.no_h2d:
+    if rank == 0 and world == 1 and args.full and not args.no_h2d:
         th, rh = test.cpu().numpy(), ref.cpu().numpy()
         m.predict(th, rh, dim_order="BCFHW", frames_per_second=fps, fixation_point=gz)
         torch.cuda.synchronize(dev)
@@ -542,7 +550,7 @@ def main():
         del th, rh
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import fvvdp_oracle as orc
         tc, rc = test.cpu().numpy(), ref.cpu().numpy()
         fl = fl_guard(fps) + 1
@@ -586,7 +594,7 @@ def main():
     gpath = os.path.join(ROOT, "tests", "golden", "g3_synth_uhd_60f.npz")
     if foveated:
         gpath = os.path.join(ROOT, "tests", "golden", "g4_foveated_uhd_120f.npz")
-    if rank == 0 and os.path.exists(gpath) and not frames_mode and (
+    if rank == 0 and args.full and os.path.exists(gpath) and not frames_mode and (
             (W, H, N, fps, args.display, foveated) in ((3840, 2160, 60, 30, "standard_4k", False), (3840, 2160, 120, 30, "standard_hdr_pq", True))):
         g = np.load(gpath)
         jod_delta = abs(float(jods[0]) - float(g["jod"]))

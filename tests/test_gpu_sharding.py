@@ -111,9 +111,9 @@ def test_use_checkpoints_flag_is_accepted_and_gradients_are_refused():
         m.predict(t, ref.to(torch.float32) / 255, frames_per_second=FPS)
 
 
-def _run_bench(backend, world, extra=(), dims=(960, 540, 20, 2), torchrun=None):
+def _run_bench(backend, world, extra=(), dims=(960, 540, 20, 2), torchrun=None, full=True):
     """bench.py launched the way the driver launches it (torch.distributed.run, one process per rank; a plain process for one rank);
-    returns the JSON line."""
+    returns the JSON line.  full: with `--full`, whose figures beyond the headline `_check_bench_line` asserts."""
     import json
     import subprocess
     import sys
@@ -121,7 +121,7 @@ def _run_bench(backend, world, extra=(), dims=(960, 540, 20, 2), torchrun=None):
     W, H, N, K = dims
     args = [os.path.join(root, "bench.py"), "--gpus", str(world), "--backend", backend,
             "--pairs-per-gpu", str(K), "--width", str(W), "--height", str(H), "--frames", str(N), "--steps", "3", "--warmup", "1",
-            "--no-cpu-baseline", "--no-h2d", "--no-measure-traffic"] + list(extra)
+            "--no-cpu-baseline", "--no-h2d", "--no-measure-traffic"] + (["--full"] if full else []) + list(extra)
     if world > 1 or torchrun:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                "--master-port", str(_free_port())] + args
@@ -203,11 +203,18 @@ def test_bench_one_rank_takes_the_same_step_path():
 @pytest.mark.timeout(600)
 def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
     """`--dump-outputs DIR`: the JODs and Q_per_ch of the last timed step as .npy files -- the JODs of the JSON line, bit for bit, and
-    the Q_per_ch of single predict() calls on the same synthetic pairs."""
+    the Q_per_ch of single predict() calls on the same synthetic pairs.  A plain run (no `--full`) writes them too, and its line carries
+    the headline and the step timing but none of the figures that take runs of their own."""
     import fovvideovdp_amd as fv
     from fovvideovdp_amd.synth import synth_video_pair
     d = tmp_path / "dump"
-    out, (W, H, N, K) = _run_bench("nccl", 1, extra=("--collective", "off", "--dump-outputs", str(d)), dims=(960, 540, 20, 2))
+    out, (W, H, N, K) = _run_bench("nccl", 1, extra=("--collective", "off", "--dump-outputs", str(d)), dims=(960, 540, 20, 2), full=False)
+    assert out["unit"] == "Mpixels/s (test+ref)" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["steps"] == 3 and out["warmup"] == 1 and len(out["timing"]["ms_per_step_in_order"]) == 3
+    assert abs(out["value"] - 2.0 * W * H * N * K / (out["ms_per_step"] * 1e-3) / 1e6) <= (1e-3 + 0.0006 / out["ms_per_step"]) * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["predict_call_ms"] is None
+    assert out["jod_delta_vs_reference"] is None
+    assert not {"roofline_k1", "level0_alloc", "graded_pass", "value_h2d_inclusive", "collective"} & set(out)
     jod, q = np.load(d / "jod.npy"), np.load(d / "q_per_ch.npy")
     assert jod.dtype == np.float64 and q.dtype == np.float32 and jod.shape == (K,) and q.shape[0] == K
     assert [float(j).hex() for j in jod] == out["jod_exact"]

@@ -8,8 +8,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_bundle
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_plain.json 2> $OUT/bench_plain.err
-rocprofv3 --kernel-trace --stats -d /tmp/kt -o bench -- python $R/bench.py --no-cpu-baseline --no-measure-traffic > $OUT/bench_profiled.json 2> /tmp/kt.err
+python $R/bench.py --full > $OUT/bench_plain.json 2> $OUT/bench_plain.err
+rocprofv3 --kernel-trace --stats -d /tmp/kt -o bench -- python $R/bench.py --full --no-cpu-baseline --no-measure-traffic > $OUT/bench_profiled.json 2> /tmp/kt.err
 python $R/tools/rocpd_summary.py $(find /tmp/kt -name "*.db" | head -1) --band-levels 7 --dispatches band2_kernel > $OUT/kernel_trace_bench.md
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pf -o f -- python $R/tools/gpu_bandonly.py > /tmp/pf.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/pw -o w -- python $R/tools/gpu_bandonly.py > /tmp/pw.log 2>&1
@@ -18,7 +18,7 @@ python $R/tools/pmc_level0.py $(find /tmp/pf -name "*.db" | head -1) $(find /tmp
 FVVDP_BAND_FUSE=0 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/pf0 -o f -- python $R/tools/gpu_bandonly.py > /tmp/pf0.log 2>&1
 FVVDP_BAND_FUSE=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/pw0 -o w -- python $R/tools/gpu_bandonly.py > /tmp/pw0.log 2>&1
 python $R/tools/pmc_level0.py $(find /tmp/pf0 -name "*.db" | head -1) $(find /tmp/pw0 -name "*.db" | head -1) $OUT/pmc_level0_onelevel.json > /dev/null
-FVVDP_BAND_FUSE=0 rocprofv3 --kernel-trace --stats -d /tmp/kt0 -o bench0 -- python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_profiled_onelevel.json 2> /tmp/kt0.err
+FVVDP_BAND_FUSE=0 rocprofv3 --kernel-trace --stats -d /tmp/kt0 -o bench0 -- python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_profiled_onelevel.json 2> /tmp/kt0.err
 python $R/tools/rocpd_summary.py $(find /tmp/kt0 -name "*.db" | head -1) --band-levels 7 > $OUT/kernel_trace_bench_onelevel.md
 python $R/tools/gpu_bandonly_speed.py 12 > $OUT/bandonly_fused.txt 2>/dev/null
 FVVDP_BAND_FUSE=0 python $R/tools/gpu_bandonly_speed.py 12 > $OUT/bandonly_onelevel.txt 2>/dev/null
@@ -32,7 +32,7 @@ echo "PROBE_DISPLAY=standard_hdr_pq:" >> $OUT/fps_probe.txt
 PROBE_DISPLAY=standard_hdr_pq python $R/tools/gpu_fps.py 30:60:u8 30:60:u16 60:60:u16 120:120:u16 240:120:u16 30:60:f32rgb 120:120:f32rgb 2>/dev/null | grep -v Warn >> $OUT/fps_probe.txt
 BATCHES=None,60 python $R/tools/gpu_feeder.py 2>/dev/null | cut -c1-110 > $OUT/feeder_probe.txt
 HH=2160 WW=3840 BATCHES=None,60 python $R/tools/gpu_feeder.py 2>/dev/null | cut -c1-110 >> $OUT/feeder_probe.txt
-python $R/bench.py --pairs-per-gpu 8 --no-cpu-baseline --no-h2d > $OUT/bench_pairs8.json 2>/dev/null
+python $R/bench.py --full --pairs-per-gpu 8 --no-cpu-baseline --no-h2d > $OUT/bench_pairs8.json 2>/dev/null
 rocprofv3 --kernel-trace --stats -d /tmp/kr -o rates -- python $R/tools/gpu_fps.py 60:120:u8 120:120:u8 144:120:u8 240:120:u8 30:60:u16 > /dev/null 2> /tmp/kr.err
 python $R/tools/rocpd_summary.py $(find /tmp/kr -name "*.db" | head -1) --only temporal_vec > $OUT/kernel_trace_rates.md
 # K1 (temporal kernel): HBM traffic per 60-frame launch from the same two counters (algorithmic: 67 frames read x 49.8 MB + 60 x 132.7 MB written)
@@ -65,19 +65,19 @@ for T in bandonly fov_bandonly; do
 done
 python $R/tools/codeobj_report.py > $OUT/codeobj.md 2>/dev/null
 # BASELINE configs[1]: 1920x1080 x60 (standard_fhd, 6 bands): kernel table + the bench line
-rocprofv3 --kernel-trace --stats -d /tmp/kfhd -o fhd -- python $R/bench.py --width 1920 --height 1080 --display standard_fhd --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_fhd.json 2> /tmp/kfhd.err
+rocprofv3 --kernel-trace --stats -d /tmp/kfhd -o fhd -- python $R/bench.py --full --width 1920 --height 1080 --display standard_fhd --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_fhd.json 2> /tmp/kfhd.err
 python $R/tools/rocpd_summary.py $(find /tmp/kfhd -name "*.db" | head -1) --band-levels 6 > $OUT/kernel_trace_fhd.md
-python $R/bench.py --width 1920 --height 1080 --display standard_fhd --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_fhd_plain.json 2>/dev/null
+python $R/bench.py --full --width 1920 --height 1080 --display standard_fhd --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_fhd_plain.json 2>/dev/null
 # the same allocation A/B as profiles/r04_level0_chunks.md on this box
-FVVDP_ALLOC=malloc FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_malloc.json 2>/dev/null
-FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_chunks.json 2>/dev/null
-FVVDP_BAND_INRANGE=0 python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_clamps.json 2>/dev/null
-[ -f $R/build_variants/k1wpb1.so ] && FVVDP_LIB=$R/build_variants/k1wpb1.so python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_k1wpb1.json 2>/dev/null
-FVVDP_BAND2_TICKET=0 python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_noticket.json 2>/dev/null
-python $R/bench.py --shard frames --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_frames.json 2>/dev/null
+FVVDP_ALLOC=malloc FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_malloc.json 2>/dev/null
+FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_chunks.json 2>/dev/null
+FVVDP_BAND_INRANGE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_clamps.json 2>/dev/null
+[ -f $R/build_variants/k1wpb1.so ] && FVVDP_LIB=$R/build_variants/k1wpb1.so python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_k1wpb1.json 2>/dev/null
+FVVDP_BAND2_TICKET=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_noticket.json 2>/dev/null
+python $R/bench.py --full --shard frames --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_frames.json 2>/dev/null
 # round 6: the one-rank collective off / forced (the default is auto = forced where RCCL initialises), configs[3] with its roofline_fov block
-python $R/bench.py --collective off --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_collective_off.json 2>/dev/null
-python $R/bench.py --collective force --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_collective_force.json 2>/dev/null
-python $R/bench.py --config 3 --no-cpu-baseline --no-h2d > $OUT/bench_config3.json 2>/dev/null
+python $R/bench.py --full --collective off --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_collective_off.json 2>/dev/null
+python $R/bench.py --full --collective force --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_collective_force.json 2>/dev/null
+python $R/bench.py --full --config 3 --no-cpu-baseline --no-h2d > $OUT/bench_config3.json 2>/dev/null
 python $R/tools/gpu_rccl_one_rank.py > $OUT/rccl_one_rank.txt 2>/dev/null
 ls -la $OUT

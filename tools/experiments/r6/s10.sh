@@ -16,7 +16,7 @@ for i in 1 2 3; do
     if [ $v = new ]; then unset FVVDP_LIB; else export FVVDP_LIB=$R/build_variants/$v.so; fi
     python $R/tools/gpu_yuv.py $SPECS 2>/dev/null | grep -v Warn | sed "s/^/$v #$i /" >> $O/yuv.txt
     python $R/tools/gpu_fps.py $K1S 2>/dev/null | grep -v Warn | sed "s/^/$v #$i /" >> $O/k1.txt
-    python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_${v}_$i.json 2>/dev/null
+    python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_${v}_$i.json 2>/dev/null
   done
 done
 unset FVVDP_LIB

@@ -21,7 +21,7 @@ con = sqlite3.connect(db)
 for r in con.execute("select name, count(*), avg(duration), min(duration), max(duration) from kernels where name like '%ccl%' or name like '%oneRank%' or name like '%Reduce%' group by name").fetchall():
     print(r)
 PY
-python $R/bench.py --collective auto --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_auto.json 2> $O/bench_auto.err
+python $R/bench.py --full --collective auto --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_auto.json 2> $O/bench_auto.err
 for i in 1 2 3; do
   for V in base fov_prio fov_tailprio fov_wpb6 fov_phase4 fov_abl_tail fov_abl_mem; do
     if [ $V = base ]; then python $R/tools/gpu_config4.py 2>/dev/null | grep -E "^kernel us" > $O/fov_${V}_$i.txt

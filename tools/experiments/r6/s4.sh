@@ -22,5 +22,5 @@ rocprofv3 --pmc $SQ1 --kernel-trace -d /tmp/sq_a -o a -- python $R/tools/gpu_yuv
 python $R/tools/pmc_sq_summary.py temporal_yuv $(find /tmp/sq_a -name "*.db") > $O/pmc_sq_yuv_step2.md 2>/dev/null
 rocprofv3 --kernel-trace --stats -d /tmp/ky -o yuv -- python $R/tools/gpu_yuv.py $SPECS > /dev/null 2> /tmp/ky.err
 python $R/tools/rocpd_summary.py $(find /tmp/ky -name "*.db" | head -1) --only temporal_yuv > $O/kernel_trace_yuv.md
-python $R/bench.py --no-cpu-baseline --no-h2d > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --no-cpu-baseline --no-h2d > $O/bench.json 2> $O/bench.err
 ls $O

@@ -8,6 +8,6 @@ cd /tmp && export TMPDIR=/tmp
 python $R/tools/experiments/gpu_predict_overhead.py > $O/predict_overhead.txt 2>&1
 python $R/tools/experiments/gpu_predict_overhead.py > $O/predict_overhead2.txt 2>&1
 for i in 1 2; do
-  python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_$i.json 2> /dev/null
+  python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_$i.json 2> /dev/null
 done
 cat $O/predict_overhead.txt

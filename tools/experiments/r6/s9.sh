@@ -15,8 +15,8 @@ for i in 1 2 3; do
   python $R/tools/gpu_yuv.py $SPECS 2>/dev/null | grep -v Warn | sed "s/^/new #$i /" >> $O/yuv.txt
   FVVDP_LIB=$OLD python $R/tools/gpu_fps.py $K1S 2>/dev/null | grep -v Warn | sed "s/^/old #$i /" >> $O/k1.txt
   python $R/tools/gpu_fps.py $K1S 2>/dev/null | grep -v Warn | sed "s/^/new #$i /" >> $O/k1.txt
-  FVVDP_LIB=$OLD python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_old_$i.json 2>/dev/null
-  python $R/bench.py --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_new_$i.json 2>/dev/null
+  FVVDP_LIB=$OLD python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_old_$i.json 2>/dev/null
+  python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $O/bench_new_$i.json 2>/dev/null
 done
 cat $O/yuv.txt $O/k1.txt
 for f in $O/bench_*.json; do python - $f <<'PY'

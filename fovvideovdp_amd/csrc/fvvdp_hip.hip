@@ -42,6 +42,9 @@ static int fail(int code, const char* fmt, ...) {
     } while (0)
 
 extern "C" const char* fvvdp_last_error(void) { return g_err; }
+// the message of fvvdp_last_error for a failure in another translation unit of the library (grad_launch.hip); C++ linkage,
+// so the export map (fvvdp_*) keeps it out of the C ABI
+int fvvdp_fail_from(int code, const char* msg) { return fail(code, "%s", msg); }
 
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"

@@ -1,0 +1,271 @@
+// Backward of the still-image JOD (include/fvvdp_hip_grad.h): the adjoint of fvvdp_images_channels + fvvdp_images_forward_pool
+// with respect to the test image.  Instantiated and launched by grad_launch.hip.
+//
+// Forward, per pair (fvvdp_lpyr_dec.py:246-273, fvvdp.py:337-357, 395-467, 574-596):
+//   G_0 = sum_c w_c EOTF(V_c),  G_{b+1} = Reduce(G_b),  layer_b = G_b - Expand(G_{b+1})
+//   T_b = m_b min(layer_b / L_bkg_b, cmax),  T' = T S gain,  D = min(|T'-R'|^p / (1 + (k min(|T'|,|R'|))^q), d_max)
+//   Q_b = (mean D^beta)^(1/beta),  JOD = pool(Q_per_ch)
+// L_bkg and S come from the reference only (plane 1), so they are constants here.  Backward, per pair:
+//   grad_coef_kernel   c[b]      = gamma dJOD/dQ_b Q_b^(1-beta) / n_b                                  (one thread per pair)
+//   adj_layer_kernel   GL_b      = c[b] D^(beta-1) dD/dT' S gain m_b / L_bkg     (pointwise on the maps, every band, one launch)
+//   adj_sweep_kernel   GG_L      = GL_L - Expand^T(GL_{L-1}) + Reduce^T(GG_{L+1})                 (one launch per level L >= 1)
+//   grad_input_kernel  dtest_c   = w_c EOTF'(V_c) (GL_0 + Reduce^T(GG_1))                          (level 0, 128 pairs a launch)
+// The transposes are gathers over the exact forward stencils (edge fix-ups and the row-parity quirk of the reduce's last
+// column included), so every output is a fixed sum per pixel: no atomics, and a pair's result does not depend on its batch.
+#pragma once
+
+#define GRAD_MAX_PAIRS 128      // pointer-table entries of one grad_input_kernel launch (2 x 1 KB of kernel arguments)
+
+// the 5-tap kernel of the pyramid (fvvdp_lpyr_dec.py:174-178, kernel_a = 0.4)
+__device__ __forceinline__ float pyr_k(int k) {
+    return (k == 0 || k == 4) ? 0.05f : (k == 2 ? 0.4f : 0.25f);
+}
+
+// Weight of fine sample j in coarse sample r of one axis of gausspyr_reduce (fvvdp_lpyr_dec.py:183-207): the zero-padded
+// stride-2 5-tap filter plus the edge fix-ups.  n: fine size, nr: coarse size, odd_fix: the last fix-up's parity -- the
+// row count of the fine level on BOTH axes (the reference tests x.shape[-2] for the columns too).
+__device__ __forceinline__ float reduce_w(int r, int j, int n, int nr, bool odd_fix) {
+    const int k = j - 2 * r + 2;
+    float w = (k >= 0 && k <= 4) ? pyr_k(k) : 0.0f;
+    if (r == 0) w += (j == 0 ? pyr_k(1) : 0.0f) + (j == 1 ? pyr_k(0) : 0.0f);
+    if (r == nr - 1) {
+        if (odd_fix) w += (j == n - 1 ? pyr_k(3) : 0.0f) + (j == n - 2 ? pyr_k(4) : 0.0f);
+        else w += (j == n - 1 ? pyr_k(4) : 0.0f);
+    }
+    return w;
+}
+
+// Weight of coarse sample j in fine sample i of one axis of gausspyr_expand (fvvdp_lpyr_dec.py:126-142, 219-235; closed form
+// of oracle _expand_axis): even i = 2c -> 2K0 x[c-1] + 2K2 x[c] + 2K4 x[c+1], odd i -> 2K1 x[c] + 2K3 x[c+1], indices
+// clamped to [0, n).  n: coarse size.
+__device__ __forceinline__ float expand_w(int i, int j, int n) {
+    const int c = i >> 1, cm = max(c - 1, 0), cp = min(c + 1, n - 1);
+    if ((i & 1) == 0)
+        return (cm == j ? 2.0f * pyr_k(0) : 0.0f) + (c == j ? 2.0f * pyr_k(2) : 0.0f) + (cp == j ? 2.0f * pyr_k(4) : 0.0f);
+    return (c == j ? 2.0f * pyr_k(1) : 0.0f) + (cp == j ? 2.0f * pyr_k(3) : 0.0f);
+}
+
+// Reduce^T of the coarse image G [hc][wc] at fine pixel (y, x) of a w x h level: the coarse samples whose stencil reads it
+// (at most 3 per axis: r in [y/2 - 1, y/2 + 1])
+__device__ __forceinline__ float reduce_t(const float* G, int wc, int hc, int w, int h, int y, int x) {
+    const bool odd = (h & 1) != 0;
+    float wy[3], wx[3];
+    const int ry0 = (y >> 1) - 1, rx0 = (x >> 1) - 1;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const int ry = ry0 + d, rx = rx0 + d;
+        wy[d] = (ry >= 0 && ry < hc) ? reduce_w(ry, y, h, hc, odd) : 0.0f;
+        wx[d] = (rx >= 0 && rx < wc) ? reduce_w(rx, x, w, wc, odd) : 0.0f;
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        if (wy[dy] == 0.0f) continue;
+        const float* row = G + (size_t)(ry0 + dy) * wc;
+        float t = 0.0f;
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx)
+            if (wx[dx] != 0.0f) t = fmaf(wx[dx], row[rx0 + dx], t);
+        s = fmaf(wy[dy], t, s);
+    }
+    return s;
+}
+
+// Expand^T of the fine image Y [hf][wf] at coarse pixel (y, x) of a wc x hc level: the fine samples whose stencil reads it
+// (i in [2y - 2, 2y + 2] per axis; 2y + 3 never does, see expand_w)
+__device__ __forceinline__ float expand_t(const float* Y, int wf, int hf, int wc, int hc, int y, int x) {
+    float wy[5], wx[5];
+    const int iy0 = 2 * y - 2, ix0 = 2 * x - 2;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) {
+        const int iy = iy0 + d, ix = ix0 + d;
+        wy[d] = (iy >= 0 && iy < hf) ? expand_w(iy, y, hc) : 0.0f;
+        wx[d] = (ix >= 0 && ix < wf) ? expand_w(ix, x, wc) : 0.0f;
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int dy = 0; dy < 5; ++dy) {
+        if (wy[dy] == 0.0f) continue;
+        const float* row = Y + (size_t)(iy0 + dy) * wf;
+        float t = 0.0f;
+#pragma unroll
+        for (int dx = 0; dx < 5; ++dx)
+            if (wx[dx] != 0.0f) t = fmaf(wx[dx], row[ix0 + dx], t);
+        s = fmaf(wy[dy], t, s);
+    }
+    return s;
+}
+
+// ---- per-band coefficients --------------------------------------------------------------------------------------------
+struct GradCoefArgs {
+    const float* Q;         // Q_per_ch of the forward, [n_bands][2][q_stride], pair k in column q_col0 + k
+    const float* gamma;     // [n] upstream gradient of each JOD
+    float* coef;            // [n][n_bands]
+    int n, n_bands, q_stride, q_col0;
+    float beta, beta_sch, beta_tch, jod_a, beta_jod;
+    float inv_npx[FVVDP_MAX_BANDS];     // 1 / (h_b w_b)
+};
+
+// JOD = sgn(a) (|a|^(1/beta_jod) Q)^beta_jod + 10, Q = Q_tc of the single frame (beta_t drops out), Q_tc = (Q_sc^beta_tch +
+// 0)^(1/beta_tch) (the transient column of an image is 0), Q_sc = (sum_b Q_b^beta_sch)^(1/beta_sch)  (pool_frame, aux_kernels.hpp).
+// Zero where Q or Q_b is 0 (an identical pair), as the reference's norm backward gives.  In double: one thread per pair.
+__global__ __launch_bounds__(64) void grad_coef_kernel(const GradCoefArgs a) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= a.n) return;
+    const int col = a.q_col0 + k;
+    double qb[FVVDP_MAX_BANDS];
+    double qsc = 0.0;
+    for (int b = 0; b < a.n_bands; ++b) {
+        qb[b] = fabs((double)a.Q[(size_t)b * 2 * a.q_stride + col]);
+        qsc += pow(qb[b], (double)a.beta_sch);
+    }
+    qsc = pow(qsc, 1.0 / a.beta_sch);
+    const double qtc = pow(pow(qsc, (double)a.beta_tch), 1.0 / a.beta_tch);
+    double g = 0.0;
+    if (qsc > 0.0 && qtc > 0.0) {
+        const double sgn = a.jod_a < 0.0f ? -1.0 : 1.0;
+        const double aq = pow(fabs((double)a.jod_a), 1.0 / a.beta_jod) * qtc;
+        g = (double)a.gamma[k] * sgn * a.beta_jod * pow(aq, (double)a.beta_jod) / qtc;     // dJOD/dQ
+        g *= pow(qsc / qtc, a.beta_tch - 1.0);                                              // dQ_tc/dQ_sc
+    }
+    for (int b = 0; b < a.n_bands; ++b) {
+        double c = 0.0;
+        if (qb[b] > 0.0 && g != 0.0)
+            c = g * pow(qb[b] / qsc, a.beta_sch - 1.0) * pow(qb[b], 1.0 - a.beta) * a.inv_npx[b];
+        a.coef[(size_t)k * a.n_bands + b] = (float)c;
+    }
+}
+
+// ---- layer gradients: pointwise on the maps, every band in one launch ----------------------------------------------------
+struct GradBand {
+    const float* D;         // [n][2][h][w]  plane 0: sustained (the only channel of an image)
+    const float* Cn;        // [n][2][h][w]  plane 0: test contrast x m_b, plane 1: reference
+    const float* L;         // [n][h][w]
+    const float* S;         // [n][2][h][w]  plane 0: sensitivity before the gain
+    float* GL;              // [n][h][w]     out
+    int w, h, blk0;         // first workgroup of this band in blockIdx.x
+    float m;                // band multiplier
+};
+struct GradLayerArgs {
+    GradBand band[FVVDP_MAX_BANDS];
+    const float* coef;      // [n][n_bands]
+    int n_bands;
+    float p, q, k_mask, beta, gain, cmax_hi, dmax_hi;
+};
+
+__global__ __launch_bounds__(256) void adj_layer_kernel(const GradLayerArgs a) {
+    int b = 0;
+    while (b + 1 < a.n_bands && (int)blockIdx.x >= a.band[b + 1].blk0) ++b;
+    const GradBand& B = a.band[b];
+    const int k = blockIdx.y;
+    const size_t hw = (size_t)B.w * B.h;
+    const size_t px = (size_t)((int)blockIdx.x - B.blk0) * 256 + threadIdx.x;
+    if (px >= hw) return;
+    const float c = a.coef[(size_t)k * a.n_bands + b];
+    const float T = B.Cn[(size_t)k * 2 * hw + px];
+    const float R = B.Cn[((size_t)k * 2 + 1) * hw + px];
+    const float Dm = B.D[(size_t)k * 2 * hw + px];
+    float g = 0.0f;
+    // zero: no pooling weight, D == 0 (an identical pixel), the d_max clamp or the contrast clamp binds
+    if (c != 0.0f && Dm > 0.0f && Dm < a.dmax_hi && T < B.m * a.cmax_hi) {
+        const float s = B.S[(size_t)k * 2 * hw + px] * a.gain;
+        const float Tp = T * s, Rp = R * s;
+        const float u = Tp - Rp, au = fabsf(u);
+        const float aT = fabsf(Tp), aR = fabsf(Rp);
+        const float M = a.k_mask * fminf(aT, aR);
+        const float Mq = M > 0.0f ? powf(M, a.q) : 0.0f;
+        const float den = 1.0f + Mq;
+        const float num = powf(au, a.p);
+        const float D = num / den;
+        // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
+        float dD = au > 0.0f ? copysignf(a.p * num / au, u) / den : 0.0f;
+        if (M > 0.0f && aT <= aR) {
+            const float share = aT < aR ? 1.0f : 0.5f;
+            dD -= share * copysignf(D / den * a.q * Mq / aT, Tp);
+        }
+        const float lb = B.L[(size_t)k * hw + px];
+        g = c * powf(D, a.beta - 1.0f) * dD * s * (B.m / lb);
+    }
+    B.GL[(size_t)k * hw + px] = g;
+}
+
+// ---- coarse-to-fine sweep, one level L >= 1 ----------------------------------------------------------------------------
+struct GradSweepArgs {
+    const float* GL;        // [n][h][w] layer gradient of level L (nullptr: L is the base band, no layer of its own)
+    const float* GLf;       // [n][hf][wf] layer gradient of level L - 1
+    const float* GGc;       // [n][hc][wc] gradient of G_{L+1} (nullptr for the base band)
+    float* GG;              // [n][h][w] out: gradient of G_L
+    int w, h, wf, hf, wc, hc;
+};
+
+__global__ __launch_bounds__(256) void adj_sweep_kernel(const GradSweepArgs a) {
+    const int k = blockIdx.y;
+    const size_t hw = (size_t)a.w * a.h;
+    const size_t px = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (px >= hw) return;
+    const int y = (int)(px / (size_t)a.w), x = (int)(px - (size_t)y * a.w);
+    float g = -expand_t(a.GLf + (size_t)k * a.wf * a.hf, a.wf, a.hf, a.w, a.h, y, x);
+    if (a.GL) g += a.GL[(size_t)k * hw + px];
+    if (a.GGc) g += reduce_t(a.GGc + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
+    a.GG[(size_t)k * hw + px] = g;
+}
+
+// ---- input gradient: level 0 of the sweep and the display model's derivative ----------------------------------------------
+// dL/dV of eotf_one (temporal_kernels.hpp) with the reference's clamps: 0 where V lies outside [0, 1] for SRGB / GAMMA / PQ
+// (fvvdp_display_model.py:147-150) and where the luminance clip of PQ, LINEAR or ABSOLUTE binds; sRGB takes the branch the
+// forward takes (V > 0.04045).
+__device__ __forceinline__ float eotf_grad(float V, const EotfDev& e) {
+    switch (e.kind) {
+        case FVVDP_EOTF_SRGB:
+            if (!(V >= 0.0f && V <= 1.0f)) return 0.0f;
+            return e.scale * (V > 0.04045f ? (2.4f / 1.055f) * powf((V + 0.055f) * (1.0f / 1.055f), 1.4f) : 1.0f / 12.92f);
+        case FVVDP_EOTF_GAMMA:
+            if (!(V > 0.0f && V <= 1.0f)) return 0.0f;
+            return e.scale * e.gamma * powf(V, e.gamma - 1.0f);
+        case FVVDP_EOTF_PQ: {
+            if (!(V > 0.0f && V <= 1.0f)) return 0.0f;
+            const float m = 78.843750000000000f, n = 0.15930175781250000f;
+            const float c1 = 0.83593750000000000f, c2 = 18.851562500000000f, c3 = 18.687500000000000f;
+            const float t = powf(V, 1.0f / m);
+            if (!(t > c1)) return 0.0f;
+            const float den = c2 - c3 * t;
+            const float r = (t - c1) / den;
+            const float L = 10000.0f * powf(r, 1.0f / n);
+            if (!(L >= 0.005f && L <= e.y_peak)) return 0.0f;
+            return L / (n * r) * ((c2 - c3 * c1) / (den * den)) * (t / (m * V));
+        }
+        case FVVDP_EOTF_LINEAR:
+            return (V >= 0.005f && V <= e.y_peak) ? 1.0f : 0.0f;
+        case FVVDP_EOTF_ABSOLUTE:
+            return (V >= e.l_min && V <= e.l_max) ? 1.0f : 0.0f;
+        default:
+            return 0.0f;
+    }
+}
+
+struct GradInputArgs {
+    const float* test[GRAD_MAX_PAIRS];
+    float* grad[GRAD_MAX_PAIRS];
+    const float* GL0;       // [n][h][w] layer gradient of level 0, pair 0 of the launch
+    const float* GG1;       // [n][hc][wc] gradient of G_1
+    size_t chan_stride;
+    int C, w, h, wc, hc;
+    EotfDev e;
+    float wgt[3];
+};
+
+__global__ __launch_bounds__(256) void grad_input_kernel(const GradInputArgs a) {
+    const int k = blockIdx.y;
+    const size_t hw = (size_t)a.w * a.h;
+    const size_t px = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (px >= hw) return;
+    const int y = (int)(px / (size_t)a.w), x = (int)(px - (size_t)y * a.w);
+    const float g0 = a.GL0[(size_t)k * hw + px] +
+                     reduce_t(a.GG1 + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
+    const float* V = a.test[k];
+    float* out = a.grad[k];
+    for (int c = 0; c < a.C; ++c) {
+        const size_t o = (size_t)c * a.chan_stride + px;
+        out[o] = a.wgt[c] * eotf_grad(V[o], a.e) * g0;
+    }
+}

@@ -83,7 +83,8 @@ def window_frame_indices(N, fl, temp_padding):
 def _refuse_grad(a):
     if isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("Gradients through the metric are not supported on the HIP path (forward-only kernels); "
-                           "detach the inputs or wrap the call in torch.no_grad()")
+                           "detach the inputs or wrap the call in torch.no_grad() (differentiable still images: "
+                           "fvvdp.jod_images)")
 
 
 def _image_stack(test, reference, dim_order):
@@ -294,6 +295,19 @@ class fvvdp:
             fix = self._fixation(fixation_point, t.shape[3], t.shape[2], B)
         with torch.cuda.device(self.device):
             return self._predict_image_group([t[k] for k in range(B)], [r[k] for k in range(B)], fix, sync)
+
+    def jod_images(self, test, reference, dim_order="BCHW", fixation_point=None):
+        """Extension: the JOD of B still-image pairs as a differentiable [B] fp32 tensor on the metric's device, for losses
+        such as `10 - metric.jod_images(x, ref)`.  Values are bit-identical to predict_images(test.detach(), reference, ...)[0].
+        When `test` requires grad (and grad mode is on), backward() puts dJOD_k/dtest_k into `test`, whatever its layout or
+        device; the reference is a constant (a reference that requires grad is refused).  float32 samples only, behind a
+        display model with a closed form (sRGB, gamma, PQ, linear, absolute); samples the display model clamps (outside
+        [0, 1], or beyond a luminance clip) get a zero gradient.  Foveated metrics take `fixation_point` as predict_images.
+        Nothing is synchronised with the host (a user geometry model's gaze conversion aside): the out-of-range warning of predict_images is not issued and no heat maps are
+        made, whatever `heatmap` the metric was built with.  Double backward is not supported.  The backward re-runs the
+        forward with per-band maps in batches of up to `self.grad_batch` pairs (None: as many as about 4 GB of maps allow)."""
+        from .image_grad import jod_images
+        return jod_images(self, test, reference, dim_order, fixation_point)
 
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,

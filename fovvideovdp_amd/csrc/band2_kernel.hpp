@@ -23,11 +23,9 @@
 // (fvvdp_lpyr_dec.py:126-142).  A level-B row past the bottom is the mirrored row (B[hb] = B[hb-1], B[hb+1] = B[hb-2]),
 // which is what both the reduce (symmetric) and the expand (clamp, only B[hb]) ask for.
 // ------------------------------------------------------------------------------------------------------------
-#ifndef F2_PITCH
-#define F2_PITCH 54         // level-B columns owned per wave: lanes 6..59, all the two-level halo leaves valid (the kernel is
-                            // co-bound -- its arithmetic alone takes as long as its data flow, profiles/r03_pyramid_bounds.md: 54 vs a line-aligned 52 columns measured +3.4 %)
-#define F2_HL 6             // halo lanes on the left (4 on the right); even, so lane parity == column parity
-#endif
+constexpr int F2_PITCH = 54;    // level-B columns owned per wave: lanes 6..59, all the two-level halo leaves valid (the kernel is
+                                // co-bound -- its arithmetic alone takes as long as its data flow, profiles/r03_pyramid_bounds.md: 54 vs a line-aligned 52 columns measured +3.4 %)
+constexpr int F2_HL = 6;        // halo lanes on the left (4 on the right); even, so lane parity == column parity
 
 struct Band2Args {
     L0Addr A;               // level A, frame f at l0_frame(A, f): [h][w][P] (level 0 may live in two ranges, device_common.hpp)
@@ -87,9 +85,7 @@ __device__ __forceinline__ v2f dpp_expand2_taps(v2f t, v2f e, float fl, float fr
     return v2f{x, y};
 }
 
-#ifndef BAND2_LB
-#define BAND2_LB 3
-#endif
+constexpr int BAND2_LB = 3;
 // INRANGE: the host has PROVEN from the display model, the RGB->Y weights and the temporal taps (luminance_range,
 // fvvdp_hip.hip) that on these levels  (1) expand(ref sustained) >= lbkg_min, so L_bkg = max(., 0.1) is the identity
 // (fvvdp_lpyr_dec.py:265),  (2) g - e < contrast_max * L_bkg for every plane, so the upper clamp of the contrast never binds
@@ -154,19 +150,12 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
     // register, computed by the scalar unit), the lane's column offset a loop-invariant vector register -- no vector
     // instruction goes into addressing (flat loads cost one 64-bit v_lshl_add_u64 each: 16 per loop iteration of a kernel
     // whose arithmetic is as long as its data flow).
-#if defined(BAND2_ABLATE_MEM)      // profiling ablation: every wave re-reads 8 rows of frame 0 (L2 hits), nothing is stored
-    const __amdgpu_buffer_rsrc_t Ga_rsrc = level_rsrc(a.A.lo, (unsigned int)(h * w * P) * 4u);
-#else
     const __amdgpu_buffer_rsrc_t Ga_rsrc = level_rsrc(const_cast<float*>(Ga), (unsigned int)(h * w * P) * 4u);   // <= 133 MB per frame
-#endif
     const unsigned int col0_b = (unsigned int)xc0 * (P * 4u), col1_b = (unsigned int)xc1 * (P * 4u);
     const unsigned int row_b = (unsigned int)w * (P * 4u);
     auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) {
         int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);   // symmetric padding (fvvdp_lpyr_dec.py:190-195)
         rr = min(max(rr, 0), h - 1);
-#if defined(BAND2_ABLATE_MEM)
-        rr &= 7;
-#endif
         const unsigned int so = (unsigned int)rr * row_b;
         p0 = ld_px_buf<P>(Ga_rsrc, col0_b, so);
         p1 = ld_px_buf<P>(Ga_rsrc, col1_b, so);
@@ -212,11 +201,6 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
 
     // per-pixel tail (contrast, CSF, masking, pooling term), see band_kernel::band_px for the derivation
     auto tail = [&](const Px<P>& g, const Px<P>& e, bool valid, const int band, float (&acc)[2]) {
-#if defined(BAND2_ABLATE) && BAND2_ABLATE >= 1      // profiling ablation: no per-pixel tail, keep the data flow alive
-        acc[0] += g.h[0].x + e.h[0].y + (valid ? 1.0f : 0.0f);
-        (void)band;
-        return;
-#endif
         const float lb = INRANGE ? e.h[0].y : fmaxf(e.h[0].y, a.lbkg_min);
         const float dcap = a.cmax * lb;
         v2f d[HP];
@@ -384,11 +368,7 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
             v = pfma(R[4].h[q], K4, v);
             Cn.h[q] = dpp_reduce5_pair(v * uq2, v, uq0, uq1, uq3, uq4);
         }
-#if defined(BAND2_ABLATE_MEM)
-        st_px(Gc_rsrc, (k < -1000000) ? 0u : FVVDP_NO_STORE, Cn);
-#else
         st_px(Gc_rsrc, (k >= ka && k < kb && owned && jeven && K < wc) ? (unsigned int)(k * wc + K) * (P * 4u) : FVVDP_NO_STORE, Cn);
-#endif
         CH[0] = CH[1];
         CH[1] = CH[2];
         CH[2] = Cn;
@@ -426,9 +406,6 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
 // waves per workgroup of band2_kernel: 1 .. 4 (adjacent strips of one chunk and frame, one barrier per stage); the launch decides.
 // 8 and 12 waves, or a second barrier per stage, were slower (profiles/r04_lockstep.md).
 #define BAND2_WPB_MAX 4
-#ifdef BAND2_TIMELINE      // profiling build: (start, end) of every workgroup on the 100 MHz wall clock + where it ran (tools/gpu_timeline.py)
-__device__ unsigned long long g_band2_timeline[4 * 65536];
-#endif
 
 // Work distribution of band2_kernel: one workgroup (wpb adjacent strips x one chunk x one frame) per work item, in two phases of
 // block indices -- the tall chunks of all frames, then the short chunks (the bottom rows of every frame, cut finer).  The launch
@@ -450,9 +427,6 @@ __global__ __launch_bounds__(64 * BAND2_WPB_MAX, BAND2_LB) void band2_kernel(con
     __shared__ float4 s_csf[2][FVVDP_LUT_N];
     __shared__ int s_item[2];
     const int lane = threadIdx.x & 63;
-#ifdef BAND2_TIMELINE
-    const unsigned long long tl_t0 = wall_clock64();
-#endif
     const int wpb = (int)(blockDim.x >> 6);
     const int n_groups = a.n_strips / wpb;                    // (the launch makes wpb divide n_strips)
     const int first = n_groups * a.n_big * a.n_frames;        // workgroups of the first phase
@@ -504,13 +478,4 @@ __global__ __launch_bounds__(64 * BAND2_WPB_MAX, BAND2_LB) void band2_kernel(con
     }
     __syncthreads();
     band2_item<P, INRANGE>(a, strip, chunk, frame, lane, s_csf, wpb > 1);
-#ifdef BAND2_TIMELINE
-    if (lane == 0 && a.w >= 2560 && blockIdx.x * wpb + (threadIdx.x >> 6) < 65536) {       // (the large launch only)
-        unsigned long long* t = g_band2_timeline + 4 * (size_t)(blockIdx.x * wpb + (threadIdx.x >> 6));
-        t[0] = tl_t0;
-        t[1] = wall_clock64();
-        t[2] = ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) << 32) | (unsigned int)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4);   // XCC_ID, HW_ID
-        t[3] = ((unsigned long long)frame << 32) | (unsigned int)(chunk * a.n_strips + strip);
-    }
-#endif
 }

@@ -14,9 +14,7 @@
 //   (test, ref) live in adjacent registers and go through packed fp32 math (v_pk_fma_f32), which also makes the
 //   test and reference planes bit-symmetric (identical inputs give exactly D = 0).
 // ------------------------------------------------------------------------------------------------------------
-#ifndef STRIP_J             // (overridable for one timing-only experiment, profiles/r03_fov_variants.md)
-#define STRIP_J 60          // coarse columns produced per wave (64 lanes - 2 halo lanes each side)
-#endif
+constexpr int STRIP_J = 60;     // coarse columns produced per wave (64 lanes - 2 halo lanes each side)
 
 
 template <int P>
@@ -67,9 +65,7 @@ __device__ __forceinline__ Px<2> ld_px_buf<2>(__amdgpu_buffer_rsrc_t r, unsigned
 // top of the next step (loads and stores share one in-order counter on gfx9), i.e. every step would wait for the
 // previous step's store to be acknowledged before its own prefetched rows are usable.
 // (level_rsrc / FVVDP_NO_STORE: device_common.hpp)
-#ifndef BAND_STORE_AUX
-#define BAND_STORE_AUX 2    // cache policy bits of the coarse-level stores: 2 = nt (streaming)
-#endif
+constexpr int BAND_STORE_AUX = 2;   // cache policy bits of the coarse-level stores: 2 = nt (streaming)
 __device__ __forceinline__ void st_px(__amdgpu_buffer_rsrc_t r, unsigned int byte_off, const Px<4>& a) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, v4f{a.h[0].x, a.h[0].y, a.h[1].x, a.h[1].y}), r, byte_off, 0, BAND_STORE_AUX);
 }
@@ -121,12 +117,8 @@ __device__ __forceinline__ void dpp_expand_taps(v2f e, float el, float er, float
 // (MI355X_MICROARCH.md, LDS): the slot of cell (r, e, y) is (8 r + 4 e + y) mod 16, so the cells a group typically touches --
 // a few adjacent Y intervals in one or two adjacent ecc intervals -- never collide.  Unpadded (row = 32 entries = two full
 // bank rows) every pair (e, y), (e + 1, y) did: one extra LDS cycle on almost every access (r2 PMC).
-#ifndef FOV_ROW
-#define FOV_ROW 36
-#endif
-#ifndef FOV_PLANE
-#define FOV_PLANE (FVVDP_LUT_N * FOV_ROW + 8)
-#endif
+constexpr int FOV_ROW = 36;
+constexpr int FOV_PLANE = FVVDP_LUT_N * FOV_ROW + 8;
 
 struct BandArgs {
     L0Addr F;               // fine level, frame f at l0_frame(F, f): [h][w][P] (level 0 may live in two ranges, device_common.hpp)
@@ -225,18 +217,9 @@ __device__ __forceinline__ int floor_to_int(float x) {
     return r;
 }
 
-#ifndef FOV_WPB
-#define FOV_WPB 4            // foveated mode: 4 independent waves per workgroup share the band's LUT slice in LDS
-#endif
-#ifndef FOV_MINW
-#define FOV_MINW 2
-#endif
-#ifndef FOV_MINW_LEAN
-#define FOV_MINW_LEAN 3     // the stock-geometry instantiation (FOVM == 1): 168 VGPRs, 3 waves per SIMD
-#endif
-#ifndef FOV_PHASE
-#define FOV_PHASE 2          // pixels whose LDS reads are batched: pairs (160 VGPRs, 3 waves per SIMD); 4 = all of a step (181 VGPRs)
-#endif
+constexpr int FOV_WPB = 4;          // foveated mode: 4 independent waves per workgroup share the band's LUT slice in LDS
+constexpr int FOV_MINW = 2;
+constexpr int FOV_MINW_LEAN = 3;    // the stock-geometry instantiation (FOVM == 1): 168 VGPRs, 3 waves per SIMD
 extern __shared__ __attribute__((aligned(16))) float4 s_lut_dyn[];
 
 // One work item of a level: the wave streams down strip `strip` of frame `frame`, coarse rows of chunk `chunk`.  The tables
@@ -304,19 +287,12 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
 
     // rows of the fine level through a buffer resource: scalar row offset + loop-invariant lane offset, no vector address
     // arithmetic (see ld_px_buf)
-#if defined(BAND_ABLATE_MEM)       // profiling ablation: every wave re-reads 8 rows of frame 0 (L2 hits), nothing is stored
-    const __amdgpu_buffer_rsrc_t Gf_rsrc = level_rsrc(a.F.lo, (unsigned int)(h * w * P) * 4u);
-#else
     const __amdgpu_buffer_rsrc_t Gf_rsrc = level_rsrc(const_cast<float*>(Gf), (unsigned int)(h * w * P) * 4u);    // <= 133 MB per frame
-#endif
     const unsigned int col0_b = (unsigned int)xc0 * (P * 4u), col1_b = (unsigned int)xc1 * (P * 4u);
     const unsigned int row_b = (unsigned int)w * (P * 4u);
     auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) {
         int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);   // symmetric padding (fvvdp_lpyr_dec.py:190-195)
         rr = min(max(rr, 0), h - 1);
-#if defined(BAND_ABLATE_MEM)
-        rr &= 7;
-#endif
         const unsigned int so = (unsigned int)rr * row_b;
         p0 = ld_px_buf<P>(Gf_rsrc, col0_b, so);
         p1 = ld_px_buf<P>(Gf_rsrc, col1_b, so);
@@ -535,7 +511,7 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         }
     };
 
-    // Foveated mode, plain evaluation (no maps written): the pixels of a step in two phases (FOV_PHASE at a time), so that
+    // Foveated mode, plain evaluation (no maps written): the pixels of a step in two phases (two pixels at a time), so that
     // their LDS reads (the 4 corners of the LUT cell per pixel) are issued back to back and waited for once,
     // instead of dependent LDS round trips per pixel.  The same formula as band_px above; it differs from it by rounding only
     // (fractions from the grid position, blends in slope form: ~2e-6 of an interval, 1 ulp per blend).
@@ -556,43 +532,26 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         }
         q.llb = fast_log2(lb);
         const float yq = __builtin_amdgcn_fmed3f(q.llb, a.ly_lo, a.ly_hi);
-#ifdef FOV_ABLATE_ECC     // timing experiment only: what the eccentricity arithmetic costs (results are wrong)
-        const float eq = dx2 + dy2;
-#else
         const float ecc = __builtin_amdgcn_sqrtf(dx2 + dy2);
         const float eq = __builtin_amdgcn_sqrtf(__builtin_amdgcn_fmed3f(ecc, a.ecc_lo, a.ecc_hi));
-#endif
         // Y and ecc axes are uniform: interval = floor of the grid position t, fraction = (t - interval) * step/(step+1e-6)
         // (interp.py:11-20 computes (q - knot)/(knot' - knot + 1e-6) from the stored knots: equal to ~2e-6 of an interval,
         // which band_px, the map-writing path, still does).  No LDS look-up, no dependent round trip before the cell reads.
         const float tY = fmaf(yq, a.inv_step[0], a.grid_off[0]);
         const float iY = __builtin_amdgcn_fmed3f(floorf(tY), 0.0f, (float)(FVVDP_LUT_N - 2));
         q.fY = (tY - iY) * a.frac_scale[0];
-#ifdef FOV_ABLATE_ECC
-        const float iE = 3.0f;
-        q.fE = eq;
-#else
         const float tE = fmaf(eq, a.inv_step[2], a.grid_off[2]);
         const float iE = __builtin_amdgcn_fmed3f(floorf(tE), 0.0f, (float)(FVVDP_LUT_N - 2));
         q.fE = (tE - iE) * a.frac_scale[2];
-#endif
         // byte offset of the cell (rho plane + ecc * 512 + Y * 16) in float: small integers are exact, one conversion
         const int bo = (int)fmaf(iE, (float)(FOV_ROW * 16), fmaf(iY, 16.0f, pre_kR));
         q.fR = pre_fR;
         const float4* cell = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s_lut_dyn) + bo);
         constexpr int sj = 1, sk = FOV_ROW;
-#ifdef FOV_ABLATE_LDS      // timing experiment only: no LUT reads (results are wrong)
-        (void)cell; (void)sj; (void)sk;
-        q.v00 = make_float4(q.fY, q.fE, 0.1f, 0.2f);
-        q.v10 = make_float4(q.fE, q.fY, 0.2f, 0.1f);
-        q.v01 = make_float4(q.fY, q.fY, 0.3f, 0.1f);
-        q.v11 = make_float4(q.fE, q.fE, 0.1f, 0.3f);
-#else
         q.v00 = cell[0];
         q.v10 = cell[sj];
         q.v01 = cell[sk];
         q.v11 = cell[sk + sj];
-#endif
         return q;
     };
     auto fov_b = [&](const FovQ& q, bool valid) {
@@ -664,20 +623,13 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
                 }
             }
         }
-#if defined(FOV_PRIO)       // A/B build (profiles/r06_fov_floor.md): the memory-issuing head of a step at raised wave priority
-        if constexpr (FOV) __builtin_amdgcn_s_setprio(FOV_PRIO);
-#endif
         if constexpr (FOV) __builtin_amdgcn_sched_barrier(0);
         load_row(2 * c + 5, R[(s0 + 5) & 7][0], R[(s0 + 5) & 7][1]);
         load_row(2 * c + 6, R[(s0 + 6) & 7][0], R[(s0 + 6) & 7][1]);
         const Px<P> cN = coarse_step(integral_constant<int, s0>());       // coarse row c+1
         const bool has_next = (c + 1) <= (hc - 1);
         Px<P> Gp1 = has_next ? cN : G0;       // index clamp of the expand (fvvdp_lpyr_dec.py:134,138)
-#if defined(BAND_ABLATE_MEM)
-        st_px(Gc_rsrc, (c < -1000000) ? 0u : FVVDP_NO_STORE, cN);
-#else
         st_px(Gc_rsrc, (has_next && (c + 1) < cb && active) ? (unsigned int)((c + 1) * wc + J) * (P * 4u) : FVVDP_NO_STORE, cN);
-#endif
         Px<P> x00, x01, x10, x11;             // expanded level at (row 2c|2c+1, col X0|X1)
         Px<P> evE, evO;
 #pragma unroll
@@ -698,17 +650,6 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
             dpp_expand_taps(evO.h[k], el, er, orr, x10.h[k], x11.h[k]);
         }
         const bool row1_ok = (2 * c + 1) < h;
-#if defined(FOV_PRIO)
-#if !defined(FOV_TAILPRIO)
-#define FOV_TAILPRIO 0      // (the reverse experiment: the arithmetic tail at raised priority)
-#endif
-        if constexpr (FOV) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(FOV_TAILPRIO); }
-#endif
-#if defined(BAND_ABLATE) && BAND_ABLATE >= 1      // profiling ablation: no per-pixel tail, keep the data flow alive
-        acc[0] += x00.h[0].x + x01.h[0].x + x10.h[0].x + x11.h[0].x + W0[0].h[0].x + W0[1].h[0].x + W1[0].h[0].x + W1[1].h[0].x;
-        if (false)
-#endif
-        {
         float vy0 = 0.0f, vy1 = 0.0f;        // vertical view angle of the two fine rows (foveated)
         if constexpr (FOV) {
             const float* s_vy = reinterpret_cast<const float*>(s_lut_dyn + (LUT_LDS ? FOV_PLANE * a.rw : 0));
@@ -734,17 +675,9 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
                 }
             }
             if constexpr (LUT_LDS && !DBG) {
-                if (FOV_PHASE != 0 && (LEAN || (a.rmap && !a.mvx))) {   // stock geometry: phased evaluation (see fov_a / fov_b)
-#if FOV_PHASE == 4
-                    const FovQ q0 = fov_a(W0[0], x00, dxa2, dy02, ra.x, ra.y);
-                    const FovQ q1 = fov_a(W0[1], x01, dxb2, dy02, ra.z, ra.w);
-                    const FovQ q2 = fov_a(W1[0], x10, dxa2, dy12, rb.x, rb.y);
-                    const FovQ q3 = fov_a(W1[1], x11, dxb2, dy12, rb.z, rb.w);
-                    fov_b(q0, active);
-                    fov_b(q1, active && col1_ok);
-                    fov_b(q2, active && row1_ok);
-                    fov_b(q3, active && row1_ok && col1_ok);
-#else               // two pixels per phase (default): half the registers in flight; the scheduler may not interleave the phases
+                if (LEAN || (a.rmap && !a.mvx)) {   // stock geometry: phased evaluation (see fov_a / fov_b)
+                    // two pixels per phase: half the registers in flight (160 VGPRs, 3 waves per SIMD; all four pixels of a step
+                    // in one phase took 181); the scheduler may not interleave the phases
                     __builtin_amdgcn_sched_barrier(0);
                     {
                         const FovQ q0 = fov_a(W0[0], x00, dxa2, dy02, ra.x, ra.y);
@@ -760,7 +693,6 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
                         fov_b(q3, active && row1_ok && col1_ok);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-#endif
                 } else {
                     band_px(W0[0], x00, active, 2 * c, X0, vx4[0], vy4[0], rm4[0], ra.x, ra.y);
                     band_px(W0[1], x01, active && col1_ok, 2 * c, X1, vx4[1], vy4[1], rm4[1], ra.z, ra.w);
@@ -778,7 +710,6 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
             band_px(W0[1], x01, active && col1_ok, 2 * c, X1, 0.0f, 0.0f, 1.0f);
             band_px(W1[0], x10, active && row1_ok, 2 * c + 1, X0, 0.0f, 0.0f, 1.0f);
             band_px(W1[1], x11, active && row1_ok && col1_ok, 2 * c + 1, X1, 0.0f, 0.0f, 1.0f);
-        }
         }
         Gm1 = G0;
         G0 = Gp1;
@@ -835,9 +766,6 @@ __device__ __forceinline__ void band_load_tables(const BandArgs& a, float4* s_cs
 // FOVM: 0 = non-foveated, 1 = foveated with the band's LUT slice in (dynamic) LDS, 2 = foveated, LUT slice in global
 // memory (slice too large, or the map-writing variant).  A compile-time choice: with a run-time flag the compiler
 // merges the two look-ups into one flat load, which is slower than ds_read_b128.
-#ifndef FOV_FRAME_FASTEST
-#define FOV_FRAME_FASTEST 1
-#endif
 template <int P, bool DBG, int FOVM>
 __global__ __launch_bounds__(FOVM ? 64 * FOV_WPB : 64, FOVM ? (FOVM == 1 ? FOV_MINW_LEAN : FOV_MINW) : (DBG ? 2 : 4)) void band_kernel(const BandArgs a_byval) {
     // the argument block is read from the kernel-argument segment where it is needed (scalar loads) instead of being held in
@@ -864,7 +792,7 @@ __global__ __launch_bounds__(FOVM ? 64 * FOV_WPB : 64, FOVM ? (FOVM == 1 ? FOV_M
     }
     const bool wave_has_work = !FOV || bid < a.n_items;
     int strip, chunk, frame;
-    if constexpr (FOVM == 1 && FOV_FRAME_FASTEST) {
+    if constexpr (FOVM == 1) {
         // frame fastest: an XCD walks all frames of a tile before the next tile, the tile's slice of the (frame-invariant)
         // rho map stays in that XCD's L2 instead of being fetched once per frame
         const int n_tiles = a.n_strips * a.n_chunks, n_frames = a.n_items / n_tiles;

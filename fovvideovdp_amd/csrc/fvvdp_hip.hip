@@ -69,12 +69,11 @@ struct CtxEnv {
     float probe_mixed = 6.75f;    // FVVDP_PLACEMENT_MIXED_TBS: a pair written at once at this rate [TB/s] lies in both classes of memory
     bool inrange_off = false;     // FVVDP_BAND_INRANGE=0: always the pyramid kernels with clamps
     int fuse_mode = -1;           // FVVDP_BAND_FUSE=0 / 1: two-level pyramid kernel never / wherever valid (default: large levels)
-    int band_cr = 0, band2_kr = 0, band2_kr2 = -1, band2_wpb = 0;   // FVVDP_BAND_CR, FVVDP_BAND2_KR, _KR2, _WPB: work decomposition overrides
+    int band2_kr = 0, band2_kr2 = -1, band2_wpb = 0;   // FVVDP_BAND2_KR, _KR2, _WPB: work decomposition overrides
     int k1_ticket = -1;           // FVVDP_K1_TICKET=0 / 1: temporal kernel (16-slot ring) without / with its block counter
     int level0_split = -1;        // FVVDP_LEVEL0_SPLIT=1: level 0 in two ranges for ANY context, no choice among candidates (tests)
     int band2_ticket = -1;        // FVVDP_BAND2_TICKET=0 / 1: two-level pyramid kernel with the static split of work / per-XCD counters
     bool temporal_scalar = false; // FVVDP_TEMPORAL_SCALAR=1: the per-pixel temporal kernels (fallbacks for unaligned sizes)
-    bool fov_no_rhomap = false;   // FVVDP_FOV_NO_RHOMAP=1: foveated kernels evaluate the rho coordinate per pixel
     bool debug_variant = false;   // FVVDP_DEBUG_VARIANT=1: print which kernel variants are launched (tests)
     bool yuv_general = false;     // FVVDP_YUV_GENERAL_MATRIX=1: YUV ingest with the nine-term colour matrix also where it has the ITU shape (tests)
 };
@@ -88,7 +87,6 @@ static CtxEnv read_env() {
     if (const char* v = getenv("FVVDP_PLACEMENT_MIXED_TBS")) e.probe_mixed = (float)atof(v);
     if (const char* v = getenv("FVVDP_BAND_INRANGE")) e.inrange_off = v[0] == '0';
     if (const char* v = getenv("FVVDP_BAND_FUSE")) e.fuse_mode = (v[0] == '0' || v[0] == '1') ? v[0] - '0' : -1;
-    e.band_cr = num("FVVDP_BAND_CR", 0);
     e.band2_kr = num("FVVDP_BAND2_KR", 0);
     e.band2_kr2 = num("FVVDP_BAND2_KR2", -1);
     e.band2_wpb = num("FVVDP_BAND2_WPB", 0);
@@ -96,7 +94,6 @@ static CtxEnv read_env() {
     if (const char* v = getenv("FVVDP_BAND2_TICKET")) e.band2_ticket = v[0] != '0' ? 1 : 0;
     if (const char* v = getenv("FVVDP_LEVEL0_SPLIT")) e.level0_split = v[0] != '0' ? 1 : 0;
     e.temporal_scalar = getenv("FVVDP_TEMPORAL_SCALAR") != nullptr;
-    e.fov_no_rhomap = getenv("FVVDP_FOV_NO_RHOMAP") != nullptr;
     e.debug_variant = getenv("FVVDP_DEBUG_VARIANT") != nullptr;
     e.yuv_general = getenv("FVVDP_YUV_GENERAL_MATRIX") != nullptr;
     return e;
@@ -342,7 +339,7 @@ static void chunking2(int hc, int n_strips, int n, long long capacity, int kr_ov
     n_chunks = (hc + kr - 1) / kr;
 }
 
-static void chunking(int hc, int n_strips, int n, long long capacity, int cr_override, int& n_chunks, int& cr) {
+static void chunking(int hc, int n_strips, int n, long long capacity, int& n_chunks, int& cr) {
     // Every single-wave workgroup does the same amount of work (cr steps + the prologue for the two halo coarse
     // rows, whose 7 extra fine rows are re-read from HBM: weighted as 8 steps), so the launch proceeds in "rounds"
     // of `capacity` resident waves.  Pick the chunk height that minimises rounds x per-wave cost.
@@ -357,7 +354,6 @@ static void chunking(int hc, int n_strips, int n, long long capacity, int cr_ove
         if (cost < best) { best = cost; cr = c; }
         if (cand >= hc) break;
     }
-    if (cr_override >= 1) cr = cr_override > hc ? hc : cr_override;      // tuning override (FVVDP_BAND_CR)
     n_chunks = (hc + cr - 1) / cr;
 }
 
@@ -716,7 +712,7 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                     a.idx1[u] = h_frame_idx1 ? h_frame_idx1[src < 0 ? 0 : src] : a.idx[u];
                 }
                 // vector path needs the lane's PX consecutive samples to be naturally aligned
-                const int PXv = k1_px(FL, dtype);        // temporal_launch.hpp
+                const int PXv = k1_px(FL);        // temporal_launch.hpp
                 const int es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
                 const bool vec_ok = !c->env.temporal_scalar && (HW % PXv == 0) && (HW >= PXv) &&
                                     (chan_stride % PXv == 0) && (frame_stride % PXv == 0) &&
@@ -1178,7 +1174,7 @@ static int build_sublut(fvvdp_ctx* c, const fvvdp_geom* g, hipStream_t st) {
         HIP_TRY(hipMemcpy(c->sublut[b], h.data(), n * sizeof(float4), hipMemcpyHostToDevice));
         c->sub_rw[b] = rw;
         c->sub_ilo[b] = i_lo;
-        if (g && !c->env.fov_no_rhomap) {   // frame-invariant rho-axis coordinates of every pixel (stock geometry)
+        if (g) {   // frame-invariant rho-axis coordinates of every pixel (stock geometry)
             const int pw = (c->lw[b] + 1) / 2;
             if (!c->rmap[b]) {
                 int rc = dev_alloc(c, &c->rmap[b], (size_t)pw * c->lh[b]);
@@ -1405,7 +1401,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
         a.wc = c->lw[b + 1];
         a.hc = c->lh[b + 1];
         a.n_strips = band_strips(a.wc);
-        chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, c->env.band_cr, a.n_chunks, a.cr);
+        chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, a.n_chunks, a.cr);
         a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
         a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
         a.csf_y = c->csf_y;
@@ -1466,7 +1462,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             }
             a.frame_w = c->W;
             a.frame_h = c->H;
-            a.rmap = (geom && !c->env.fov_no_rhomap) ? c->rmap[b] : nullptr;
+            a.rmap = geom ? c->rmap[b] : nullptr;
             a.rmap_w = (c->lw[b] + 1) / 2;
         }
         const int nblk = a.n_strips * a.n_chunks;
@@ -1967,12 +1963,3 @@ extern "C" int fvvdp_ctx_call_stats(const fvvdp_ctx* c, int64_t* h_counts3) {
     h_counts3[2] = c->n_free;
     return FVVDP_OK;
 }
-
-#ifdef BAND2_TIMELINE      // profiling build only (tools/build_variant.sh timeline "-DBAND2_TIMELINE"): not part of the C ABI
-extern "C" int fvvdp_debug_timeline(unsigned long long* h_out, size_t n_records) {
-    if (n_records > 65536) n_records = 65536;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_band2_timeline), n_records * 4 * sizeof(unsigned long long)));
-    return FVVDP_OK;
-}
-#endif

@@ -83,7 +83,7 @@ __device__ __forceinline__ float eotf_f32(float V, const EotfDev& e, B& bad) {
 template <int N, int KIND = -1, typename B = bool>
 __device__ __forceinline__ void eotf_apply(float (&V)[N], const EotfDev& e, B& bad) {
     // (round 6: a wave-uniform branch that skips the sRGB toe, as in the YUV kernel, was measured here for 16-bit / float sources:
-    // 47.2 -> 46.7 us per 4K frame on uint16 RGB, nothing on float RGB (tools/experiments/r6/s5.sh) -- these kernels wait on memory, not on
+    // 47.2 -> 46.7 us per 4K frame on uint16 RGB, nothing on float RGB (profiles/r06_yuv_ingest.md) -- these kernels wait on memory, not on
     // the toe's three instructions per sample; not kept)
     if constexpr (KIND >= 0) {
 #pragma unroll
@@ -327,11 +327,7 @@ __device__ __forceinline__ void frame_lum(const FRAME& f, int C, const float* lu
             if (c > 0 && C != 3) break;
 #pragma unroll
             for (int i = 0; i < PX; ++i) {
-    #ifdef K1_ABLATE_LUT
-                if constexpr (SRC == SRC_U8) v[c][i] = (float)f.ch[c].code(i);
-#else
                 if constexpr (SRC == SRC_U8) v[c][i] = lutw[c * 256 + f.ch[c].code(i)];
-#endif
                 else v[c][i] = __fmul_rn(lut_entry(lut16, f.ch[c].code(i), e), w[c]);
             }
         }
@@ -350,9 +346,6 @@ __device__ __forceinline__ void frame_lum(const FRAME& f, int C, const float* lu
 // differ in the last bit of a luminance.  CHECK: flag and clip samples outside [0,1] (float sources; codes / 65535 cannot leave the range).
 // No inline assembly here on purpose: an asm instruction that reads the result of v_exp / v_log / v_rcp misses the wait state the compiler
 // inserts between a transcendental and its consumer (gfx940+), and reads a stale register now and then.
-#ifndef K1_PAIRS
-#define K1_PAIRS 1
-#endif
 template <int N, int KIND, bool CHECK, typename B>
 __device__ __forceinline__ void eotf_pairs_exact(v2f (&V)[N], const EotfDev& e, B& bad) {
 #pragma clang fp contract(off)       // every product and sum rounded on its own
@@ -448,11 +441,8 @@ __device__ __forceinline__ void fir_tap_first(v2f& accS, v2f& accT, v2f x, v2f f
         : "=&v"(accS), "=&v"(accT) : "v"(x), "s"(f));
 }
 // TAPC taps = 2*TAPC floats of TemporalArgs::taps2 / YuvArgs::taps2, read from the kernel-argument segment with one scalar load
-#ifndef K1_TAPC
-#define K1_TAPC 4
-#endif
-constexpr int TAPC = K1_TAPC;
-typedef float vtapf __attribute__((ext_vector_type(2 * K1_TAPC)));
+constexpr int TAPC = 4;
+typedef float vtapf __attribute__((ext_vector_type(2 * TAPC)));
 typedef vtapf vtapf_a4 __attribute__((aligned(4)));
 typedef const vtapf_a4 __attribute__((address_space(4)))* karg_taps_p;
 
@@ -461,9 +451,7 @@ typedef const vtapf_a4 __attribute__((address_space(4)))* karg_taps_p;
 // every output pixel is written once as one float4 (test-sust, ref-sust, test-trans, ref-trans).  The raw samples
 // of the next frame are fetched while the current one is filtered (software prefetch, one frame ahead).
 // Reference: fvvdp.py:294-300 (R[:,2cc+s] = sum_k window[s][k] * F[cc].flip(0)[k]).
-#ifndef TDIST
-#define TDIST 1          // frames of raw samples in flight per thread; 2 and 4 measured slower (VGPRs -> occupancy)
-#endif
+constexpr int TDIST = 1;        // frames of raw samples in flight per thread; 2 and 4 measured slower (VGPRs -> occupancy)
 template <int FL, int PX, int SRC>
 __global__ __launch_bounds__(256) void temporal_ring_kernel(const TemporalArgs a) {
     __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
@@ -640,13 +628,8 @@ __device__ __forceinline__ void wave_lds_order() {
 
 // CC = number of colour channels as a compile-time constant (3 or 1): with a run-time `C == 3` around the loads and the
 // table look-ups, every step has control-flow joins and the compiler falls back to s_waitcnt vmcnt(0).
-#ifndef K1_STORE_AUX
-#define K1_STORE_AUX 2     // cache policy of the level-0 stores: 2 = nt.  0 / 1 (sc0) / 16 (sc1) / 18: this kernel within its per-process scatter,
-                           // but the pyramid pass that follows is 2 % slower behind stores that are not nt (tools/experiments/r4_session44.sh)
-#endif
-#ifndef K1_EARLY_WORDS
-#define K1_EARLY_WORDS 1   // widest sample vector (dwords per channel and lane) whose NEXT frame is requested before the current one is converted
-#endif
+constexpr int K1_STORE_AUX = 2;    // cache policy of the level-0 stores: 2 = nt.  0 / 1 (sc0) / 16 (sc1) / 18: this kernel within its per-process
+                                   // scatter, but the pyramid pass that follows is 2 % slower behind stores that are not nt
 template <int FL, int PX, int SRC, int TD, int CC, int KIND>
 __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const float* lutw, float4* s_t, const int block = (int)blockIdx.x) {
     // the window index lists are the only dynamically indexed members of the argument block: read them straight from the
@@ -678,7 +661,7 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
     // newest frame -> ring slot u.  The pair is pinned where it is produced: the compiler otherwise sinks the channel sums
     // to their first use (many steps later), keeping three table values per pixel alive instead of one luminance.
     // closed-form display models run on (test, reference) pairs (packed instructions; the reference's roundings)
-    constexpr bool PAIRS = (K1_PAIRS != 0) && (SRC == SRC_F32 || SRC == SRC_U16) && KIND >= 0 && KIND != FVVDP_EOTF_LUT;
+    constexpr bool PAIRS = (SRC == SRC_F32 || SRC == SRC_U16) && KIND >= 0 && KIND != FVVDP_EOTF_LUT;
     auto push = [&](const RawVecFrame<SRC, PX>& c0, const RawVecFrame<SRC, PX>& c1, v2f (&slot)[PX]) {
         if constexpr (PAIRS) {
             frame_lum_pairs<SRC, PX, CC, KIND>(c0, c1, w, a.e, slot, bad);
@@ -719,22 +702,21 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
 #pragma unroll
     for (int i = 0; i < PX; ++i) soff[i] = (p0 + i * 64 + lane < a.HW) ? (unsigned int)(p0 + i * 64 + lane) * 16u : FVVDP_NO_STORE;
     const unsigned int frame_bytes = (unsigned int)a.HW * 16u;      // <= 531 MB (8K)
-#ifndef K1_NO_ENTRY_DRAIN
     // One drain on the way in: the loop header joins the history (whose last batch requested the first output frames: loads pending, the
     // first step's registers among the youngest) and the back edge (a step's stores behind the prefetch).  Served by one wait, that
     // came out as vmcnt(1) / vmcnt(0) at the top of every FL frames -- the stores just issued and the prefetch drained.  With nothing
     // pending on the entry path the wait at the header is the back edge's own: counted, stores in flight.
     __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15 = no wait)
-#endif
     for (int t0 = 0; t0 < a.n_out; t0 += FL) {
 #pragma unroll
         for (int j = 0; j < FL; ++j) {
             const int t = t0 + j;
             if (t >= a.n_out) break;
             const int u = (FL - 1 + j) % FL;         // ring slot of the newest frame (compile-time after unrolling)
-            // The next frame is requested before this one is converted when a frame is a few registers (8-bit samples); wide
-            // samples (12-24 registers per frame pair) are requested after the conversion has freed the registers.
-            if constexpr (RawVec<SRC, PX>::WORDS <= K1_EARLY_WORDS) {
+            // The next frame is requested before this one is converted when a frame is a few registers (8-bit samples, one dword
+            // per channel and lane); wide samples (12-24 registers per frame pair) are requested after the conversion has freed the
+            // registers (requesting them first too measured no faster).
+            if constexpr (RawVec<SRC, PX>::WORDS == 1) {
                 const RawVecFrame<SRC, PX> cur0 = nx[u % TD][0], cur1 = nx[u % TD][1];
                 prefetch(FL - 1 + t + TD, nx[u % TD][0], nx[u % TD][1]);
                 push(cur0, cur1, ring[u]);
@@ -751,13 +733,8 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
             // of the frame loop, where 2*FL scalar values would have to stay alive next to everything else (spills).
             karg_p tp = ka + offsetof(TemporalArgs, taps2);
             if constexpr (FL > 16) asm volatile("" : "+s"(tp));
-#ifdef K1_ABLATE_FIR
-#pragma unroll
-            for (int c = 0; c >= 0; --c) {
-#else
 #pragma unroll
             for (int c = FL / TAPC - 1; c >= 0; --c) {
-#endif
                 const vtapf tc = *(karg_taps_p)(tp + c * (8 * TAPC));
 #pragma unroll
                 for (int kk = TAPC - 1; kk >= 0; --kk) {
@@ -802,54 +779,24 @@ __device__ __forceinline__ void temporal_vec_cc(const TemporalArgs& a, const flo
 }
 
 // waves per SIMD the register allocation aims at (uint8: 116 / 128 / 168 VGPRs for the 8 / 16 / 32-slot ring)
-#ifndef K1_WAVES8
-#define K1_WAVES8 4
-#endif
-#ifndef K1_WAVES16
-#define K1_WAVES16 4
-#endif
-#ifndef K1_WAVES32
-#define K1_WAVES32 3
-#endif
-#ifndef K1_WAVES64
-#define K1_WAVES64 3     // 64-slot ring (uint8 only, 1 pixel per lane): above 128 fps
-#endif
-#ifndef K1_WAVESX8
-#define K1_WAVESX8 3     // uint16 / float sources: wider raw samples in flight, closed-form display model
-#endif
-#ifndef K1_WAVESF8
-#define K1_WAVESF8 3     // float source, 8-slot ring
-#endif
-#ifndef K1_WAVESX16
-#define K1_WAVESX16 4
-#endif
-#ifndef K1_WAVESX32
-#define K1_WAVESX32 2
-#endif
+constexpr int K1_WAVES8 = 4;
+constexpr int K1_WAVES16 = 4;
+constexpr int K1_WAVES32 = 3;
+constexpr int K1_WAVES64 = 3;      // 64-slot ring (uint8 only, 1 pixel per lane): above 128 fps
+constexpr int K1_WAVESX8 = 3;      // uint16 / float sources: wider raw samples in flight, closed-form display model
+constexpr int K1_WAVESF8 = 3;      // float source, 8-slot ring
+constexpr int K1_WAVESX16 = 4;
+constexpr int K1_WAVESX32 = 2;
 constexpr int k1_waves(int FL, int SRC) {
     return SRC == SRC_U8 ? (FL == 8 ? K1_WAVES8 : (FL == 16 ? K1_WAVES16 : (FL == 32 ? K1_WAVES32 : K1_WAVES64)))
                          : FL == 64 ? K1_WAVES64 : (FL == 8 ? (SRC == SRC_F32 ? K1_WAVESF8 : K1_WAVESX8) : (FL == 16 ? K1_WAVESX16 : K1_WAVESX32));
 }
-#ifdef K1_TIMELINE         // profiling build: (start, end) of every workgroup on the 100 MHz wall clock (tools/gpu_timeline.py k1)
-static __device__ unsigned long long g_k1_timeline[4 * 65536];
-__device__ __forceinline__ void k1_clock_record(int block, unsigned long long t0) {
-    if (threadIdx.x == 0 && block < 65536) {
-        unsigned long long* t = g_k1_timeline + 4 * (size_t)block;
-        t[0] = t0;
-        t[1] = wall_clock64();
-        t[2] = ((unsigned long long)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) << 32) | (unsigned int)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4);
-        t[3] = (unsigned long long)block;
-    }
-}
-#endif
 // Waves per workgroup: the 8-slot ring runs K1_WPB8 = 4 waves per workgroup, each on its own pixel block, the four blocks adjacent
 // in memory (1 KiB of every source plane and 16 KiB of level 0 per frame and workgroup instead of 256 B / 4 KiB).  The waves share
 // the code-value table and nothing else (no barrier after the table is built); a workgroup's waves start together and stay close,
 // so the memory system sees longer contiguous runs: -1.3 ... -1.5 us per 4K frame on every destination buffer, slow or fast
 // (tools/microbench/k1_stream.hip "k1_4w" against "k1", profiles/r05_k1_mode.md; 8 waves: the same; 2 waves: half of it).
-#ifndef K1_WPB8
-#define K1_WPB8 4
-#endif
+constexpr int K1_WPB8 = 4;
 constexpr int k1_wpb(int FL) { return FL == 8 ? K1_WPB8 : 1; }
 template <int FL, int PX, int SRC, int TD = 1>
 __global__ __launch_bounds__(64 * k1_wpb(FL), k1_waves(FL, SRC))
@@ -860,6 +807,7 @@ void temporal_vec_kernel(const TemporalArgs a_byval) {
     // scratch per lane and every filter tap reloaded from it.
     const TemporalArgs& a = *(const TemporalArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     (void)a_byval;
+    static_assert(TD == 1, "one frame of raw samples in flight (temporal_launch.hpp)");
     constexpr int WPB = k1_wpb(FL);
     __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
     __shared__ float4 s_t_all[WPB][64 * (PX + 1)];  // per wave: one padded row of PX float4 per lane
@@ -888,13 +836,7 @@ void temporal_vec_kernel(const TemporalArgs a_byval) {
                 int* const tk = *(int* const __attribute__((address_space(4)))*)(ka + offsetof(TemporalArgs, ticket));
                 if (tk && threadIdx.x == 0) next = (int)gridDim.x + atomicAdd(tk, 1);       // asked for now, looked at after the block
             }
-#ifdef K1_TIMELINE
-            const unsigned long long k1_t0 = wall_clock64();
-#endif
             temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_LUT>(a, lutw, s_t, block);
-#ifdef K1_TIMELINE
-            k1_clock_record(block, k1_t0);
-#endif
             block = __builtin_amdgcn_readfirstlane(next);
             if (block >= n_blocks) break;
             wave_lds_order();                        // the transposes of the next block reuse s_t
@@ -1046,7 +988,7 @@ __global__ __launch_bounds__(256) void temporal_yuv_kernel(const YuvArgs a) {
 }
 
 // ---- vector variant of the YUV ingest (the fast path for W % 4 == 0) -----------------------------------------------
-// Single-wave workgroups, a lane owns PX CONSECUTIVE pixels of one image row (x0 = PX*j; PX = 4 or 2).  Everything that depends
+// Single-wave workgroups, a lane owns PX = 4 CONSECUTIVE pixels of one image row (x0 = PX*j).  Everything that depends
 // only on the pixel position (plane offsets, the bilinear weights of the 4:2:0 chroma upsampling) is computed once per
 // lane; per frame a lane issues one Y load (PX samples) and, per chroma plane and source row, one load of its own PX/2 chroma
 // columns; the two neighbour columns (clamped) come from the adjacent lanes through DPP
@@ -1054,13 +996,11 @@ __global__ __launch_bounds__(256) void temporal_yuv_kernel(const YuvArgs a) {
 // Test and reference stream are converted together as packed (test, reference) pairs (v_pk_* instructions); the
 // result agrees with yuv_lum above to rounding order.  Raw samples of the next frame are prefetched while the
 // current one is converted, and the finished float4 pixels go through the same LDS transpose as temporal_vec_kernel.
-// PX = 2 halves the registers of the window (2*FL*PX) and of everything per pixel: more waves per SIMD where the window is what
-// limits them (the 16-slot window above all), at the price of twice the per-lane work (loads, stores, branches) per pixel.
 template <typename T, bool C420, int PX>
 struct YuvRaw {
-    static constexpr int YW = (PX * (int)sizeof(T) + 3) / 4;      // dwords holding PX samples (PX = 2, 8 bit: half a dword)
+    static constexpr int YW = (PX * (int)sizeof(T) + 3) / 4;      // dwords holding PX samples
     unsigned int y[YW];
-    // 4:2:0: cp[plane][row] = the lane's own chroma columns (PX = 4: columns 2j, 2j+1 packed; PX = 2: column j); the neighbour
+    // 4:2:0: cp[plane][row] = the lane's own chroma columns (2j, 2j+1 packed); the neighbour
     // columns are the finished values of the adjacent lanes (DPP; lanes 0 and 63 of a wave are halo lanes that only supply them).
     // 4:4:4: cp[plane][0..YW-1] = PX samples.
     unsigned int cp[2][2];
@@ -1089,11 +1029,10 @@ struct YuvGeom {           // per-lane constants
 // no vector instruction goes into addressing (global loads: a 64-bit vector add per load, 10 per lane and frame).
 template <int BYTES>
 __device__ __forceinline__ void yuv_load_bytes(__amdgpu_buffer_rsrc_t f, unsigned int off, unsigned int* out) {
-    if constexpr (BYTES == 1) out[0] = (unsigned int)(unsigned char)__builtin_amdgcn_raw_buffer_load_b8(f, (int)off, 0, 0);
-    else if constexpr (BYTES == 2) out[0] = (unsigned int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(f, (int)off, 0, 0);
+    if constexpr (BYTES == 2) out[0] = (unsigned int)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(f, (int)off, 0, 0);
     else if constexpr (BYTES == 4) out[0] = (unsigned int)__builtin_amdgcn_raw_buffer_load_b32(f, (int)off, 0, 0);
     else {
-        static_assert(BYTES == 8, "1, 2, 4 or 8 bytes");
+        static_assert(BYTES == 8, "2, 4 or 8 bytes");
         const v2i t = __builtin_bit_cast(v2i, __builtin_amdgcn_raw_buffer_load_b64(f, (int)off, 0, 0));
         out[0] = (unsigned int)t.x; out[1] = (unsigned int)t.y;
     }
@@ -1133,6 +1072,7 @@ __device__ __forceinline__ v2f pfma_clamp01(v2f a, float s, v2f c) {
 template <typename T, bool C420, bool STDM, int PX>
 __device__ __forceinline__ void yuv_pair_rgb(const YuvRaw<T, C420, PX>& r0, const YuvRaw<T, C420, PX>& r1, const YuvArgs& a,
                                              const YuvGeom& g, float fy, float gy, float fx0, float gx0, v2f (&rgb)[3 * PX]) {
+    static_assert(PX == 4, "4 pixels per lane: the 4:2:0 chroma columns are two per lane");
     auto cf = [&](float c0, float c1) { return clamp2(pfma(v2f{c0, c1}, a.wc, splat(-(128.0f / 224.0f))), -0.5f, 0.5f); };
     auto from_left = [](v2f v) { return v2f{__uint_as_float(lane_left_u32(__float_as_uint(v.x))), __uint_as_float(lane_left_u32(__float_as_uint(v.y)))}; };
     auto from_right = [](v2f v) { return v2f{__uint_as_float(lane_right_u32(__float_as_uint(v.x))), __uint_as_float(lane_right_u32(__float_as_uint(v.y)))}; };
@@ -1148,37 +1088,24 @@ __device__ __forceinline__ void yuv_pair_rgb(const YuvRaw<T, C420, PX>& r0, cons
             // streams; the same values, bit for bit).  At a row start / end the clamped neighbour column is one of the lane's own.
             // An even pixel 2c blends column c (weight fx = .75, or 0 at x = 0) with column c-1, an odd pixel 2c+1 column c (.75)
             // with column c+1 (.25) -- torch's bilinear x2, align_corners=False.
-            if constexpr (PX == 4) {
-                v2f own[2];
+            v2f own[2];
 #pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const v2f a0 = k == 0 ? cf(R::lo(r0.cp[pl][0]), R::lo(r1.cp[pl][0])) : cf(R::hi(r0.cp[pl][0]), R::hi(r1.cp[pl][0]));
-                    const v2f a1 = k == 0 ? cf(R::lo(r0.cp[pl][1]), R::lo(r1.cp[pl][1])) : cf(R::hi(r0.cp[pl][1]), R::hi(r1.cp[pl][1]));
-                    own[k] = pfma(a1, fy, a0 * gy);
-                }
-                const v2f nl = from_left(own[1]);
-                const v2f nr = from_right(own[0]);
-                v2f col[4];
-                col[0] = g.left_own ? own[0] : nl;
-                col[1] = own[0];
-                col[2] = own[1];
-                col[3] = g.right_own ? own[1] : nr;
-                uv[pl][0] = pfma(col[1], fx0, col[0] * gx0);
-                uv[pl][1] = pfma(col[2], 0.25f, col[1] * 0.75f);
-                uv[pl][2] = pfma(col[2], 0.75f, col[1] * 0.25f);
-                uv[pl][3] = pfma(col[3], 0.25f, col[2] * 0.75f);
-            } else {
-                static_assert(PX == 2, "4 or 2 pixels per lane");
-                const v2f a0 = cf(R::lo(r0.cp[pl][0]), R::lo(r1.cp[pl][0]));
-                const v2f a1 = cf(R::lo(r0.cp[pl][1]), R::lo(r1.cp[pl][1]));
-                const v2f own = pfma(a1, fy, a0 * gy);
-                const v2f nl = from_left(own);
-                const v2f nr = from_right(own);
-                const v2f cl = g.left_own ? own : nl;
-                const v2f cr = g.right_own ? own : nr;
-                uv[pl][0] = pfma(own, fx0, cl * gx0);
-                uv[pl][1] = pfma(cr, 0.25f, own * 0.75f);
+            for (int k = 0; k < 2; ++k) {
+                const v2f a0 = k == 0 ? cf(R::lo(r0.cp[pl][0]), R::lo(r1.cp[pl][0])) : cf(R::hi(r0.cp[pl][0]), R::hi(r1.cp[pl][0]));
+                const v2f a1 = k == 0 ? cf(R::lo(r0.cp[pl][1]), R::lo(r1.cp[pl][1])) : cf(R::hi(r0.cp[pl][1]), R::hi(r1.cp[pl][1]));
+                own[k] = pfma(a1, fy, a0 * gy);
             }
+            const v2f nl = from_left(own[1]);
+            const v2f nr = from_right(own[0]);
+            v2f col[4];
+            col[0] = g.left_own ? own[0] : nl;
+            col[1] = own[0];
+            col[2] = own[1];
+            col[3] = g.right_own ? own[1] : nr;
+            uv[pl][0] = pfma(col[1], fx0, col[0] * gx0);
+            uv[pl][1] = pfma(col[2], 0.25f, col[1] * 0.75f);
+            uv[pl][2] = pfma(col[2], 0.75f, col[1] * 0.25f);
+            uv[pl][3] = pfma(col[3], 0.25f, col[2] * 0.75f);
         } else {
 #pragma unroll
             for (int i = 0; i < PX; ++i) uv[pl][i] = cf(r0.c444(pl, i), r1.c444(pl, i));
@@ -1316,12 +1243,8 @@ __device__ __forceinline__ void yuv_window_dispatch(int slot, v2f (&win)[FL][PX]
 }
 
 #define YUV_QUADS 62     // pixel groups (PX consecutive pixels, one per lane) written per wave
-#ifndef YUV_TD8
-#define YUV_TD8 2        // frames of raw samples in flight per lane, 8-slot window
-#endif
-#ifndef YUV_TD16
-#define YUV_TD16 1       // 16-slot window: 128 registers of window leave room for one frame of raw samples (2 -> 2-11 spilled dwords)
-#endif
+constexpr int YUV_TD8 = 2;       // frames of raw samples in flight per lane, 8-slot window
+constexpr int YUV_TD16 = 1;      // 16-slot window: 128 registers of window leave room for one frame of raw samples (2 -> 2-11 spilled dwords)
 // One rolled loop over the frames, straight-line inside (see temporal_vec_kernel for why: counted waits instead of
 // drains).  The conversion of a frame is a few hundred instructions and exists once; the window of the last FL luminance
 // pairs stays where it is (yuv_window_step above) and only the short FIR exists FL times.
@@ -1338,11 +1261,7 @@ __device__ __forceinline__ void temporal_yuv_vec_body(const YuvArgs& a, float4* 
     // chroma columns to lanes 1 and 62 (quads are clamped to the frame: a clamped lane duplicates its neighbour,
     // which then sits at a row start / end and does not look at it)
     const int p0 = block * (YUV_QUADS * PX);
-#ifdef YUV_ABLATE_MEM      // profiling ablation: every wave converts the same 64 quads of source frame 0 (cache hits), nothing is stored
-    const int quad = lane;
-#else
     const int quad = min(max(block * YUV_QUADS - 1 + lane, 0), HW / PX - 1);
-#endif
     const int pl = quad * PX;
     YuvGeom g;
     float g_fy = 0.0f, g_gy = 0.0f;      // vertical bilinear weights
@@ -1384,11 +1303,7 @@ __device__ __forceinline__ void temporal_yuv_vec_body(const YuvArgs& a, float4* 
     const int total = FL - 1 + a.n_out;
     const unsigned int src_bytes = (unsigned int)(HW + 2 * uvplane) * (unsigned int)sizeof(T);      // one planar frame
     auto prefetch = [&](int v, YuvRaw<T, C420, PX>& f0, YuvRaw<T, C420, PX>& f1) {
-#ifdef YUV_ABLATE_MEM
-        const size_t off = (size_t)(idx[min(v, total - 1)] & 0) * a.frame_stride;
-#else
         const size_t off = (size_t)idx[min(v, total - 1)] * a.frame_stride;      // past the end: the last frame again (unused)
-#endif
         f0 = yuv_fetch<T, C420, PX>(src_rsrc(reinterpret_cast<const char*>(a.src[0]) + off * sizeof(T), src_bytes), g);
         f1 = yuv_fetch<T, C420, PX>(src_rsrc(reinterpret_cast<const char*>(a.src[1]) + off * sizeof(T), src_bytes), g);
     };
@@ -1403,14 +1318,12 @@ __device__ __forceinline__ void temporal_yuv_vec_body(const YuvArgs& a, float4* 
         soff[i] = (q < YUV_QUADS * PX && p0 + q < HW) ? (unsigned int)(p0 + q) * 16u : FVVDP_NO_STORE;
     }
     const unsigned int frame_bytes = (unsigned int)HW * 16u;
-#ifndef YUV_NO_ENTRY_DRAIN
     // The loop header joins the entry path (TD frames of loads pending, the registers the first step reads among the LAST requested) and
     // the back edge (the same registers requested two steps ago, with a step's stores and the other slot's loads behind them): the
     // compiler's wait at the top of the loop has to serve both and came out as vmcnt(1) / vmcnt(0) -- a drain of the stores just issued
     // and of the prefetch one step old, every TD frames.  Draining ONCE here leaves the back edge as the only path with loads pending,
     // and the wait inside the loop becomes a counted one (stores and the younger prefetch stay in flight).
     __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15 = no wait)
-#endif
     for (int v0 = 0; v0 < total; v0 += TD) {
 #pragma unroll
         for (int d = 0; d < TD; ++d) {
@@ -1432,11 +1345,7 @@ __device__ __forceinline__ void temporal_yuv_vec_body(const YuvArgs& a, float4* 
             for (int i = 0; i < PX; ++i)
                 s_t[lane * (PX + 1) + i] = make_float4(acc_s[i].x, acc_s[i].y, acc_t[i].x, acc_t[i].y);
             wave_lds_order();
-#ifdef YUV_ABLATE_MEM
-            const bool live = v < -1000000;
-#else
             const bool live = (v >= FL - 1) && (v < total);
-#endif
             // history frames and the steps past the end store nothing: their descriptor covers 0 bytes (a scalar select; the per-lane
             // offsets stay as they are -- round 6: -4 vector selects per frame)
             const __amdgpu_buffer_rsrc_t o = level_rsrc(l0_frame(a.out, max(v - (FL - 1), 0)), live ? frame_bytes : 0u);
@@ -1451,48 +1360,26 @@ __device__ __forceinline__ void temporal_yuv_vec_body(const YuvArgs& a, float4* 
     }
 }
 
-// Pixels per lane of the vector kernel, per window length (4 or 2; A/B: tools/experiments/r6/s11.sh)
-#ifndef YUV_PX8
-#define YUV_PX8 4
-#endif
-#ifndef YUV_PX16
-#define YUV_PX16 4
-#endif
-constexpr int yuv_px(int FL) { return FL == 8 ? YUV_PX8 : YUV_PX16; }
+// Pixels per lane of the vector kernel: 4.  2 pixels per lane (4-5 waves per SIMD) measured 16 % slower (profiles/r06_yuv_ingest.md).
+constexpr int YUV_PX = 4;
 // waves per SIMD the register allocation aims at
-#ifndef YUV_WAVES8
-#define YUV_WAVES8 (YUV_PX8 == 4 ? 3 : 5)
-#endif
-#ifndef YUV_WAVES16
-#define YUV_WAVES16 (YUV_PX16 == 4 ? 2 : 4)
-#endif
-#ifndef YUV_WAVES8_WIDE
-#define YUV_WAVES8_WIDE (YUV_PX8 == 4 ? 2 : 4)      // 16-bit 4:4:4 (8 raw dwords per frame pair more at PX = 4), PQ (the longest display model)
-#endif
+constexpr int YUV_WAVES8 = 3;
+constexpr int YUV_WAVES16 = 2;
+constexpr int YUV_WAVES8_WIDE = 2;      // 16-bit 4:4:4 (8 raw dwords per frame pair more), PQ (the longest display model)
 // KIND = display model (compile-time: the host picks the instantiation): one loop body per kernel.  With a switch over the six
 // bodies inside one kernel, scalar values of the prologue stayed alive across all of them and spilled (8 SGPRs in the 16-slot
 // 4:2:0 kernels).
-// Waves per workgroup (A/B switch): temporal_vec_kernel gains 4 % from 4 waves per workgroup on adjacent pixel blocks (K1_WPB8); this kernel
-// does not -- 37.5-38.1 against 37.7-38.2 us per 4K frame, 1080p 10.5-11.2 against 10.2-10.4 (tools/experiments/r6/s5.sh), and the
-// 8-bit 4:2:0 sRGB instantiation then spills one register -- so it stays at one wave per workgroup.
-#ifndef YUV_WPB8
-#define YUV_WPB8 1
-#endif
-constexpr int yuv_wpb(int FL) { return FL == 8 ? YUV_WPB8 : 1; }
+// One wave per workgroup: temporal_vec_kernel gains 4 % from 4 waves per workgroup on adjacent pixel blocks (K1_WPB8); this kernel
+// does not -- 37.5-38.1 against 37.7-38.2 us per 4K frame, 1080p 10.5-11.2 against 10.2-10.4 (profiles/r06_yuv_ingest.md), and the
+// 8-bit 4:2:0 sRGB instantiation then spills one register.
 template <int FL, typename T, bool C420, int KIND, bool STDM>
-__global__ __launch_bounds__(64 * yuv_wpb(FL), (FL == 8 ? (((sizeof(T) == 2 && !C420) || KIND == FVVDP_EOTF_PQ) ? YUV_WAVES8_WIDE : YUV_WAVES8) : YUV_WAVES16))
+__global__ __launch_bounds__(64, (FL == 8 ? (((sizeof(T) == 2 && !C420) || KIND == FVVDP_EOTF_PQ) ? YUV_WAVES8_WIDE : YUV_WAVES8) : YUV_WAVES16))
 void temporal_yuv_vec_kernel(const YuvArgs a_byval) {
     const YuvArgs& a = *(const YuvArgs*)__builtin_amdgcn_kernarg_segment_ptr();     // see temporal_vec_kernel
     (void)a_byval;
-    constexpr int WPB = yuv_wpb(FL);
-    constexpr int PX = yuv_px(FL);
-    __shared__ float4 s_t_all[WPB][64 * (PX + 1)];
-    const int wave = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    const int block = (int)blockIdx.x * WPB + wave;           // this wave's run of 62 pixel groups
-    if constexpr (WPB > 1) {
-        if (block * (YUV_QUADS * PX) >= a.W * a.H) return;     // the last workgroup of a frame whose block count is not a multiple
-    }
-    temporal_yuv_vec_body<FL, T, C420, KIND, STDM, PX>(a, s_t_all[wave], (int)(threadIdx.x & 63), block);
+    __shared__ float4 s_t[64 * (YUV_PX + 1)];
+    // this wave's run of 62 pixel groups: workgroup b
+    temporal_yuv_vec_body<FL, T, C420, KIND, STDM, YUV_PX>(a, s_t, (int)(threadIdx.x & 63), (int)blockIdx.x);
 }
 
 // Generic (any fl, any frame size) version: one thread per pixel per output frame, the window is re-read from

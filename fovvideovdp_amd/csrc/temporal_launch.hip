@@ -19,8 +19,8 @@ static constexpr int SRC = DT == FVVDP_U8 ? SRC_U8 : (DT == FVVDP_U16 ? SRC_U16 
 
 template <int FL>
 static void launch_vec(const TemporalArgs& a, hipStream_t st) {
-    constexpr int PX = k1_px(FL, DT);
-    constexpr int TD = FL == 8 ? K1_TD8 : (FL == 16 ? K1_TD16 : (FL == 32 ? K1_TD32 : 1));
+    constexpr int PX = k1_px(FL);
+    constexpr int TD = 1;
     constexpr int WPB = k1_wpb(FL);                       // waves per workgroup, one pixel block each
     const int n_blocks = (a.HW + 64 * PX - 1) / (64 * PX);
     dim3 grid((n_blocks + WPB - 1) / WPB), block(64 * WPB);
@@ -56,13 +56,6 @@ static void launch_generic(const GenericArgs& a, hipStream_t st) {
 #define K1_NAME(f) f##_u16
 #else
 #define K1_NAME(f) f##_f32
-#endif
-#if defined(K1_TIMELINE) && K1_PART == 0      // profiling build only: not part of the C ABI
-extern "C" int fvvdp_debug_k1_timeline(unsigned long long* h_out, size_t n_records) {
-    if (n_records > 65536) n_records = 65536;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    return hipMemcpyFromSymbol(h_out, HIP_SYMBOL(g_k1_timeline), n_records * 4 * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
 #endif
 void K1_NAME(k1_vec)(int FL, const TemporalArgs& a, hipStream_t st) {
     if (FL == 8) launch_vec<8>(a, st);
@@ -134,9 +127,7 @@ static bool yuv_matrix_is_standard(const YuvArgs& a) {
 }
 template <int FL, typename T, bool C420, bool STDM>
 static void launch_yuv_vec_kind(const YuvArgs& a, dim3 grid, hipStream_t st) {
-    constexpr int WPB = yuv_wpb(FL);                       // waves per workgroup, one run of 62 pixel quads each
-    const dim3 block(64 * WPB);
-    grid.x = (grid.x + WPB - 1) / WPB;
+    const dim3 block(64);                                  // one wave per workgroup and run of 62 pixel quads
     switch (a.e.kind) {          // the display model is a template constant of the kernel
         case FVVDP_EOTF_SRGB: hipLaunchKernelGGL((temporal_yuv_vec_kernel<FL, T, C420, FVVDP_EOTF_SRGB, STDM>), grid, block, 0, st, a); break;
         case FVVDP_EOTF_GAMMA: hipLaunchKernelGGL((temporal_yuv_vec_kernel<FL, T, C420, FVVDP_EOTF_GAMMA, STDM>), grid, block, 0, st, a); break;
@@ -154,7 +145,7 @@ static void launch_yuv_vec_kind(bool general, const YuvArgs& a, dim3 grid, hipSt
 template <int FL>
 static void launch_yuv_vec(int bytes, bool c420, bool general, const YuvArgs& a, hipStream_t st) {
     const int HW = a.W * a.H;
-    dim3 grid((HW / yuv_px(FL) + YUV_QUADS - 1) / YUV_QUADS);      // one wave per run of 62 pixel groups
+    dim3 grid((HW / YUV_PX + YUV_QUADS - 1) / YUV_QUADS);      // one wave per run of 62 pixel groups
     if (bytes == 1) {
         if (c420) launch_yuv_vec_kind<FL, unsigned char, true>(general, a, grid, st);
         else launch_yuv_vec_kind<FL, unsigned char, false>(general, a, grid, st);

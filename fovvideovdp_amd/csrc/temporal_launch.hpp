@@ -4,38 +4,15 @@
 #pragma once
 #include "temporal_kernels.hpp"
 
-// Pixels per lane (PX) and frames of raw samples in flight (TD) of temporal_vec_kernel, per ring length and sample type.
+// Pixels per lane (PX) of temporal_vec_kernel, per ring length; one frame of raw samples in flight (TD = 1).
 // Measured at 4K (tools/gpu_fps.py): the long rings are register-bound (2*FL*PX ring registers), float samples are 4x
 // wider than 8-bit ones in the prefetch registers.
-#ifndef K1_PX8
-#define K1_PX8 4
-#endif
-#ifndef K1_PXF8
-#define K1_PXF8 4         // float samples, 8-slot ring
-#endif
-#ifndef K1_PX16
-#define K1_PX16 2
-#endif
-#ifndef K1_PX32
-#define K1_PX32 2
-#endif
-#ifndef K1_TD8
-#define K1_TD8 1
-#endif
-#ifndef K1_TD16
-#define K1_TD16 1
-#endif
-#ifndef K1_TD32
-#define K1_TD32 1
-#endif
+static constexpr int k1_px(int FL) { return FL == 8 ? 4 : (FL == 64 ? 1 : 2); }
 // what the 64-slot ring (temporal filters of 33-64 taps, 129-256 fps) is instantiated for
 static inline bool k1_ring64_ok(int dtype, int C, int eotf_kind) {
     if (dtype == FVVDP_U8) return true;
     if (C == 3 && (eotf_kind == FVVDP_EOTF_SRGB || eotf_kind == FVVDP_EOTF_PQ)) return true;      // uint16 (closed form) / float RGB
     return dtype == FVVDP_F32 && C == 1 && eotf_kind == FVVDP_EOTF_NONE;                          // luminance frames
-}
-static constexpr int k1_px(int FL, int dtype) {
-    return FL == 8 ? (dtype == FVVDP_F32 ? K1_PXF8 : K1_PX8) : (FL == 16 ? K1_PX16 : (FL == 32 ? K1_PX32 : 1));
 }
 
 // FL in {8, 16, 32}; dtype FVVDP_U8 / U16 / F32.  FL = 64: see k1_ring64_ok().

@@ -72,7 +72,6 @@ python $R/bench.py --full --width 1920 --height 1080 --display standard_fhd --no
 FVVDP_ALLOC=malloc FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_malloc.json 2>/dev/null
 FVVDP_PLACEMENT_PROBE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_chunks.json 2>/dev/null
 FVVDP_BAND_INRANGE=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_clamps.json 2>/dev/null
-[ -f $R/build_variants/k1wpb1.so ] && FVVDP_LIB=$R/build_variants/k1wpb1.so python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_k1wpb1.json 2>/dev/null
 FVVDP_BAND2_TICKET=0 python $R/bench.py --full --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_noticket.json 2>/dev/null
 python $R/bench.py --full --shard frames --no-cpu-baseline --no-h2d --no-measure-traffic > $OUT/bench_frames.json 2>/dev/null
 # round 6: the one-rank collective off / forced (the default is auto = forced where RCCL initialises), configs[3] with its roofline_fov block

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Turn gpurun_out/prof_bundle/ (written by tools/collect_profiles.sh on the GPU box, ONE gpurun call = one box) into the
-tracked files profiles/<round>_final_kernel_trace.md, profiles/<round>_pmc_level0.json, profiles/<round>_parity_stages.md (round 6 on: `<round>_parity.md` is the evidence file of tools/make_r6_evidence.py).
+tracked files profiles/<round>_final_kernel_trace.md, profiles/<round>_pmc_level0.json, profiles/<round>_parity_stages.md (round 6 on: `<round>_parity.md` is a separate evidence file).
 usage: make_profile_doc.py r02"""
 import json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -121,7 +121,7 @@ def quoted_figures():
     rs = jp["roofline_step"]
     out.append("* whole step: %.2f GB per pair, %.2f TB/s = %.3f; kernels back to back %.3f ms of %.3f ms" % (
         rs["bytes_per_step"] / 1e9, rs["achieved"] / 1e3, rs["frac"], rs["kernels_back_to_back_ms"], rs["ms_per_step"]))
-    for name in ("bench_malloc.json", "bench_chunks.json", "bench_clamps.json", "bench_k1wpb1.json", "bench_noticket.json", "bench_pairs8.json", "bench_frames.json",
+    for name in ("bench_malloc.json", "bench_chunks.json", "bench_clamps.json", "bench_noticket.json", "bench_pairs8.json", "bench_frames.json",
                  "bench_fhd.json", "bench_fhd_plain.json", "bench_collective_off.json", "bench_collective_force.json"):
         try:
             j = json.loads(rd(name).split("\n")[-1])
@@ -224,15 +224,13 @@ bench.py JSON of the unprofiled run on the same box, right before:
 
 Same box, one switch at a time: the level-0 buffer fixed to one kind and no comparison at creation (`FVVDP_ALLOC=malloc
 FVVDP_PLACEMENT_PROBE=0`, then `FVVDP_PLACEMENT_PROBE=0` = 32 MB chunks; the default line above keeps the fastest of four candidates,
-`level0_alloc` says which: `profiles/r05_k1_mode.md`), `FVVDP_BAND_INRANGE=0` (the pyramid kernel with its clamps), the temporal kernel
-with ONE wave per workgroup (`FVVDP_LIB=build_variants/k1wpb1.so`, built with `-DK1_WPB8=1`: round 4's launch shape), and
+`level0_alloc` says which: `profiles/r05_k1_mode.md`), `FVVDP_BAND_INRANGE=0` (the pyramid kernel with its clamps) and
 `FVVDP_BAND2_TICKET=0` (static split of the pyramid kernel's work items, `profiles/r05_band2_tickets.md`):
 
 ```
 {rd('bench_malloc.json')}
 {rd('bench_chunks.json')}
 {rd('bench_clamps.json')}
-{rd('bench_k1wpb1.json')}
 {rd('bench_noticket.json')}
 ```
 

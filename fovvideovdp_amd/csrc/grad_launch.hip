@@ -33,6 +33,14 @@ static int gfail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return gfail(FVVDP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
+// adj_sweep_kernel on `planes` planes of one level, for the video backward (video_grad_launch.hip): the kernel is defined in
+// this translation unit only, so the other one launches it through here
+hipError_t grad_sweep_launch(const GradSweepArgs& sa, int planes, hipStream_t st) {
+    const size_t hw = (size_t)sa.w * sa.h;
+    hipLaunchKernelGGL(adj_sweep_kernel, dim3((unsigned int)((hw + 255) / 256), planes), dim3(256), 0, st, sa);
+    return hipGetLastError();
+}
+
 // Workspace, in floats, each part 64-float (256 B) aligned:
 //   coef [n][n_bands] | GL_b [n][h_b][w_b] for b in [0, n_bands) | GG_L [n][h_L][w_L] for L in [1, n_bands]
 struct GradLayout {

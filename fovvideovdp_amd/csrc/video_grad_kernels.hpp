@@ -1,0 +1,308 @@
+// Backward of the video JOD (include/fvvdp_hip_video_grad.h): the adjoint of fvvdp_temporal_channels + fvvdp_bands_forward +
+// fvvdp_pool_jod with respect to the test clip.  Instantiated and launched by video_grad_launch.hip.
+//
+// Forward, per output frame f and temporal channel cc (fvvdp.py:258-300, 337-357, 395-467, 574-596):
+//   X_cc[f] = sum_k taps[cc][k] Lum[idx[f + fl - 1 - k]],  Lum[j] = sum_c w_c EOTF(V_c[j])           (level 0, test plane of cc)
+//   pyramid, contrast, masking and spatial pooling per plane as for a still image (grad_kernels.hpp) -> Q[b, cc, f]
+//   Q_sc[cc, f] = (sum_b (w_cc Q)^beta_sch)^(1/beta_sch),  Q_tc[f] = (sum_cc Q_sc^beta_tch)^(1/beta_tch),
+//   Q = (sum_f Q_tc^beta_t / N)^(1/beta_t),  JOD = sgn(a) (|a|^(1/beta_jod) Q)^beta_jod + 10
+// Backward, per batch of n frames:
+//   video_coef_kernel    c[f][cc][b] = gamma dJOD/dQ dQ/dQ_tc[f] dQ_tc/dQ_sc[cc] dQ_sc/dQ[b,cc,f] Q^(1-beta) / n_b   (one workgroup)
+//   video_layer_kernel   GL_b[f][cc]  = c D^(beta-1) dD/dT' S gain m_b / L_bkg        (both channels of a pixel per thread)
+//   adj_sweep_kernel     GG_L = GL_L - Expand^T(GL_{L-1}) + Reduce^T(GG_{L+1})        (grad_kernels.hpp, on the 2n planes)
+//   video_level0_kernel  g0[f][cc]    = GL_0 + Reduce^T(GG_1)                          (into the clip-long buffer)
+// and once per clip:
+//   video_input_kernel   dtest_c[j]   = w_c EOTF'(V_c[j]) sum_{p : idx[p] = j} A[p],  A[p] = sum_cc sum_k taps[cc][k] g0[p-(fl-1)+k][cc]
+#pragma once
+
+// ---- coefficients ---------------------------------------------------------------------------------------------------------
+struct VideoCoefArgs {
+    const float* Q;         // Q_per_ch of the forward, [n_bands][2][N]
+    const float* gamma;     // [1] upstream gradient of the JOD
+    float* coef;            // [n][2][n_bands]
+    int n, n_bands, N, f0;
+    float beta, beta_sch, beta_tch, beta_t, w_transient, jod_a, beta_jod;
+    float inv_npx[FVVDP_MAX_BANDS];     // 1 / (h_b w_b)
+};
+
+// Q_sc of both channels and Q_tc of frame f, as pool_frame (aux_kernels.hpp) in double
+__device__ __forceinline__ double video_qtc(const VideoCoefArgs& a, int f, double (&qsc)[2]) {
+    double qt = 0.0;
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        const double wc = cc == 1 ? (double)a.w_transient : 1.0;
+        double qs = 0.0;
+        for (int b = 0; b < a.n_bands; ++b)
+            qs += pow(fabs((double)a.Q[((size_t)b * 2 + cc) * a.N + f] * wc), (double)a.beta_sch);
+        qsc[cc] = pow(qs, 1.0 / a.beta_sch);
+        qt += pow(qsc[cc], (double)a.beta_tch);
+    }
+    return pow(qt, 1.0 / a.beta_tch);
+}
+
+// One workgroup.  First the clip-level norm over all N frames (thread t sums frames t, t + 256, ... in order, then a fixed
+// tree: the same value in every batch of the clip), then thread k the coefficients of frame f0 + k.  A factor is zero where
+// the norm it divides by is zero (an identical clip or frame), as the reference's norm backward gives.
+__global__ __launch_bounds__(256) void video_coef_kernel(const VideoCoefArgs a) {
+    __shared__ double s_part[256];
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (int f = tid; f < a.N; f += 256) {
+        double qsc[2];
+        acc += pow(video_qtc(a, f, qsc), (double)a.beta_t);
+    }
+    s_part[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) s_part[tid] += s_part[tid + o];
+        __syncthreads();
+    }
+    const double q_all = pow(s_part[0] / (double)a.N, 1.0 / a.beta_t);
+    double dj = 0.0;                                                                    // gamma dJOD/dQ
+    if (q_all > 0.0) {
+        const double sgn = a.jod_a < 0.0f ? -1.0 : 1.0;
+        const double aq = pow(fabs((double)a.jod_a), 1.0 / a.beta_jod) * q_all;
+        dj = (double)a.gamma[0] * sgn * a.beta_jod * pow(aq, (double)a.beta_jod) / q_all;
+    }
+    for (int k = tid; k < a.n; k += 256) {
+        const int f = a.f0 + k;
+        double qsc[2];
+        const double qtc = video_qtc(a, f, qsc);
+        const double gf = (qtc > 0.0 && dj != 0.0) ? dj * pow(qtc / q_all, a.beta_t - 1.0) / (double)a.N : 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+            const double wc = cc == 1 ? (double)a.w_transient : 1.0;
+            const double gc = (qsc[cc] > 0.0 && gf != 0.0) ? gf * pow(qsc[cc] / qtc, a.beta_tch - 1.0) : 0.0;
+            for (int b = 0; b < a.n_bands; ++b) {
+                const double qb = fabs((double)a.Q[((size_t)b * 2 + cc) * a.N + f]);
+                double c = 0.0;
+                if (qb * wc > 0.0 && gc != 0.0)
+                    c = gc * wc * pow(qb * wc / qsc[cc], a.beta_sch - 1.0) * pow(qb, 1.0 - a.beta) * a.inv_npx[b];
+                a.coef[((size_t)k * 2 + cc) * a.n_bands + b] = (float)c;
+            }
+        }
+    }
+}
+
+// ---- layer gradients: pointwise on the maps, every band in one launch, both temporal channels per thread --------------------
+struct VideoBand {
+    const float* D;         // [n][2][h][w]  plane cc
+    const float* Cn;        // [n][4][h][w]  plane 2cc: test contrast x m_b, plane 2cc + 1: reference
+    const float* L;         // [n][h][w]
+    const float* S;         // [n][2][h][w]  plane cc: sensitivity before the gain
+    float* GL;              // [n][2][h][w]  out
+    int w, h, blk0;         // first workgroup of this band in blockIdx.x
+    float m;                // band multiplier
+};
+struct VideoLayerArgs {
+    VideoBand band[FVVDP_MAX_BANDS];
+    const float* coef;      // [n][2][n_bands]
+    int n_bands;
+    float p, q[2], k_mask, beta, gain, cmax_hi, dmax_hi;
+};
+
+// adj_layer_kernel's formula for one temporal channel, the powers in the forward's log2 / exp2 form (band_kernel.hpp):
+// three transcendental pairs per value instead of three powf.  s = S gain; s * m_lb = S gain m / L_bkg is d(T')/d(layer).
+__device__ __forceinline__ float video_layer_one(float c, float T, float R, float Dm, float s, float m_lb, float q, float m,
+                                                 const VideoLayerArgs& a) {
+    // zero: no pooling weight, D == 0 (an identical pixel), the d_max clamp or the contrast clamp binds
+    if (!(c != 0.0f && Dm > 0.0f && Dm < a.dmax_hi && T < m * a.cmax_hi)) return 0.0f;
+    const float Tp = T * s, Rp = R * s;
+    const float u = Tp - Rp, au = fabsf(u);
+    const float aT = fabsf(Tp), aR = fabsf(Rp);
+    const float M = a.k_mask * fminf(aT, aR);
+    const float Mq = M > 0.0f ? fast_exp2(q * fast_log2(M)) : 0.0f;
+    const float den = 1.0f + Mq;
+    const float lnum = a.p * fast_log2(au);                 // au == 0 (with D > 0 it cannot be): -inf, num = 0
+    const float num = fast_exp2(lnum);
+    const float rden = fast_rcp(den);
+    const float D = num * rden;
+    // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
+    float dD = au > 0.0f ? copysignf(a.p * num * fast_rcp(au), u) * rden : 0.0f;
+    if (M > 0.0f && aT <= aR) {
+        const float share = aT < aR ? 1.0f : 0.5f;
+        dD -= share * copysignf(D * rden * q * Mq * fast_rcp(aT), Tp);
+    }
+    const float Db = fast_exp2((a.beta - 1.0f) * (lnum - fast_log2(den)));      // D^(beta - 1)
+    return c * Db * dD * s * m_lb;
+}
+
+__global__ __launch_bounds__(256) void video_layer_kernel(const VideoLayerArgs a) {
+    int b = 0;
+    while (b + 1 < a.n_bands && (int)blockIdx.x >= a.band[b + 1].blk0) ++b;
+    const VideoBand& B = a.band[b];
+    const int k = blockIdx.y;
+    const size_t hw = (size_t)B.w * B.h;
+    const size_t px = (size_t)((int)blockIdx.x - B.blk0) * 256 + threadIdx.x;
+    if (px >= hw) return;
+    const float m_lb = B.m / B.L[(size_t)k * hw + px];
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+        const float c = a.coef[((size_t)k * 2 + cc) * a.n_bands + b];
+        const float T = B.Cn[((size_t)k * 4 + 2 * cc) * hw + px];
+        const float R = B.Cn[((size_t)k * 4 + 2 * cc + 1) * hw + px];
+        const float Dm = B.D[((size_t)k * 2 + cc) * hw + px];
+        const float s = B.S[((size_t)k * 2 + cc) * hw + px] * a.gain;
+        B.GL[((size_t)k * 2 + cc) * hw + px] = video_layer_one(c, T, R, Dm, s, m_lb, a.q[cc], B.m, a);
+    }
+}
+
+// ---- level 0 of the sweep: grad_input_kernel without the display model ------------------------------------------------------
+struct VideoLevel0Args {
+    const float* GL0;       // [2n][h][w] layer gradient of level 0
+    const float* GG1;       // [2n][hc][wc] gradient of G_1
+    float* g0;              // [2n][h][w] out: the batch's columns of the clip-long buffer
+    int w, h, wc, hc;
+};
+
+// grid (ceil(w / 256), h, 2n): the row comes from the block, no division per pixel
+__global__ __launch_bounds__(256) void video_level0_kernel(const VideoLevel0Args a) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, k = blockIdx.z;
+    if (x >= a.w) return;
+    const size_t o = ((size_t)k * a.h + y) * a.w + x;
+    a.g0[o] = a.GL0[o] + reduce_t(a.GG1 + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
+}
+
+// ---- temporal transpose + display model: the mirror image of temporal_vec_kernel ---------------------------------------------
+// A lane owns PX consecutive pixels for the whole launch and walks the window-list positions p = 0 .. N + fl - 2 once.  Position
+// p collects taps[cc][k] g0[t][cc] from the output frames t = p - (fl - 1) + k, i.e. step t adds to the positions t .. t + fl - 1;
+// after step p nothing more arrives at position p.  The fl open positions live in a register ring that SHIFTS by one slot
+// per step: slot m holds position p + m, and the shift is free because the multiply-add that adds step p's term to slot m
+// writes its result to slot m - 1 (three-operand FMA) -- the loop over p is a plain loop, nothing is unrolled over time, and
+// the code stays small whatever FL.  tapsT[m] = taps[.][fl - 1 - m] (zero for m >= fl) is the tap slot m receives.
+// A finished position p < fl belongs to the head (the frames the temporal padding shows before frame 0): it goes to the side
+// buffer head[p]; a finished position p >= fl is the one streaming term of frame p - fl + 1.  Frame j = p - (fl - 1) is
+// complete after step p: its head positions (fold list: sorted by frame, then position -- a cursor walks it) are added in
+// ascending order, then the streaming term, then the display model's derivative -- a fixed order, no atomics.  A frame no
+// window shows (circular padding, N > fl: frame 0) sums nothing and gets exact zeros.
+#define VG_MAX_FL 64
+struct VideoInputArgs {
+    const float* g0;        // [N][2][HW]
+    const float* test;      // element (c, f, px) at c * chan_stride + f * frame_stride + px
+    float* grad;            // the same layout
+    float* head;            // [fl][HW]
+    size_t chan_stride, frame_stride;
+    int C, HW, N, fl;
+    EotfDev e;
+    float wgt[3];
+    float tapsT[VG_MAX_FL][2];      // {sustained, transient} tap of ring slot m
+    int fold_frame[VG_MAX_FL];      // [fl] sorted; padded with -1
+    int fold_pos[VG_MAX_FL];
+};
+
+template <int PX>
+struct VgVec {
+    float v[PX];
+};
+template <int PX>
+__device__ __forceinline__ VgVec<PX> vg_load(const float* p) {
+    VgVec<PX> r;
+    if constexpr (PX == 4) {
+        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else if constexpr (PX == 2) {
+        const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(p));
+        r.v[0] = t.x; r.v[1] = t.y;
+    } else {
+        r.v[0] = __builtin_nontemporal_load(p);
+    }
+    return r;
+}
+template <int PX>
+__device__ __forceinline__ void vg_store(float* p, const VgVec<PX>& r) {
+    if constexpr (PX == 4) __builtin_nontemporal_store(v4f{r.v[0], r.v[1], r.v[2], r.v[3]}, reinterpret_cast<v4f*>(p));
+    else if constexpr (PX == 2) __builtin_nontemporal_store(v2f{r.v[0], r.v[1]}, reinterpret_cast<v2f*>(p));
+    else __builtin_nontemporal_store(r.v[0], p);
+}
+
+// FL: ring slots (fl rounded up to 8 / 16 / 32 / 64).  PX: pixels per lane (4 or 2: HW and the strides are multiples of PX and
+// the pointers PX-float aligned; 1: any size).
+template <int FL, int PX>
+__global__ __launch_bounds__(256) void video_input_kernel(const VideoInputArgs a) {
+    const size_t px = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
+    if (px >= (size_t)a.HW) return;
+    // fold list and (long rings) taps straight from the kernel-argument segment: scalar loads, no copy of the block to scratch
+    typedef const int __attribute__((address_space(4)))* karg_int_p;
+    typedef const char __attribute__((address_space(4)))* karg_p;
+    const karg_p ka = (karg_p)__builtin_amdgcn_kernarg_segment_ptr();
+    const karg_int_p fold_frame = (karg_int_p)(ka + offsetof(VideoInputArgs, fold_frame));
+    const karg_int_p fold_pos = (karg_int_p)(ka + offsetof(VideoInputArgs, fold_pos));
+    float ring[FL - 1][PX];                     // before step p: slot m = position p + m (slot FL - 1 is still empty: not kept)
+#pragma unroll
+    for (int m = 0; m < FL - 1; ++m)
+#pragma unroll
+        for (int i = 0; i < PX; ++i) ring[m][i] = 0.0f;
+    int cur = 0;                                // cursor in the fold list (wave-uniform)
+    const int total = a.N + a.fl - 1;
+    const size_t HW = (size_t)a.HW;
+    for (int p = 0; p < total; ++p) {
+        const int j = p - (a.fl - 1);           // the frame that is complete after this step
+        VgVec<PX> gs, gt;
+        if (p < a.N) {
+            gs = vg_load<PX>(a.g0 + (size_t)p * 2 * HW + px);
+            gt = vg_load<PX>(a.g0 + ((size_t)p * 2 + 1) * HW + px);
+        } else {                                // past the last output frame: the open positions only drain
+#pragma unroll
+            for (int i = 0; i < PX; ++i) gs.v[i] = gt.v[i] = 0.0f;
+        }
+        VgVec<PX> V[3];                         // the test samples of frame j, requested before the arithmetic
+        if (j >= 0) {
+            const float* t = a.test + (size_t)j * a.frame_stride + px;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                if (c < a.C) V[c] = vg_load<PX>(t + (size_t)c * a.chan_stride);
+        }
+        // taps: long rings re-read them in every step, TAPC at a time through a laundered pointer -- hoisted out of the loop,
+        // 2 FL scalar values would stay alive and spill (see temporal_ring_kernel)
+        karg_p tp = ka + offsetof(VideoInputArgs, tapsT);
+        if constexpr (FL > 8) asm volatile("" : "+s"(tp));
+        VgVec<PX> done;                         // position p
+#pragma unroll
+        for (int c = 0; c < FL / TAPC; ++c) {
+            karg_p tpc = tp + c * (8 * TAPC);
+            if constexpr (FL > 16) asm volatile("" : "+s"(tpc));       // (else the chunks' loads are merged back into one)
+            const vtapf tc = *(karg_taps_p)tpc;
+#pragma unroll
+            for (int kk = 0; kk < TAPC; ++kk) {
+                const int m = c * TAPC + kk;
+                const float fs = tc[2 * kk], ft = tc[2 * kk + 1];
+#pragma unroll
+                for (int i = 0; i < PX; ++i) {
+                    const float old = m < FL - 1 ? ring[m][i] : 0.0f;
+                    float v = fmaf(fs, gs.v[i], fmaf(ft, gt.v[i], old));
+                    asm volatile("" : "+v"(v));             // pinned where it is produced: left alone, the compiler sinks the ring
+                                                            // updates below the branches that follow and keeps every tap alive
+                    if (m == 0) done.v[i] = v;              // position p: nothing more arrives
+                    else ring[m - 1][i] = v;                // the shift: slot m becomes slot m - 1 of the next step
+                }
+            }
+            if constexpr (FL > 8) __builtin_amdgcn_sched_barrier(0);      // one chunk of taps in scalar registers at a time
+        }
+        if (p < a.fl) vg_store<PX>(a.head + (size_t)p * HW + px, done);
+        if (j >= 0) {
+            VgVec<PX> s;
+#pragma unroll
+            for (int i = 0; i < PX; ++i) s.v[i] = 0.0f;
+            while (cur < a.fl && fold_frame[cur] == j) {
+                const VgVec<PX> hd = vg_load<PX>(a.head + (size_t)fold_pos[cur] * HW + px);
+#pragma unroll
+                for (int i = 0; i < PX; ++i) s.v[i] += hd.v[i];
+                ++cur;
+            }
+            if (j >= 1) {
+#pragma unroll
+                for (int i = 0; i < PX; ++i) s.v[i] += done.v[i];
+            }
+            float* o = a.grad + (size_t)j * a.frame_stride + px;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c < a.C) {
+                    VgVec<PX> r;
+#pragma unroll
+                    for (int i = 0; i < PX; ++i) r.v[i] = a.wgt[c] * eotf_grad(V[c].v[i], a.e) * s.v[i];
+                    vg_store<PX>(o + (size_t)c * a.chan_stride, r);
+                }
+            }
+        }
+    }
+}

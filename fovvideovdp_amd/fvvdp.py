@@ -84,7 +84,7 @@ def _refuse_grad(a):
     if isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("Gradients through the metric are not supported on the HIP path (forward-only kernels); "
                            "detach the inputs or wrap the call in torch.no_grad() (differentiable still images: "
-                           "fvvdp.jod_images)")
+                           "fvvdp.jod_images; differentiable clips: fvvdp.jod_video)")
 
 
 def _image_stack(test, reference, dim_order):
@@ -308,6 +308,23 @@ class fvvdp:
         forward with per-band maps in batches of up to `self.grad_batch` pairs (None: as many as about 4 GB of maps allow)."""
         from .image_grad import jod_images
         return jod_images(self, test, reference, dim_order, fixation_point)
+
+    def jod_video(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+        """Extension: the JOD of one clip as a differentiable 0-d fp32 tensor on the metric's device, for losses such as
+        `10 - metric.jod_video(x, ref, frames_per_second=30)`.  The value is bit-identical to
+        predict(test.detach(), reference, dim_order, frames_per_second, fixation_point)[0].  When `test` requires grad (and grad
+        mode is on), backward() puts dJOD/dtest into `test`, whatever its layout or device; the reference is a constant (a
+        reference that requires grad is refused).  float32 samples behind a display model with a closed form (sRGB, gamma, PQ,
+        linear, absolute), C = 1 or 3, one clip (B = 1) of at least 2 frames (a single frame: jod_images), every temporal
+        padding, frame rates of up to 256 per second (a temporal filter of up to 64 taps), foveated or not (`fixation_point`
+        as predict takes it).  Samples the display model clamps get a zero gradient, and so does a frame that no temporal
+        window shows (`circular` padding of a clip more than one frame longer than the filter: frame 0).  Nothing is
+        synchronised with the host (a user geometry model's gaze conversion aside): no out-of-range warning, no heat maps.
+        Double backward is not supported.
+        The backward re-runs the forward with per-band maps in batches of up to `self.grad_batch` frames (None: as many as
+        about 4 GB of maps allow); the gradient does not depend on the batching, bit for bit."""
+        from .video_grad import jod_video
+        return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point)
 
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,

@@ -1,0 +1,235 @@
+"""fvvdp.jod_video on the GPU: values against predict, gradients against the reference's autograd (goldens g19) and against
+finite differences of the float64 CPU oracle, batch invariance, determinism, layouts, interleaving, refusals, host
+synchronisation and a short optimisation.  Tolerances are 3x the worst error measured on MI355X."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import fovvideovdp_amd as fv
+from fovvideovdp_amd import _native as nat
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_grad_cases import CASES, case_gaze, case_inputs, load_golden          # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+
+# max|g - g_ref| / max|g_ref| over the whole clip against the reference's autograd, per case: 3x the value measured on
+# MI355X (a 2.1e-5, b 1.8e-5, c 1.5e-5, d 3.9e-4, e 2.1e-4, f 2.7e-5, g 2.5e-5, h 7.8e-5, i 0, j 6.3e-5); the image path's
+# widest is 1.6e-3 (foveated), and the foveated case d is the widest here too
+GOLDEN_TOL = {"a_gray_30_replicate": 6.5e-5, "b_rgb_60_circular": 5.5e-5, "c_gray_30_circular": 4.5e-5,
+              "d_rgb_30_pingpong_fov": 1.2e-3, "e_rgb_pq_oob": 6.3e-4, "f_gray_linear": 8.2e-5, "g_rgb_gamma22": 7.4e-5,
+              "h_rgb_2f_120": 2.4e-4, "i_identical": 0.0, "j_partly_identical": 1.9e-4}
+# |<g, d> - (JOD64(x+) - JOD64(x-))| / |JOD64(x+) - JOD64(x-)|: 3x the worst measured on MI355X (2.8e-4: gray 6 f 68x121 @30
+# replicate; the 1920x1080 clip 1.6e-5); the image path's bound is 9e-3
+FD_TOL = 8.3e-4
+
+
+def _metric(display, padding="replicate", opt=None):
+    opt = opt or {}
+    kw = {}
+    if "photometry" in opt:
+        kw["display_photometry"] = fv.fvvdp_display_photo_eotf(**opt["photometry"])
+    return fv.fvvdp(display_name=display, foveated=bool(opt.get("foveated")), temp_padding=padding, quiet=True, device=DEV, **kw)
+
+
+def _grad(m, test, ref, fps, fix=None, dim_order="CFHW", weight=None):
+    x = test.clone().requires_grad_(True)
+    jod = m.jod_video(x, ref, dim_order=dim_order, frames_per_second=fps, fixation_point=fix)
+    (jod if weight is None else weight * jod).backward()
+    return jod.detach(), x.grad
+
+
+def _synth(C, N, H, W, seed):
+    from fovvideovdp_amd.synth import synth_video_pair
+    t8, r8 = synth_video_pair(N, H, W, C=C, seed_ref=seed, seed_test=seed + 7)
+    return (t8[0].numpy().astype(np.float32) / np.float32(255.0), r8[0].numpy().astype(np.float32) / np.float32(255.0))
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_golden_gradients(name):
+    C, N, H, W, fps, padding, display, opt = CASES[name]
+    t, r = case_inputs(name)
+    jod_ref, g_ref = load_golden(name)
+    m = _metric(display, padding, opt)
+    fix = case_gaze(name)
+    test, ref = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    jod, g = _grad(m, test, ref, fps, fix=fix)
+    q_p, _ = m.predict(test, ref, dim_order="CFHW", frames_per_second=fps, fixation_point=fix)
+    assert jod.dim() == 0 and jod.dtype == torch.float32 and jod.device == DEV
+    assert torch.equal(jod, q_p), (jod, q_p)
+    assert abs(float(jod) - jod_ref) < 2e-3, (float(jod), jod_ref)
+    g = g.cpu().numpy()
+    assert g.shape == g_ref.shape and np.isfinite(g).all()
+    gmax = float(np.abs(g_ref).max())
+    err = float(np.abs(g - g_ref).max())
+    print("%s: max|g - g_ref| = %.3e, max|g_ref| = %.3e, rel %.3e" % (name, err, gmax, err / max(gmax, 1e-30)))
+    if name == "i_identical":
+        assert (g == 0).all() and (g_ref == 0).all()
+    else:
+        assert err <= GOLDEN_TOL[name] * gmax
+    if opt.get("oob"):
+        oob = (t < 0) | (t > 1)
+        assert oob.any() and (g[oob] == 0).all() and (g_ref[oob] == 0).all()
+    if name == "c_gray_30_circular":              # no temporal window shows frame 0
+        assert (g_ref[:, 0] == 0).all() and (g[:, 0] == 0).all() and (g[:, 1:] != 0).any()
+
+
+def _fd_check(display, padding, fps, t, r, n_dirs, eps=3e-5, seed=0):
+    """<g, d> against a central difference of the float64 oracle, d = the realised x+ - x-."""
+    from oracle import fvvdp_oracle as orc
+    m = _metric(display, padding)
+    test, ref = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    _, g = _grad(m, test, ref, fps)
+    g = g.double().cpu().numpy()
+    assert np.isfinite(g).all()
+    o = orc.Oracle(display, dtype=np.float64, temp_padding=padding)
+    rng = np.random.default_rng(seed)
+    worst = 0.0
+    for _ in range(n_dirs):
+        d = rng.standard_normal(t.shape)
+        d[(t < 4 * eps) | (t > 1 - 4 * eps)] = 0.0          # stay clear of the display model's clamps
+        xp = (t + eps * d).astype(np.float32)
+        xm = (t - eps * d).astype(np.float32)
+        dj = (o.predict(xp, r, dim_order="CFHW", frames_per_second=fps)[0] -
+              o.predict(xm, r, dim_order="CFHW", frames_per_second=fps)[0])
+        lin = float((g * (xp.astype(np.float64) - xm.astype(np.float64))).sum())
+        rel = abs(lin - dj) / abs(dj)
+        worst = max(worst, rel)
+        print("%s %s %s @%g: <g,d> %.6e  dJOD64 %.6e  rel %.3e" % (display, padding, t.shape, fps, lin, dj, rel))
+    assert worst <= FD_TOL
+
+
+@pytest.mark.parametrize("C,N,H,W,display,padding,fps,n_dirs", [
+    (1, 6, 68, 121, "standard_fhd", "replicate", 30, 2), (3, 5, 68, 121, "standard_4k", "circular", 60, 2),
+    (1, 4, 68, 121, "standard_4k", "pingpong", 120, 2), (3, 6, 135, 240, "standard_4k", "pingpong", 30, 1),
+    (1, 7, 68, 121, "standard_fhd", "circular", 120, 1), (3, 3, 1080, 1920, "standard_4k", "replicate", 30, 1)])
+def test_finite_differences_fp64_oracle(C, N, H, W, display, padding, fps, n_dirs):
+    t, r = _synth(C, N, H, W, seed=H + W + N)
+    _fd_check(display, padding, fps, t, r, n_dirs)
+
+
+def test_determinism_and_batch_invariance():
+    t, r = _synth(3, 7, 64, 96, seed=21)
+    T, R = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    for padding in ("replicate", "circular", "pingpong"):
+        m = _metric("standard_4k", padding)
+        j0, g0 = _grad(m, T, R, 30)
+        j1, g1 = _grad(m, T, R, 30)
+        assert torch.equal(g0, g1) and torch.equal(j0, j1)
+        assert torch.isfinite(g0).all() and (g0 != 0).any()
+        for gb in (1, 3):
+            m.grad_batch = gb
+            _, gs = _grad(m, T, R, 30)
+            assert torch.equal(gs, g0), (padding, gb)
+
+
+def test_layouts():
+    m = _metric("standard_4k")
+    t, r = _synth(3, 5, 64, 96, seed=22)
+    T, R = torch.from_numpy(t), torch.from_numpy(r)
+    _, g = _grad(m, T.to(DEV), R.to(DEV), 30)
+    # host FHWC tensor: the gradient lands on the host, in FHWC
+    xh = T.permute(1, 2, 3, 0).contiguous().requires_grad_(True)
+    jod = m.jod_video(xh, R.permute(1, 2, 3, 0).contiguous(), dim_order="FHWC", frames_per_second=30)
+    jod.backward()
+    assert xh.grad.device.type == "cpu" and xh.grad.shape == xh.shape
+    assert torch.equal(xh.grad.permute(3, 0, 1, 2).to(DEV), g)
+    # non-contiguous device view of a larger leaf
+    base = torch.zeros((1, 3, 5, 64, 104), device=DEV)
+    base[..., 4:100] = T.to(DEV)
+    base.requires_grad_(True)
+    view = base[..., 4:100]
+    assert not view.is_contiguous()
+    m.jod_video(view, R.to(DEV)[None], frames_per_second=30).backward()
+    assert torch.equal(base.grad[0, ..., 4:100], g)
+    assert (base.grad[..., :4] == 0).all() and (base.grad[..., 100:] == 0).all()
+
+
+def test_upstream_weights():
+    m = _metric("standard_4k")
+    t, r = _synth(3, 5, 64, 96, seed=23)
+    T, R = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    _, g1 = _grad(m, T, R, 30)
+    _, g4 = _grad(m, T, R, 30, weight=4.0)
+    _, gh = _grad(m, T, R, 30, weight=-0.5)
+    _, gz = _grad(m, T, R, 30, weight=0.0)
+    assert torch.equal(g4, 4.0 * g1) and torch.equal(gh, -0.5 * g1) and (gz == 0).all()
+
+
+def test_interleaved_calls():
+    m = _metric("standard_4k")
+    t, r = _synth(3, 6, 72, 120, seed=24)
+    A, RA = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    _, g_plain = _grad(m, A, RA, 30)
+    x = A.clone().requires_grad_(True)
+    jod = m.jod_video(x, RA, dim_order="CFHW", frames_per_second=30)
+    t2, r2 = _synth(3, 4, 130, 90, seed=25)
+    m.predict(torch.from_numpy(t2).to(DEV), torch.from_numpy(r2).to(DEV), dim_order="CFHW", frames_per_second=60)
+    m.jod_images(torch.from_numpy(t2[:, 0][None]).to(DEV).requires_grad_(True),
+                 torch.from_numpy(r2[:, 0][None]).to(DEV)).sum().backward()
+    jod.backward()
+    assert torch.equal(x.grad, g_plain)
+
+
+def test_refusals():
+    m = _metric("standard_4k")
+    t, r = _synth(3, 4, 64, 96, seed=26)
+    x = torch.from_numpy(t).to(DEV).requires_grad_(True)
+    R = torch.from_numpy(r).to(DEV)
+    jod = m.jod_video(x, R, dim_order="CFHW", frames_per_second=30)
+    (g,) = torch.autograd.grad(jod, x, create_graph=True)
+    with pytest.raises(RuntimeError):
+        g.sum().backward()
+    with pytest.raises(RuntimeError, match="reference are not supported"):
+        m.jod_video(x, R.clone().requires_grad_(True), dim_order="CFHW", frames_per_second=30)
+    with pytest.raises(RuntimeError, match="Gradients through the metric are not supported"):
+        m.predict(x, R, dim_order="CFHW", frames_per_second=30)
+
+
+def _call_stats(m):
+    out = (ctypes.c_int64 * 3)()
+    nat.check(nat.lib().fvvdp_ctx_call_stats(m._ctx.handle, out))
+    return [int(v) for v in out]
+
+
+def test_backward_adds_no_host_sync():
+    """{host synchronisations, allocations, frees} inside the per-frame entry points of the context: the backward of a clip adds
+    nothing to what its forward left (the re-run with maps writes into the caller's buffers), first use included, and a second
+    forward + backward adds nothing either."""
+    m = _metric("standard_4k")
+    t, r = _synth(3, 6, 64, 96, seed=27)
+    T, R = torch.from_numpy(t).to(DEV), torch.from_numpy(r).to(DEV)
+    x = T.clone().requires_grad_(True)
+    jod = m.jod_video(x, R, dim_order="CFHW", frames_per_second=30)
+    after_fwd = _call_stats(m)
+    jod.backward()
+    after_bwd = _call_stats(m)
+    print("call stats after forward %s, after backward %s" % (after_fwd, after_bwd))
+    assert after_bwd == after_fwd
+    _grad(m, T, R, 30)
+    assert _call_stats(m) == after_fwd
+
+
+def test_gradient_ascent_raises_jod():
+    m = _metric("standard_fhd")
+    t, r = _synth(3, 6, 128, 128, seed=28)
+    rng = np.random.default_rng(3)
+    x = torch.from_numpy(np.clip(r + 0.06 * rng.standard_normal(r.shape), 0, 1).astype(np.float32)).to(DEV)
+    R = torch.from_numpy(r).to(DEV)
+    prev = None
+    for step in range(20):
+        xg = x.clone().requires_grad_(True)
+        jod = m.jod_video(xg, R, dim_order="CFHW", frames_per_second=30)
+        jod.backward()
+        q = float(jod.detach())
+        if prev is not None:
+            assert q > prev, (step, q, prev)
+        prev = q
+        with torch.no_grad():
+            x = (x + 0.004 * xg.grad / xg.grad.abs().max()).clamp(0, 1)
+    print("JOD after 20 steps: %.4f" % prev)

@@ -3,10 +3,8 @@
 // what the caller passes, never a context, and changes nothing the forward path or the still-image backward compiles.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 
 #include "fvvdp_hip.h"
@@ -15,69 +13,21 @@
 #include "temporal_kernels.hpp"
 #include "grad_common.hpp"
 #include "video_grad_kernels.hpp"
-
-int fvvdp_fail_from(int code, const char* msg);      // fvvdp_hip.hip: sets the message of fvvdp_last_error
-hipError_t grad_sweep_launch(const GradSweepArgs& sa, int planes, hipStream_t st);      // grad_launch.hip: adj_sweep_kernel
+#include "grad_host.hpp"
 
 static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == VG_MAX_FL, "the header states the ring's reach");
 
-static int vfail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-static int vfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return fvvdp_fail_from(code, buf);
-}
-
-#define VGRAD_HIP_TRY(expr)                                                                              \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return vfail(FVVDP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
-// Workspace, in floats, each part 64-float (256 B) aligned:
-//   coef [n][2][n_bands] | GL_b [n][2][h_b][w_b] for b in [0, n_bands) | GG_L [n][2][h_L][w_L] for L in [1, n_bands]
-struct VideoGradLayout {
-    int w[FVVDP_MAX_BANDS + 1], h[FVVDP_MAX_BANDS + 1];
-    size_t coef, gl[FVVDP_MAX_BANDS], gg[FVVDP_MAX_BANDS + 1], total;
-};
-
-static size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
-
-static void video_grad_layout(int width, int height, int n_bands, int n, VideoGradLayout& L) {
-    L.w[0] = width;
-    L.h[0] = height;
-    for (int b = 1; b <= n_bands; ++b) {            // ceil(/2), as the context's levels (fvvdp_lpyr_dec.py:198)
-        L.w[b] = (L.w[b - 1] + 1) / 2;
-        L.h[b] = (L.h[b - 1] + 1) / 2;
-    }
-    size_t off = 0;
-    L.coef = off;
-    off += align64((size_t)n * 2 * n_bands);
-    for (int b = 0; b < n_bands; ++b) {
-        L.gl[b] = off;
-        off += align64((size_t)n * 2 * L.w[b] * L.h[b]);
-    }
-    L.gg[0] = 0;
-    for (int b = 1; b <= n_bands; ++b) {
-        L.gg[b] = off;
-        off += align64((size_t)n * 2 * L.w[b] * L.h[b]);
-    }
-    L.total = off;
-}
-
-// n <= 16384: the 2n planes of a batch are one grid dimension (65535 at most); a context holds 128 frames anyway
-static bool bad_dims(int width, int height, int n_bands, int n) {
-    return width < 1 || height < 1 || n < 1 || n > 16384 || n_bands < 1 || n_bands > FVVDP_MAX_BANDS || height > 65535;
+// n <= 16384: the 2n planes of a batch are one grid dimension (65535 at most); a context holds 128 frames anyway.
+// height <= 65535: the rows of level 0 are another (video_level0_kernel)
+static int check_dims(int width, int height, int n_bands, int n) {
+    return grad_check_dims(width, height, n_bands, n, 16384, 65535, "frames");
 }
 
 extern "C" int fvvdp_video_grad_workspace(int width, int height, int n_bands, int n, size_t* bytes) {
-    if (!bytes) return vfail(FVVDP_EINVAL, "null argument");
-    if (bad_dims(width, height, n_bands, n)) return vfail(FVVDP_EINVAL, "bad shape %dx%d, %d bands, %d frames", width, height, n_bands, n);
-    VideoGradLayout L;
-    video_grad_layout(width, height, n_bands, n, L);
+    if (!bytes) return grad_fail(FVVDP_EINVAL, "null argument");
+    GRAD_CHECK(check_dims(width, height, n_bands, n));
+    GradLayout L;
+    grad_layout(width, height, n_bands, n, 2, L);
     *bytes = L.total * sizeof(float);
     return FVVDP_OK;
 }
@@ -86,21 +36,16 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
                                        const fvvdp_pool_params* pool, const float* d_Q, int n_frames, int f0,
                                        const float* d_gamma, const fvvdp_band_maps* maps, float* d_g0, void* d_work,
                                        size_t work_bytes, void* stream) {
-    if (!prm || !pool || !d_Q || !d_gamma || !maps || !d_g0 || !d_work) return vfail(FVVDP_EINVAL, "null argument");
-    if (bad_dims(width, height, n_bands, n)) return vfail(FVVDP_EINVAL, "bad shape %dx%d, %d bands, %d frames", width, height, n_bands, n);
+    if (!prm || !pool || !d_Q || !d_gamma || !maps || !d_g0 || !d_work) return grad_fail(FVVDP_EINVAL, "null argument");
+    GRAD_CHECK(check_dims(width, height, n_bands, n));
     if (n_frames < 1 || f0 < 0 || f0 + n > n_frames)
-        return vfail(FVVDP_EINVAL, "frames [%d, %d) lie outside the clip of %d frames", f0, f0 + n, n_frames);
-    if (!(pool->beta_sch > 0.0f && pool->beta_tch > 0.0f && pool->beta_t > 0.0f && pool->beta_jod > 0.0f && prm->beta > 0.0f))
-        return vfail(FVVDP_EINVAL, "pooling exponents must be positive");
-    for (int b = 0; b < n_bands; ++b)
-        if (!maps[b].d_D || !maps[b].d_contrast || !maps[b].d_lbkg || !maps[b].d_S)
-            return vfail(FVVDP_EINVAL, "band %d: every map (D, contrast, L_bkg, S) is required", b);
-    if (reinterpret_cast<uintptr_t>(d_work) % 256 != 0) return vfail(FVVDP_EINVAL, "workspace must be 256-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_g0) % 4 != 0) return vfail(FVVDP_EINVAL, "d_g0 must be aligned to 4 bytes");
-    VideoGradLayout L;
-    video_grad_layout(width, height, n_bands, n, L);
-    if (work_bytes < L.total * sizeof(float))
-        return vfail(FVVDP_EINVAL, "workspace of %zu bytes is below the %zu needed", work_bytes, L.total * sizeof(float));
+        return grad_fail(FVVDP_EINVAL, "frames [%d, %d) lie outside the clip of %d frames", f0, f0 + n, n_frames);
+    GRAD_CHECK(grad_check_exponents({pool->beta_sch, pool->beta_tch, pool->beta_t, pool->beta_jod, prm->beta}));
+    GRAD_CHECK(grad_check_maps(maps, n_bands));
+    if (reinterpret_cast<uintptr_t>(d_g0) % 4 != 0) return grad_fail(FVVDP_EINVAL, "d_g0 must be aligned to 4 bytes");
+    GradLayout L;
+    grad_layout(width, height, n_bands, n, 2, L);
+    GRAD_CHECK(grad_check_workspace(d_work, work_bytes, L));
     float* ws = static_cast<float*>(d_work);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const size_t HW = (size_t)width * height;
@@ -124,54 +69,19 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
     ca.beta_jod = pool->beta_jod;
     for (int b = 0; b < n_bands; ++b) ca.inv_npx[b] = (float)(1.0 / ((double)L.w[b] * L.h[b]));
     hipLaunchKernelGGL(video_coef_kernel, dim3(1), dim3(256), 0, st, ca);
-    VGRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(hipGetLastError());
 
     // 2. layer gradients of every band, both temporal channels
     VideoLayerArgs la;
     memset(&la, 0, sizeof(la));
-    int blocks = 0;
-    for (int b = 0; b < n_bands; ++b) {
-        VideoBand& B = la.band[b];
-        B.D = maps[b].d_D;
-        B.Cn = maps[b].d_contrast;
-        B.L = maps[b].d_lbkg;
-        B.S = maps[b].d_S;
-        B.GL = ws + L.gl[b];
-        B.w = L.w[b];
-        B.h = L.h[b];
-        B.blk0 = blocks;
-        B.m = b == 0 ? 1.0f : 2.0f;                  // lpyr.get_band (fvvdp_lpyr_dec.py:57-63)
-        blocks += (int)(((size_t)L.w[b] * L.h[b] + 255) / 256);
-    }
-    la.coef = ws + L.coef;
-    la.n_bands = n_bands;
-    la.p = prm->mask_p;
+    const int blocks = grad_fill_layer(la, maps, ws, L, n_bands, prm);
     la.q[0] = prm->mask_q[0];
     la.q[1] = prm->mask_q[1];
-    la.k_mask = prm->mask_k;
-    la.beta = prm->beta;
-    la.gain = prm->sens_gain;
-    // the maps hold the clamped values, rounded: a value within 2^-20 of a clamp counts as clamped
-    la.cmax_hi = prm->contrast_max * (1.0f - 0x1p-20f);
-    la.dmax_hi = prm->d_max * (1.0f - 0x1p-20f);
     hipLaunchKernelGGL(video_layer_kernel, dim3(blocks, n), dim3(256), 0, st, la);
-    VGRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(hipGetLastError());
 
     // 3. coarse to fine on the 2n planes: G_{n_bands} (base band) ... G_1
-    for (int lv = n_bands; lv >= 1; --lv) {
-        GradSweepArgs sa;
-        sa.GL = lv < n_bands ? ws + L.gl[lv] : nullptr;
-        sa.GLf = ws + L.gl[lv - 1];
-        sa.GGc = lv < n_bands ? ws + L.gg[lv + 1] : nullptr;
-        sa.GG = ws + L.gg[lv];
-        sa.w = L.w[lv];
-        sa.h = L.h[lv];
-        sa.wf = L.w[lv - 1];
-        sa.hf = L.h[lv - 1];
-        sa.wc = lv < n_bands ? L.w[lv + 1] : 0;
-        sa.hc = lv < n_bands ? L.h[lv + 1] : 0;
-        VGRAD_HIP_TRY(grad_sweep_launch(sa, 2 * n, st));
-    }
+    GRAD_HIP_TRY(grad_sweep_levels(ws, L, n_bands, 2 * n, st));
 
     // 4. level 0 into the clip-long buffer
     VideoLevel0Args za;
@@ -183,7 +93,7 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
     za.wc = L.w[1];
     za.hc = L.h[1];
     hipLaunchKernelGGL(video_level0_kernel, dim3((width + 255) / 256, height, 2 * n), dim3(256), 0, st, za);
-    VGRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }
 
@@ -204,35 +114,33 @@ extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const
                                       int C, size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf,
                                       const float* h_rgb2y, float* d_head, size_t head_bytes, void* stream) {
     if (!d_g0 || !h_fold_frame || !h_fold_pos || !h_taps || !d_test || !d_grad || !eotf || !d_head)
-        return vfail(FVVDP_EINVAL, "null argument");
-    if (width < 1 || height < 1 || n_frames < 1) return vfail(FVVDP_EINVAL, "bad shape %dx%d, %d frames", width, height, n_frames);
+        return grad_fail(FVVDP_EINVAL, "null argument");
+    if (width < 1 || height < 1 || n_frames < 1) return grad_fail(FVVDP_EINVAL, "bad shape %dx%d, %d frames", width, height, n_frames);
     const size_t HW = (size_t)width * height;
-    if (HW > 0x7FFFFFFFu) return vfail(FVVDP_EINVAL, "frame of %zu pixels is too large", HW);
-    if (fl < 1 || fl > FVVDP_MAX_TAPS) return vfail(FVVDP_EINVAL, "filter length %d outside [1, %d]", fl, FVVDP_MAX_TAPS);
+    if (HW > 0x7FFFFFFFu) return grad_fail(FVVDP_EINVAL, "frame of %zu pixels is too large", HW);
+    if (fl < 1 || fl > FVVDP_MAX_TAPS) return grad_fail(FVVDP_EINVAL, "filter length %d outside [1, %d]", fl, FVVDP_MAX_TAPS);
     if (fl > FVVDP_VIDEO_GRAD_MAX_TAPS)
-        return vfail(FVVDP_EUNSUPPORTED, "the video backward covers temporal filters of up to %d taps (256 frames per second); "
+        return grad_fail(FVVDP_EUNSUPPORTED, "the video backward covers temporal filters of up to %d taps (256 frames per second); "
                                          "this one has %d", FVVDP_VIDEO_GRAD_MAX_TAPS, fl);
-    if (C != 1 && C != 3) return vfail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
-    if (C == 3 && !h_rgb2y) return vfail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
-    if (frame_stride < HW) return vfail(FVVDP_EINVAL, "frame_stride %zu is below the frame size %zu", frame_stride, HW);
-    if (C == 3 && chan_stride < HW) return vfail(FVVDP_EINVAL, "chan_stride %zu is below the frame size %zu", chan_stride, HW);
-    if (eotf->kind < FVVDP_EOTF_SRGB || eotf->kind > FVVDP_EOTF_ABSOLUTE)
-        return vfail(FVVDP_EINVAL, "gradients need a closed-form display model (SRGB, GAMMA, PQ, LINEAR or ABSOLUTE)");
+    GRAD_CHECK(grad_check_channels(C, h_rgb2y));
+    if (frame_stride < HW) return grad_fail(FVVDP_EINVAL, "frame_stride %zu is below the frame size %zu", frame_stride, HW);
+    if (C == 3 && chan_stride < HW) return grad_fail(FVVDP_EINVAL, "chan_stride %zu is below the frame size %zu", chan_stride, HW);
+    GRAD_CHECK(grad_check_closed_form(eotf));
     // the fold list: every head position exactly once, frames inside the clip, sorted by frame and then by position
     bool seen[VG_MAX_FL] = {false};
     for (int i = 0; i < fl; ++i) {
         const int f = h_fold_frame[i], p = h_fold_pos[i];
-        if (f < 0 || f >= n_frames) return vfail(FVVDP_EINVAL, "fold list entry %d names frame %d outside [0, %d)", i, f, n_frames);
-        if (p < 0 || p >= fl || seen[p]) return vfail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
+        if (f < 0 || f >= n_frames) return grad_fail(FVVDP_EINVAL, "fold list entry %d names frame %d outside [0, %d)", i, f, n_frames);
+        if (p < 0 || p >= fl || seen[p]) return grad_fail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
         seen[p] = true;
         if (i > 0 && (f < h_fold_frame[i - 1] || (f == h_fold_frame[i - 1] && p < h_fold_pos[i - 1])))
-            return vfail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
+            return grad_fail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
     }
     if (head_bytes < (size_t)fl * HW * sizeof(float))
-        return vfail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
+        return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_test) |
                            reinterpret_cast<uintptr_t>(d_grad) | reinterpret_cast<uintptr_t>(d_head);
-    if (ptrs % 4 != 0) return vfail(FVVDP_EINVAL, "device pointers must be aligned to 4 bytes");
+    if (ptrs % 4 != 0) return grad_fail(FVVDP_EINVAL, "device pointers must be aligned to 4 bytes");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     VideoInputArgs ia;
@@ -247,15 +155,7 @@ extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const
     ia.HW = (int)HW;
     ia.N = n_frames;
     ia.fl = fl;
-    ia.e.kind = eotf->kind;
-    ia.e.scale = eotf->Y_peak - eotf->Y_black;
-    ia.e.y_black = eotf->Y_black;
-    ia.e.y_peak = eotf->Y_peak;
-    ia.e.gamma = eotf->gamma;
-    ia.e.l_min = eotf->L_min;
-    ia.e.l_max = eotf->L_max;
-    ia.e.lut = nullptr;
-    if (C == 3) { ia.wgt[0] = h_rgb2y[0]; ia.wgt[1] = h_rgb2y[1]; ia.wgt[2] = h_rgb2y[2]; } else { ia.wgt[0] = 1.0f; }
+    grad_fill_eotf(ia.e, ia.wgt, eotf, C, h_rgb2y);
     for (int m = 0; m < fl; ++m) {                  // ring slot m of step p is position p + m: it receives tap fl - 1 - m
         ia.tapsT[m][0] = h_taps[fl - 1 - m];
         ia.tapsT[m][1] = h_taps[fl + fl - 1 - m];
@@ -273,6 +173,6 @@ extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const
         case 32: launch_input<32>(ia, vec, st); break;
         default: launch_input<64>(ia, vec, st); break;
     }
-    VGRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }

@@ -61,6 +61,11 @@ def _band_frequencies(W, H, ppd):
     return height, freqs
 
 
+def filter_length(fps):
+    """Taps of the temporal filters at `fps` frames per second (fvvdp.py:236 of the reference)."""
+    return int(np.ceil(250.0 / (1000.0 / fps)))
+
+
 def window_frame_indices(N, fl, temp_padding):
     """Source frame for every virtual time step: fl-1 history entries (temporal padding before frame 0) followed
     by the newest frame of each of the N outputs.  Matches the window the reference builds at frame 0 and then
@@ -412,9 +417,7 @@ class fvvdp:
         B = len(ts)
         if C_ch != 1 and C_ch != 3:
             raise RuntimeError('The content must have either 1 or 3 colour channels.')
-        n_bands, rho_band = band_frequencies(width, height, self.pix_per_deg)
-        if n_bands < 1:
-            raise RuntimeError("Frame %dx%d is too small for this display (no band-pass level)" % (width, height))
+        n_bands, rho_band = self._band_count(width, height)
         if self.foveated and fix is None:
             fix = self._fixation(None, width, height, B)
         if self.do_heatmap and not sync:
@@ -445,8 +448,7 @@ class fvvdp:
         Q = res[:nq].view(n_bands, 2, B)
         flags = res[nq:nq + B].view(torch.int32)
         jod = res[nq + B:]
-        pp = nat.PoolParams(self.beta_sch, self.beta_tch, self.beta_t, self.w_transient, self.jod_a,
-                            float(10.0 ** self.log_jod_exp))
+        pp = self._pool_params()
         lib = nat.lib()
         for b0 in range(0, B, batch):
             nb = min(batch, B - b0)
@@ -454,24 +456,8 @@ class fvvdp:
             rp = (C.c_void_p * nb)(*[a.data_ptr() for a in rd[b0:b0 + nb]])
             nat.check(lib.fvvdp_images_channels(ctx.handle, tp, rp, nb, dtype, C_ch, height * width, C.byref(e), nat.fptr(w), 0,
                                                 C.c_void_p(flags.data_ptr() + 4 * b0), stream))
-            maps_arr, dmaps = None, None
-            if self.do_heatmap:
-                maps_arr = (nat.BandMaps * n_bands)()
-                dmaps = []
-                w_l, h_l = width, height
-                for b in range(n_bands):
-                    dmaps.append(torch.empty((nb, 2, h_l, w_l), dtype=torch.float32, device=dev))
-                    maps_arr[b].d_D = dmaps[b].data_ptr()
-                    w_l, h_l = (w_l + 1) // 2, (h_l + 1) // 2
-            fx, g = None, None
-            if self.foveated:
-                fxa = np.ascontiguousarray(fix[b0:b0 + nb], dtype=np.float32)
-                if native_geometry(self.display_geometry) is not None:
-                    g = C.byref(self._geom_struct())
-                else:
-                    self._set_view_maps(ctx, n_bands, width, height)
-                    fxa = self._gaze_view_dirs(fxa, width, height)
-                fx = nat.fptr(fxa)
+            maps_arr, dmaps = self._band_maps(nb, width, height, n_bands) if self.do_heatmap else (None, None)
+            fx, g, _keep = self._fov_args(ctx, fix, b0, nb, n_bands, width, height)
             nat.check(lib.fvvdp_images_forward_pool(ctx.handle, nb, C.c_void_p(Q.data_ptr()), B, b0, fx, g, maps_arr,
                                                     C.byref(pp), C.c_void_p(jod.data_ptr() + 4 * b0), stream))
             if self.do_heatmap:
@@ -535,22 +521,13 @@ class fvvdp:
         f0, f1 = (0, N_frames) if frame_range is None else frame_range
         if not (0 <= f0 < f1 <= N_frames):
             raise RuntimeError("frame_range out of bounds")
-        n_bands, rho_band = band_frequencies(width, height, self.pix_per_deg)
-        if n_bands < 1:
-            raise RuntimeError("Frame %dx%d is too small for this display (no band-pass level)" % (width, height))
+        n_bands, rho_band = self._band_count(width, height)
         is_image = (N_frames == 1)
         planes = 2 if is_image else 4
         if is_image:
             fl, taps = 1, np.ones((2, 1), dtype=np.float32)
         else:
-            fps = vid_source.get_frames_per_second()
-            self.filter_len = int(np.ceil(250.0 / (1000.0 / fps)))
-            fkey = (float(fps), self.filter_len, float(self.sustained_sigma), float(self.sustained_beta))
-            if fkey not in self._filters:            # taps depend on the frame rate only: evaluated once per rate
-                F, _ = self.get_temporal_filters(fps)
-                self._filters[fkey] = (F, np.ascontiguousarray(F.numpy(), dtype=np.float32))
-            self.F, taps = self._filters[fkey]
-            fl = self.filter_len
+            fl, taps = self._temporal_taps(vid_source.get_frames_per_second())
             if fl > nat.MAX_TAPS:
                 raise RuntimeError("frame rate too high: temporal filter longer than %d taps" % nat.MAX_TAPS)
         fix = self._fixation(fixation_point, width, height, N_frames) if self.foveated else None
@@ -593,8 +570,7 @@ class fvvdp:
         if schedule is None:
             schedule = [min(batch, f1 - b0) for b0 in range(f0, f1, batch)]
         # pooling + JOD regression (do_pooling_and_jods, fvvdp.py:337-357) ride on the last batch
-        pp = nat.PoolParams(self.beta_sch, self.beta_tch, self.beta_t, self.w_transient, self.jod_a,
-                            float(10.0 ** self.log_jod_exp))
+        pp = self._pool_params()
         b0 = f0
         bi = -1
         while bi + 1 < len(schedule):
@@ -612,24 +588,9 @@ class fvvdp:
                     b0 -= schedule[bi]
                 bi -= 1
                 continue
-            maps_arr, dmaps = None, None
-            if self.do_heatmap:                      # per-band difference maps as extra kernel outputs
-                maps_arr = (nat.BandMaps * n_bands)()
-                dmaps = []
-                w_l, h_l = width, height
-                for b in range(n_bands):
-                    dmaps.append(torch.empty((nb, 2, h_l, w_l), dtype=torch.float32, device=self.device))
-                    maps_arr[b].d_D = dmaps[b].data_ptr()
-                    w_l, h_l = (w_l + 1) // 2, (h_l + 1) // 2
-            fx, g = None, None
-            if self.foveated:
-                fxa = np.ascontiguousarray(fix[b0:b0 + nb], dtype=np.float32)
-                if native_geometry(self.display_geometry) is not None:
-                    g = C.byref(self._geom_struct())
-                else:                                # user geometry: maps + gaze view directions (degrees)
-                    self._set_view_maps(ctx, n_bands, width, height)
-                    fxa = self._gaze_view_dirs(fxa, width, height)
-                fx = nat.fptr(fxa)
+            # per-band difference maps as extra kernel outputs
+            maps_arr, dmaps = self._band_maps(nb, width, height, n_bands) if self.do_heatmap else (None, None)
+            fx, g, _keep = self._fov_args(ctx, fix, b0, nb, n_bands, width, height)
             if pool and b0 + nb == f1:               # the batch that completes the clip also pools (one launch fewer)
                 nat.check(nat.lib().fvvdp_bands_forward_pool(ctx.handle, nb, C.c_void_p(Q.data_ptr()), n_out, b0 - f0,
                                                              fx, g, maps_arr, C.byref(pp), C.c_void_p(res[nq + 1:].data_ptr()),
@@ -879,6 +840,71 @@ class fvvdp:
             per_frame += W * H * 8.0                   # ... and of every frame of the batch
         return max(1, min(n_out, cap, int(max(budget, per_frame) // per_frame)))
 
+    # ---- launch arguments shared by predict, predict_images and the gradient passes (image_grad.py, video_grad.py) ----------
+    def _band_count(self, width, height):
+        """(number of band-pass levels, their centre frequencies) of a frame on this display; refuses a frame with none."""
+        n_bands, rho_band = band_frequencies(width, height, self.pix_per_deg)
+        if n_bands < 1:
+            raise RuntimeError("Frame %dx%d is too small for this display (no band-pass level)" % (width, height))
+        return n_bands, rho_band
+
+    @staticmethod
+    def _level_sizes(width, height, n_bands):
+        """(w, h) of pyramid levels 0 .. n_bands: the band-pass levels and the base band's level below them."""
+        out = [(width, height)]
+        for _ in range(n_bands):
+            w, h = out[-1]
+            out.append(((w + 1) // 2, (h + 1) // 2))
+        return out
+
+    def _pool_params(self):
+        """Pooling and JOD regression constants of do_pooling_and_jods (fvvdp.py:337-357) for the pooling kernels."""
+        return nat.PoolParams(self.beta_sch, self.beta_tch, self.beta_t, self.w_transient, self.jod_a,
+                              float(10.0 ** self.log_jod_exp))
+
+    def _temporal_taps(self, fps):
+        """(filter length, taps fp32 [2, filter length]) at `fps` frames per second; sets self.filter_len and self.F as the
+        reference does.  The taps depend on the frame rate only: evaluated once per rate."""
+        self.filter_len = filter_length(fps)
+        fkey = (float(fps), self.filter_len, float(self.sustained_sigma), float(self.sustained_beta))
+        if fkey not in self._filters:
+            F, _ = self.get_temporal_filters(fps)
+            self._filters[fkey] = (F, np.ascontiguousarray(F.numpy(), dtype=np.float32))
+        self.F, taps = self._filters[fkey]
+        return self.filter_len, taps
+
+    def _band_maps(self, n, width, height, n_bands, contrast_planes=None):
+        """fvvdp_band_maps of every band for `n` frames or pairs, and the tensors behind them (the caller keeps them alive).
+        contrast_planes None: the difference maps D only (heat maps), the list holds one tensor per band.  2 (images) or 4
+        (video): all four maps (the backward passes), D, contrast, L_bkg, S per band."""
+        maps_arr = (nat.BandMaps * n_bands)()
+        keep = []
+        for b, (w, h) in enumerate(self._level_sizes(width, height, n_bands)[:n_bands]):
+            D = torch.empty((n, 2, h, w), dtype=torch.float32, device=self.device)
+            maps_arr[b].d_D = D.data_ptr()
+            keep.append(D)
+            if contrast_planes is not None:
+                Cn = torch.empty((n, contrast_planes, h, w), dtype=torch.float32, device=self.device)
+                L = torch.empty((n, h, w), dtype=torch.float32, device=self.device)
+                S = torch.empty((n, 2, h, w), dtype=torch.float32, device=self.device)
+                maps_arr[b].d_contrast, maps_arr[b].d_lbkg, maps_arr[b].d_S = Cn.data_ptr(), L.data_ptr(), S.data_ptr()
+                keep += [Cn, L, S]
+        return maps_arr, keep
+
+    def _fov_args(self, ctx, fix, b0, nb, n_bands, width, height):
+        """(fixation pointer, geometry pointer, array to keep alive until the launch) for entries [b0, b0 + nb) of the gaze
+        list `fix`; three None for a metric that is not foveated."""
+        if not self.foveated:
+            return None, None, None
+        fxa = np.ascontiguousarray(fix[b0:b0 + nb], dtype=np.float32)
+        g = None
+        if native_geometry(self.display_geometry) is not None:
+            g = C.byref(self._geom_struct())
+        else:                                # user geometry: maps + gaze view directions (degrees)
+            self._set_view_maps(ctx, n_bands, width, height)
+            fxa = self._gaze_view_dirs(fxa, width, height)
+        return nat.fptr(fxa), g, fxa
+
     def _set_view_maps(self, ctx, n_bands, width, height):
         """User geometry model: evaluate its pix2view_direction / get_resolution_magnification once per band on the
         band's pixel grid (as the reference does per frame, fvvdp.py:424-437) and hand the maps to the kernels."""
@@ -887,8 +913,7 @@ class fvvdp:
         if getattr(ctx, "view_maps", None) is not None and ctx.view_geom is geom and ctx.view_gstate == gstate:
             return
         maps = []
-        w_b, h_b = width, height
-        for b in range(n_bands):
+        for b, (w_b, h_b) in enumerate(self._level_sizes(width, height, n_bands)[:n_bands]):
             xv = torch.linspace(0.5, w_b - 0.5, w_b, device=self.device)
             yv = torch.linspace(0.5, h_b - 0.5, h_b, device=self.device)
             xx, yy = torch.meshgrid(xv, yv, indexing='xy')
@@ -902,7 +927,6 @@ class fvvdp:
             maps.append((vx, vy, rm))
             nat.check(nat.lib().fvvdp_ctx_set_view_maps(ctx.handle, b, C.c_void_p(vx.data_ptr()), C.c_void_p(vy.data_ptr()),
                                                         C.c_void_p(rm.data_ptr()), float(rm.min()), float(rm.max())))
-            w_b, h_b = (w_b + 1) // 2, (h_b + 1) // 2
         ctx.view_maps = maps          # keep the tensors alive as long as the context
         ctx.view_geom, ctx.view_gstate = geom, gstate     # strong reference: the object's id cannot be recycled
 
@@ -1038,7 +1062,7 @@ class fvvdp:
                 return feed
         if (isinstance(vs, fvvdp_video_source_yuv_frames) and native_eotf(vs.dm_photometry) is not None
                 and not (hasattr(vs, "_resizing") and vs._resizing())
-                and int(np.ceil(250.0 / (1000.0 / max(vs.get_frames_per_second(), 1e-9)))) <= 64):   # > 256 fps: generic path
+                and filter_length(max(vs.get_frames_per_second(), 1e-9)) <= 64):   # > 256 fps: generic path
             # raw planar YUV: unpacking, chroma upsampling, colour matrix and display model run in the HIP kernel
             test_d = vs.test_yuv.to(self.device).contiguous()
             ref_d = vs.reference_yuv.to(self.device).contiguous()

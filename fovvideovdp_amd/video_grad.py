@@ -1,11 +1,11 @@
 """Differentiable video JOD: fvvdp.jod_video and its autograd function (include/fvvdp_hip_video_grad.h).
 
-The forward runs the launches of fvvdp.predict for a device-resident float clip (fvvdp_temporal_channels per frame batch,
-fvvdp_bands_forward, the pooling of fvvdp_bands_forward_pool on the last batch), so the JOD is bit-identical to it.  The
-backward re-runs them per backward batch with every band's maps written, fvvdp_video_grad_frames turns the maps and the
-forward's Q_per_ch into the gradient of level 0's two test planes (a clip-long buffer), and one fvvdp_video_grad_input applies
-the transpose of the sliding-window temporal filter and the display model's derivative.  Neither pass reads context scratch
-left by the other, and neither synchronises with the host."""
+The forward makes the launches of fvvdp.predict for a device-resident float clip (fvvdp_temporal_channels per frame batch,
+fvvdp_bands_forward, the pooling of fvvdp_bands_forward_pool on the last batch) with arguments from the same methods of the
+metric, so the JOD is bit-identical to it.  The backward re-runs them per backward batch with every band's maps written,
+fvvdp_video_grad_frames turns the maps and the forward's Q_per_ch into the gradient of level 0's two test planes (a clip-long
+buffer), and one fvvdp_video_grad_input applies the transpose of the sliding-window temporal filter and the display model's
+derivative.  Neither pass reads context scratch left by the other, and neither synchronises with the host."""
 import ctypes as C
 
 import numpy as np
@@ -13,15 +13,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as nat
-from .display_model import native_eotf, native_geometry
-from .image_grad import _sizes
+from .fvvdp import filter_length, window_frame_indices      # filter_length: imported from here by tools
+from .image_grad import grad_batch_size, need_float32, place, refuse_unsupported
 from .video_source import fvvdp_video_source_array, reshuffle_dims
 
-# Device memory one backward batch may hold in maps and workspace (the pyramid scratch of the context comes on top): 52 B per
-# pyramid pixel and frame, i.e. 0.58 GB per 3840x2160 frame.  Chosen on the arithmetic alone (seven 4K frames per batch keep
-# every launch of the batch above 10^7 band pixels, the clip-long buffers of a 60-frame 4K clip -- 10 GB -- fit beside it many
-# times in 288 GB); not tuned on a measurement.
-VIDEO_GRAD_BYTES_BUDGET = 4e9
+# fp32 planes per pyramid pixel and frame: maps (D 2 + contrast 4 + L_bkg 1 + S 2) and workspace (layer + sweep gradients of
+# both channels)
+GRAD_PLANES = 9 + 4
 
 
 def fold_list(idx, fl, N):
@@ -44,35 +42,20 @@ def _fold_arrays(folds):
     return ff, fp
 
 
-def filter_length(fps):
-    """Taps of the temporal filters at `fps` frames per second (fvvdp.py:236 of the reference)."""
-    return int(np.ceil(250.0 / (1000.0 / fps)))
-
-
 class _Setup:
     """What forward and backward share for one [1, C, N, H, W] clip: pyramid size, display model, taps, window list, context."""
 
     def __init__(self, metric, t, fps):
-        from .fvvdp import band_frequencies, window_frame_indices
         _, self.C, self.N, self.H, self.W = t.shape
-        self.n_bands, self.rho_band = band_frequencies(self.W, self.H, metric.pix_per_deg)
-        if self.n_bands < 1:
-            raise RuntimeError("Frame %dx%d is too small for this display (no band-pass level)" % (self.W, self.H))
+        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
         self.dtype, self.e = metric._image_eotf(torch.float32)
         self.w = metric._rgb2y()
-        # the temporal filters exactly as _predict_on_device caches them
-        metric.filter_len = self.fl = filter_length(fps)
-        fkey = (float(fps), self.fl, float(metric.sustained_sigma), float(metric.sustained_beta))
-        if fkey not in metric._filters:
-            F, _ = metric.get_temporal_filters(fps)
-            metric._filters[fkey] = (F, np.ascontiguousarray(F.numpy(), dtype=np.float32))
-        metric.F, self.taps = metric._filters[fkey]
+        self.fl, self.taps = metric._temporal_taps(fps)
         self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
         self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
         self.ctx = metric._context(self.W, self.H, self.n_bands, 4, self.batch, self.rho_band)
         self.stream = C.c_void_p(torch.cuda.current_stream(metric.device).cuda_stream)
-        self.pp = nat.PoolParams(metric.beta_sch, metric.beta_tch, metric.beta_t, metric.w_transient, metric.jod_a,
-                                 float(10.0 ** metric.log_jod_exp))
+        self.pp = metric._pool_params()
 
     def ingest(self, lib, t, r, b0, nb, oob):
         """Level 0 of slots [0, nb) for output frames [b0, b0 + nb): the launch _make_feeder's feed makes."""
@@ -82,19 +65,6 @@ class _Setup:
                                               self.C, self.N * HW, HW, C.byref(self.e), nat.fptr(self.w),
                                               idx.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(self.taps), self.fl, nb, 0,
                                               C.c_void_p(oob.data_ptr()), self.stream))
-
-    def fov(self, metric, fix, b0, nb):
-        """(fixation pointer, geometry pointer, keep-alive) of a foveated batch, as _predict_on_device passes them."""
-        if not metric.foveated:
-            return None, None, None
-        fxa = np.ascontiguousarray(fix[b0:b0 + nb], dtype=np.float32)
-        g = None
-        if native_geometry(metric.display_geometry) is not None:
-            g = C.byref(metric._geom_struct())
-        else:
-            metric._set_view_maps(self.ctx, self.n_bands, self.W, self.H)
-            fxa = metric._gaze_view_dirs(fxa, self.W, self.H)
-        return nat.fptr(fxa), g, fxa
 
 
 def _forward(metric, t, r, fps, fix):
@@ -109,7 +79,7 @@ def _forward(metric, t, r, fps, fix):
     for b0 in range(0, N, s.batch):
         nb = min(s.batch, N - b0)
         s.ingest(lib, t, r, b0, nb, oob)
-        fx, g, _keep = s.fov(metric, fix, b0, nb)
+        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
         if b0 + nb == N:
             nat.check(lib.fvvdp_bands_forward_pool(s.ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None,
                                                    C.byref(s.pp), C.c_void_p(res[nq + 1:].data_ptr()), s.stream))
@@ -118,30 +88,16 @@ def _forward(metric, t, r, fps, fix):
     return res[nq + 1], Q
 
 
-def grad_batch_size(metric, W, H, n_bands, batch):
-    """Frames per backward batch: the context's batch, capped by VIDEO_GRAD_BYTES_BUDGET of maps + workspace
-    (metric.grad_batch overrides the cap, as for images)."""
-    gb = getattr(metric, "grad_batch", None)
-    if gb is not None:
-        return max(1, min(int(gb), batch))
-    return max(1, min(batch, int(VIDEO_GRAD_BYTES_BUDGET // _bytes_per_frame(W, H, n_bands))))
-
-
-def _bytes_per_frame(W, H, n_bands):
-    """Maps (D 2 + contrast 4 + L_bkg 1 + S 2 planes) and workspace (layer + sweep gradients of both channels) of one frame."""
-    return sum(w * h for w, h in _sizes(W, H, n_bands)) * 4 * (9 + 4)
-
-
 def _backward(metric, t, r, fps, fix, Q, gamma):
     """gamma * dJOD/dt for the contiguous device clip t [1, C, N, H, W]."""
     s = _Setup(metric, t, fps)
     N, dev, HW = s.N, metric.device, s.H * s.W
-    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch)
+    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, GRAD_PLANES)
     lib = nat.lib()
     nbytes = C.c_size_t()
     nat.check(lib.fvvdp_video_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
     # everything this pass allocates, against the free device memory: a sentence instead of an out-of-memory error
-    px = sum(w * h for w, h in _sizes(s.W, s.H, s.n_bands)[:s.n_bands])
+    px = sum(w * h for w, h in metric._level_sizes(s.W, s.H, s.n_bands)[:s.n_bands])
     need = gb * px * 4 * 9 + nbytes.value + N * HW * 8 + t.numel() * 4 + s.fl * HW * 4
     free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
     if need > free:
@@ -151,18 +107,7 @@ def _backward(metric, t, r, fps, fix, Q, gamma):
     grad = torch.empty_like(t)
     g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
     head = torch.empty((s.fl, s.H, s.W), dtype=torch.float32, device=dev)
-    sizes = _sizes(s.W, s.H, s.n_bands)
-    maps_arr = (nat.BandMaps * s.n_bands)()
-    keep = []
-    for b in range(s.n_bands):
-        w, h = sizes[b]
-        D = torch.empty((gb, 2, h, w), dtype=torch.float32, device=dev)
-        Cn = torch.empty((gb, 4, h, w), dtype=torch.float32, device=dev)
-        L = torch.empty((gb, h, w), dtype=torch.float32, device=dev)
-        S = torch.empty((gb, 2, h, w), dtype=torch.float32, device=dev)
-        keep += [D, Cn, L, S]
-        maps_arr[b].d_D, maps_arr[b].d_contrast, maps_arr[b].d_lbkg, maps_arr[b].d_S = (
-            D.data_ptr(), Cn.data_ptr(), L.data_ptr(), S.data_ptr())
+    maps_arr, _maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=4)
     work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
     q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
     oob = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -171,7 +116,7 @@ def _backward(metric, t, r, fps, fix, Q, gamma):
     for b0 in range(0, N, gb):
         nb = min(gb, N - b0)
         s.ingest(lib, t, r, b0, nb, oob)
-        fx, g, _keep = s.fov(metric, fix, b0, nb)
+        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
         nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(q_scratch.data_ptr()), nb, 0, fx, g, maps_arr, s.stream))
         nat.check(lib.fvvdp_video_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), N,
                                               b0, C.c_void_p(gamma.data_ptr()), maps_arr, C.c_void_p(g0.data_ptr()),
@@ -208,11 +153,7 @@ class JodVideoFunction(torch.autograd.Function):
 
 def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
     """fvvdp.jod_video (see there)."""
-    if isinstance(reference, torch.Tensor) and reference.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("jod_video: gradients with respect to the reference are not supported; detach the reference")
-    if native_eotf(metric.display_photometry) is None:
-        raise RuntimeError("jod_video needs a display model with a closed form for float input (sRGB, gamma, PQ, linear or "
-                           "absolute); a user photometry class has none")
+    refuse_unsupported("jod_video", metric, reference)
     if tuple(test.shape) != tuple(reference.shape):
         raise RuntimeError('Test and reference image/video tensors must be exactly the same shape')
     d = dim_order.upper()
@@ -227,8 +168,7 @@ def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, f
                            "image: use jod_images)")
     if "B" in d and t.shape[d.index("B")] != 1:
         raise RuntimeError("jod_video takes one clip per call (B must be 1)")
-    if t.dtype != torch.float32 or r.dtype != torch.float32:
-        raise RuntimeError("jod_video needs float32 test and reference clips (got %s and %s)" % (t.dtype, r.dtype))
+    need_float32("jod_video", "clips", t, r)
     if not frames_per_second > 0:
         raise RuntimeError("When passing video sequences, you must set frames_per_second parameter")
     fl = filter_length(frames_per_second)
@@ -238,10 +178,7 @@ def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, f
     t, r = reshuffle_dims(t, d, "BCFHW"), reshuffle_dims(r, d, "BCFHW")
     if t.shape[1] != 1 and t.shape[1] != 3:
         raise RuntimeError('The content must have either 1 or 3 colour channels.')
-    metric._check_device()
-    # the layout change and the move to the device stay visible to autograd: the gradient reaches the caller's own tensor
-    t = t.to(metric.device).contiguous()
-    r = r.detach().to(metric.device).contiguous()
+    t, r = place(metric, t, r)
     fix = None
     if metric.foveated:
         fix = metric._fixation(fixation_point, t.shape[4], t.shape[3], t.shape[2])

@@ -72,7 +72,7 @@ def kernel_stats(path):
 def run_case(key, a, stats):
     import fovvideovdp_amd as fv
     from fovvideovdp_amd.fvvdp import band_frequencies
-    from fovvideovdp_amd.video_grad import filter_length, grad_batch_size
+    from fovvideovdp_amd.video_grad import GRAD_PLANES, filter_length, grad_batch_size
     N, H, W = CASES[key]
     C = 3
     dev = torch.device("cuda:0")
@@ -108,7 +108,7 @@ def run_case(key, a, stats):
     n_bands = band_frequencies(W, H, m.pix_per_deg)[0]
     fl = filter_length(a.fps)
     bm = bytes_model(N, C, H, W, n_bands, fl)
-    gb = grad_batch_size(m, W, H, n_bands, m._batch_size(W, H, 4, N, fl))
+    gb = grad_batch_size(m, W, H, n_bands, m._batch_size(W, H, 4, N, fl), GRAD_PLANES)
     px = 2.0 * N * H * W
     out = {"case": key, "frames": N, "height": H, "width": W, "channels": C, "fps": a.fps, "taps": fl, "display": a.display,
            "n_bands": n_bands, "grad_batch": gb,

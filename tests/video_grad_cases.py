@@ -21,13 +21,30 @@ CASES = {
     "h_rgb_2f_120": (3, 2, 68, 121, 120, "replicate", "standard_4k", {}),            # fl = 30: nearly everything folds into frame 0
     "i_identical": (1, 4, 68, 121, 30, "replicate", "standard_4k", {"identical": (0, 4)}),
     "j_partly_identical": (3, 6, 68, 121, 30, "replicate", "standard_4k", {"identical": (0, 3)}),   # output frames 0..2 see no difference
+    # The variants of the temporal transpose (video_input_kernel<FL, PX>: ring slots, pixels per lane) the cases above do not
+    # select: an odd H*W takes the per-pixel variant, H*W % 4 == 2 the 2-pixel variant above 16 taps.  New names sort after
+    # the ones above, so every case keeps its seed.
+    "k_gray_30_odd": (1, 5, 67, 121, 30, "replicate", "standard_fhd", {}),            # fl = 8:  FL 8, PX 1
+    "l_gray_60_circular_odd": (1, 6, 67, 121, 60, "circular", "standard_4k", {}),     # fl = 15: FL 16, PX 1
+    "m_gray_120_pingpong_mod2": (1, 5, 69, 122, 120, "pingpong", "standard_4k", {}),  # fl = 30: FL 32, PX 2, H*W % 4 == 2
+    "n_gray_120_odd": (1, 4, 67, 121, 120, "replicate", "standard_fhd", {}),          # fl = 30: FL 32, PX 1
+    "o_gray_240_replicate": (1, 5, 68, 121, 240, "replicate", "standard_4k", {}),     # fl = 60: FL 64, PX 2
+    "p_gray_144_circular_odd": (1, 6, 67, 121, 144, "circular", "standard_4k", {}),   # fl = 36: FL 64, PX 1
+    "q_rgb_256": (3, 4, 68, 121, 256, "replicate", "standard_4k", {}),                # fl = 64: every slot of the longest ring
+    # more than 256 frames: the second stride of video_coef_kernel's clip sum, and many backward batches; the golden holds
+    # the gradient of the listed frames only
+    "r_gray_long": (1, 300, 18, 32, 30, "replicate", "standard_fhd", {"frames": (0, 255, 256, 299)}),
 }
 # the file each case's outputs live in (each committed file stays below 1 MiB)
 FILES = {"a_gray_30_replicate": "g19_video_grad_1.npz", "c_gray_30_circular": "g19_video_grad_1.npz",
          "f_gray_linear": "g19_video_grad_1.npz", "b_rgb_60_circular": "g19_video_grad_2.npz",
          "h_rgb_2f_120": "g19_video_grad_2.npz", "d_rgb_30_pingpong_fov": "g19_video_grad_3.npz",
          "i_identical": "g19_video_grad_3.npz", "e_rgb_pq_oob": "g19_video_grad_4.npz", "g_rgb_gamma22": "g19_video_grad_4.npz",
-         "j_partly_identical": "g19_video_grad_5.npz"}
+         "j_partly_identical": "g19_video_grad_5.npz",
+         "k_gray_30_odd": "g19_video_grad_6.npz", "l_gray_60_circular_odd": "g19_video_grad_6.npz",
+         "m_gray_120_pingpong_mod2": "g19_video_grad_6.npz", "n_gray_120_odd": "g19_video_grad_6.npz",
+         "o_gray_240_replicate": "g19_video_grad_7.npz", "p_gray_144_circular_odd": "g19_video_grad_7.npz",
+         "q_rgb_256": "g19_video_grad_8.npz", "r_gray_long": "g19_video_grad_8.npz"}
 
 
 def case_inputs(name):
@@ -54,7 +71,13 @@ def case_gaze(name):
     return synth_gaze(N, H, W).numpy() if opt.get("gaze") else None
 
 
+def golden_frames(name):
+    """The frames whose gradient the golden of a case holds (None: all of them)."""
+    frames = CASES[name][7].get("frames")
+    return None if frames is None else list(frames)
+
+
 def load_golden(name):
-    """(jod, grad [C, N, H, W]) the reference computed for one case."""
+    """(jod, grad [C, N, H, W]) the reference computed for one case (of a case with `frames`: [C, len(frames), H, W])."""
     z = np.load(os.path.join(GOLDEN, FILES[name]))
     return float(z[name + "_jod"]), z[name + "_grad"].astype(np.float32)

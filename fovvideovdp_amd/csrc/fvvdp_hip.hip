@@ -21,6 +21,7 @@
 
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_images.h"
+#include "fvvdp_hip_gaze.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // errors
@@ -52,6 +53,7 @@ int fvvdp_fail_from(int code, const char* msg) { return fail(code, "%s", msg); }
 #include "band_kernel.hpp"
 #include "band2_kernel.hpp"
 #include "aux_kernels.hpp"
+#include "multigaze_kernel.hpp"
 #include "still_kernels.hpp"
 #include "psnr_kernel.hpp"
 #include "resize_kernels.hpp"
@@ -75,6 +77,7 @@ struct CtxEnv {
     int band2_ticket = -1;        // FVVDP_BAND2_TICKET=0 / 1: two-level pyramid kernel with the static split of work / per-XCD counters
     bool temporal_scalar = false; // FVVDP_TEMPORAL_SCALAR=1: the per-pixel temporal kernels (fallbacks for unaligned sizes)
     bool debug_variant = false;   // FVVDP_DEBUG_VARIANT=1: print which kernel variants are launched (tests)
+    int gaze_group = 0;           // FVVDP_GAZE_GROUP=1 / 2 / 4 / 8: largest gaze group of one multigaze_kernel launch (tests, A/B runs)
     bool yuv_general = false;     // FVVDP_YUV_GENERAL_MATRIX=1: YUV ingest with the nine-term colour matrix also where it has the ITU shape (tests)
 };
 static CtxEnv read_env() {
@@ -96,6 +99,7 @@ static CtxEnv read_env() {
     e.temporal_scalar = getenv("FVVDP_TEMPORAL_SCALAR") != nullptr;
     e.debug_variant = getenv("FVVDP_DEBUG_VARIANT") != nullptr;
     e.yuv_general = getenv("FVVDP_YUV_GENERAL_MATRIX") != nullptr;
+    e.gaze_group = num("FVVDP_GAZE_GROUP", 0);
     return e;
 }
 
@@ -1249,6 +1253,81 @@ static int check_pool_params(const fvvdp_pool_params* prm) {
     return FVVDP_OK;
 }
 
+// Launch arguments of the one-level pass of band b (band_kernel, multigaze_kernel): the level, its work decomposition for
+// plan_n frames, the model constants and, foveated, the tables and the geometry.  Left to the caller: partial, n_items, the
+// map outputs.
+static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, bool fov, const fvvdp_geom* geom, BandArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.F = level_addr(c, b, b == 0 ? slot0 : 0);
+    a.Gc = c->level[b + 1];
+    a.w = c->lw[b];
+    a.h = c->lh[b];
+    a.wc = c->lw[b + 1];
+    a.hc = c->lh[b + 1];
+    a.n_strips = band_strips(a.wc);
+    chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, a.n_chunks, a.cr);
+    a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
+    a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
+    a.csf_y = c->csf_y;
+    a.y_first = c->y_first;
+    a.y_inv_step = c->y_inv_step;
+    a.y_lo = c->y_lo;
+    a.y_hi = c->y_hi;
+    a.ly_lo = log2f(c->y_lo);
+    a.ly_hi = log2f(c->y_hi);
+    a.lg_gain = log2f(c->prm.sens_gain);
+    a.lg_k = log2f(c->prm.mask_k);
+    a.p = c->prm.mask_p;
+    a.q0 = c->prm.mask_q[0];
+    a.q1 = c->prm.mask_q[1];
+    a.beta = c->prm.beta;
+    a.lbkg_min = c->prm.lbkg_min;
+    a.cmax = c->prm.contrast_max;
+    a.lg_dmax = log2f(c->prm.d_max);
+    if (fov) {
+        a.sublut = c->sublut[b];
+        a.axes = c->d_axes;
+        a.rw = c->sub_rw[b];
+        a.i_lo = c->sub_ilo[b];
+        a.fix = c->d_fix;
+        if (geom) {
+            a.size_m0 = geom->display_size_m[0];
+            a.size_m1 = geom->display_size_m[1];
+            a.dist_m = geom->distance_m;
+            const double delta = (1.0 / (double)geom->ppd_centre) / 2.0 * M_PI / 180.0;
+            a.delta_rad = (float)delta;
+            a.cos_delta = (float)cos(delta);
+        } else {
+            a.size_m0 = a.size_m1 = a.dist_m = 1.0f;
+            a.mvx = c->map_vx[b];
+            a.mvy = c->map_vy[b];
+            a.mrm = c->map_rm[b];
+        }
+        a.rho_band = (float)c->rho_band[b];
+        a.rho_lo = c->rho_lo;
+        a.rho_hi = c->rho_hi;
+        a.ecc_lo = c->ecc_lo;
+        a.ecc_hi = c->ecc_hi;
+        for (int ax = 0; ax < 3; ++ax) {
+            a.first[ax] = c->h_axes[ax][0];
+            a.inv_step[ax] = (float)(FVVDP_LUT_N - 1) / (c->h_axes[ax][FVVDP_LUT_N - 1] - c->h_axes[ax][0]);
+            const double step = ((double)c->h_axes[ax][FVVDP_LUT_N - 1] - (double)c->h_axes[ax][0]) / (FVVDP_LUT_N - 1);
+            a.frac_scale[ax] = (float)(step / (step + 1e-6));
+            a.grid_off[ax] = -a.first[ax] * a.inv_step[ax];
+        }
+        a.frame_w = c->W;
+        a.frame_h = c->H;
+        a.rmap = geom ? c->rmap[b] : nullptr;
+        a.rmap_w = (c->lw[b] + 1) / 2;
+    }
+    {   // LUT slice in LDS if it fits next to the row table (64 KB of dynamic LDS without opting in to more)
+        const size_t lut_b = (size_t)FOV_PLANE * c->sub_rw[b] * sizeof(float4);       // 18.6 KB per rho interval
+        // the kernel's static tables (s_csf 512 B + s_ax 768 B) share the 64 KB with the dynamic part
+        const size_t lds_static = sizeof(float4) * FVVDP_LUT_N + sizeof(float2) * 3 * FVVDP_LUT_N;
+        a.lut_lds = (fov && lut_b <= 56 * 1024 && lut_b + (size_t)c->lh[b] * sizeof(float) + lds_static <= 64 * 1024) ? 1 : 0;
+    }
+}
+
 // slot0: first level-0 frame slot of the batch (fvvdp_temporal_channels wrote slots [slot0, slot0 + n)); the levels below are
 // scratch of the pass itself and always use slots [0, n).
 // plan_n: the number of frames the work decomposition (chunk heights, and with them the grouping of the float partial sums
@@ -1393,33 +1472,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             continue;
         }
         BandArgs a;
-        memset(&a, 0, sizeof(a));
-        a.F = level_addr(c, b, b == 0 ? slot0 : 0);
-        a.Gc = c->level[b + 1];
-        a.w = c->lw[b];
-        a.h = c->lh[b];
-        a.wc = c->lw[b + 1];
-        a.hc = c->lh[b + 1];
-        a.n_strips = band_strips(a.wc);
-        chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, a.n_chunks, a.cr);
-        a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
-        a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
-        a.csf_y = c->csf_y;
-        a.y_first = c->y_first;
-        a.y_inv_step = c->y_inv_step;
-        a.y_lo = c->y_lo;
-        a.y_hi = c->y_hi;
-        a.ly_lo = log2f(c->y_lo);
-        a.ly_hi = log2f(c->y_hi);
-        a.lg_gain = log2f(c->prm.sens_gain);
-        a.lg_k = log2f(c->prm.mask_k);
-        a.p = c->prm.mask_p;
-        a.q0 = c->prm.mask_q[0];
-        a.q1 = c->prm.mask_q[1];
-        a.beta = c->prm.beta;
-        a.lbkg_min = c->prm.lbkg_min;
-        a.cmax = c->prm.contrast_max;
-        a.lg_dmax = log2f(c->prm.d_max);
+        fill_band_args(c, b, slot0, plan_n, fov, geom, a);
         a.partial = c->partial + c->partial_off[b];
         bool dbg = false;
         if (maps) {
@@ -1429,51 +1482,9 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             a.dS = maps[b].d_S;
             dbg = a.dD || a.dC || a.dL || a.dS;
         }
-        if (fov) {
-            a.sublut = c->sublut[b];
-            a.axes = c->d_axes;
-            a.rw = c->sub_rw[b];
-            a.i_lo = c->sub_ilo[b];
-            a.fix = c->d_fix;
-            if (geom) {
-                a.size_m0 = geom->display_size_m[0];
-                a.size_m1 = geom->display_size_m[1];
-                a.dist_m = geom->distance_m;
-                const double delta = (1.0 / (double)geom->ppd_centre) / 2.0 * M_PI / 180.0;
-                a.delta_rad = (float)delta;
-                a.cos_delta = (float)cos(delta);
-            } else {
-                a.size_m0 = a.size_m1 = a.dist_m = 1.0f;
-                a.mvx = c->map_vx[b];
-                a.mvy = c->map_vy[b];
-                a.mrm = c->map_rm[b];
-            }
-            a.rho_band = (float)c->rho_band[b];
-            a.rho_lo = c->rho_lo;
-            a.rho_hi = c->rho_hi;
-            a.ecc_lo = c->ecc_lo;
-            a.ecc_hi = c->ecc_hi;
-            for (int ax = 0; ax < 3; ++ax) {
-                a.first[ax] = c->h_axes[ax][0];
-                a.inv_step[ax] = (float)(FVVDP_LUT_N - 1) / (c->h_axes[ax][FVVDP_LUT_N - 1] - c->h_axes[ax][0]);
-                const double step = ((double)c->h_axes[ax][FVVDP_LUT_N - 1] - (double)c->h_axes[ax][0]) / (FVVDP_LUT_N - 1);
-                a.frac_scale[ax] = (float)(step / (step + 1e-6));
-                a.grid_off[ax] = -a.first[ax] * a.inv_step[ax];
-            }
-            a.frame_w = c->W;
-            a.frame_h = c->H;
-            a.rmap = geom ? c->rmap[b] : nullptr;
-            a.rmap_w = (c->lw[b] + 1) / 2;
-        }
         const int nblk = a.n_strips * a.n_chunks;
         if (nblk > c->max_blk[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
         a.n_items = nblk * n;
-        {   // LUT slice in LDS if it fits next to the row table (64 KB of dynamic LDS without opting in to more)
-            const size_t lut_b = (size_t)FOV_PLANE * c->sub_rw[b] * sizeof(float4);       // 18.6 KB per rho interval
-            // the kernel's static tables (s_csf 512 B + s_ax 768 B) share the 64 KB with the dynamic part
-            const size_t lds_static = sizeof(float4) * FVVDP_LUT_N + sizeof(float2) * 3 * FVVDP_LUT_N;
-            a.lut_lds = (fov && lut_b <= 56 * 1024 && lut_b + (size_t)c->lh[b] * sizeof(float) + lds_static <= 64 * 1024) ? 1 : 0;
-        }
         {
             Timed tm(c, 1 + b, st);
             if (c->P == 4) launch_band<4>(a, nblk * n, dbg, fov, st);
@@ -1515,6 +1526,155 @@ extern "C" int fvvdp_bands_forward_pool(fvvdp_ctx* c, int n, float* d_Q, int q_s
                                         float* d_jod, void* stream) {
     if (!pool) return fail(FVVDP_EINVAL, "null argument");
     return bands_forward_core(c, 0, n, d_Q, q_stride, q_col0, h_fixation, geom, maps, pool, d_jod, stream);
+}
+
+// ---- one clip under many gazes (include/fvvdp_hip_gaze.h) --------------------------------------------------------------------
+// Floats of one gaze's row of the workspace (documented in the header) and, in off[], where every band starts in it.
+static size_t gaze_row_floats(int width, int height, int n_bands, int n, size_t* off) {
+    size_t fl = 0;
+    int w = width, h = height;
+    for (int b = 0; b < n_bands; ++b) {
+        const int wc = (w + 1) / 2, hc = (h + 1) / 2;
+        if (off) off[b] = fl;
+        fl += (size_t)n * band_strips(wc) * ((hc + 1) / 2) * 2;
+        w = wc;
+        h = hc;
+    }
+    return (fl + 63) / 64 * 64;
+}
+
+extern "C" int fvvdp_gaze_workspace(int width, int height, int n_bands, int n_gazes, int n, size_t* bytes) {
+    if (!bytes) return fail(FVVDP_EINVAL, "null argument");
+    if (width < 1 || height < 1 || n_gazes < 1 || n < 1 || n_bands < 1 || n_bands > FVVDP_MAX_BANDS)
+        return fail(FVVDP_EINVAL, "bad shape: %dx%d, %d bands, %d gazes, %d frames", width, height, n_bands, n_gazes, n);
+    *bytes = (size_t)n_gazes * gaze_row_floats(width, height, n_bands, n, nullptr) * sizeof(float);
+    return FVVDP_OK;
+}
+
+template <int P>
+static void launch_multigaze(const MultiGazeArgs& m, int ng, hipStream_t st) {
+    const dim3 grid((m.b.n_items + FOV_WPB - 1) / FOV_WPB), block(64 * FOV_WPB);
+    // dynamic LDS as band_kernel<P, false, 1>: the band's LUT slice, then the vertical view angle of every band row
+    const size_t lds = (size_t)FOV_PLANE * m.b.rw * sizeof(float4) + (size_t)m.b.h * sizeof(float);
+    if (ng == 8) hipLaunchKernelGGL((multigaze_kernel<P, 8>), grid, block, lds, st, m);
+    else if (ng == 4) hipLaunchKernelGGL((multigaze_kernel<P, 4>), grid, block, lds, st, m);
+    else if (ng == 2) hipLaunchKernelGGL((multigaze_kernel<P, 2>), grid, block, lds, st, m);
+    else hipLaunchKernelGGL((multigaze_kernel<P, 1>), grid, block, lds, st, m);
+}
+
+static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const float* d_gaze, size_t gaze_stride, float* d_Q,
+                                    int q_stride, int q_col0, const fvvdp_geom* geom, void* d_work, size_t work_bytes,
+                                    const fvvdp_pool_params* pool, float* d_jod, void* stream) {
+    if (!c || !d_gaze || !d_Q || !geom || !d_work) return fail(FVVDP_EINVAL, "null argument");
+    if (pool) {
+        if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
+        int rc = check_pool_params(pool);
+        if (rc != FVVDP_OK) return rc;
+    }
+    if (n_gazes < 1) return fail(FVVDP_EINVAL, "n_gazes must be >= 1, got %d", n_gazes);
+    if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
+    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    if (gaze_stride < (size_t)2 * n) return fail(FVVDP_EINVAL, "gaze_stride %zu is less than 2 n = %d floats", gaze_stride, 2 * n);
+    if (!(c->lut3_set[0] && (c->P == 2 || c->lut3_set[1])))
+        return fail(FVVDP_EINVAL, "the context is not foveated (fvvdp_ctx_set_csf_3d not called)");
+    if (c->maps_set) return fail(FVVDP_EINVAL, "view maps of a user geometry are set: the gaze pass covers the stock geometry only");
+    if (((uintptr_t)d_work & 255) != 0) return fail(FVVDP_EINVAL, "the workspace must be 256-byte aligned");
+    size_t off[FVVDP_MAX_BANDS];
+    const size_t row = gaze_row_floats(c->W, c->H, c->n_bands, n, off);
+    if (work_bytes < (size_t)n_gazes * row * sizeof(float))
+        return fail(FVVDP_EINVAL, "workspace of %zu bytes is too small: %d gazes x %d frames need %zu", work_bytes, n_gazes, n,
+                    (size_t)n_gazes * row * sizeof(float));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    {
+        int rc = build_sublut(c, geom, st);
+        if (rc != FVVDP_OK) return rc;
+    }
+    float* work = reinterpret_cast<float*>(d_work);
+    const int group_max = c->env.gaze_group >= 1 ? c->env.gaze_group : FVVDP_GAZE_GROUP_MAX;
+    GazeFinalizeArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    MultiGazeArgs m[FVVDP_MAX_BANDS];
+    // every refusal before the first pyramid launch (build_sublut above comes first, since the slices' sizes are its result: on a
+    // new geometry it synchronises, allocates, uploads the slices and launches fov_rho_map_kernel)
+    for (int b = 0; b < c->n_bands; ++b) {
+        fill_band_args(c, b, 0, n, true, geom, m[b].b);
+        const int nblk = m[b].b.n_strips * m[b].b.n_chunks;
+        if ((size_t)n * nblk * 2 > (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+        m[b].b.fix = nullptr;
+        m[b].b.n_items = nblk * n;
+        m[b].gaze_stride = (long long)gaze_stride;
+        m[b].partial_stride = (long long)row;
+        fa.f.nblk[b] = nblk;
+        fa.f.off[b] = (long long)off[b];
+        fa.f.npx[b] = (float)m[b].b.w * (float)m[b].b.h;
+    }
+    for (int b = 0; b < c->n_bands; ++b) {
+        Timed tm(c, 1 + b, st);
+        if (!m[b].b.lut_lds) {
+            // The band's slice of the CSF table does not fit the LDS (wide fields of view: standard_hmd needs 8-9 rho intervals
+            // per band; band 0 of a 2160-row frame with 3): multigaze_kernel has no variant for it.  The band takes the kernel a
+            // single-gaze call takes, once per gaze, on that gaze's row of the gaze array and of the workspace -- the same bits by
+            // construction, nothing shared but K1 (every launch rewrites the next level with the same values).
+            BandArgs a = m[b].b;
+            for (int g = 0; g < n_gazes; ++g) {
+                a.fix = d_gaze + (size_t)g * gaze_stride;
+                a.partial = work + (size_t)g * row + off[b];
+                if (c->P == 4) launch_band<4>(a, a.n_items, false, true, st);
+                else launch_band<2>(a, a.n_items, false, true, st);
+            }
+            continue;
+        }
+        for (int g0 = 0; g0 < n_gazes;) {
+            const int left = n_gazes - g0;
+            int ng = FVVDP_GAZE_GROUP_MAX;           // the largest instantiation that the gazes left fill: 8, 4, 2, 1
+            while (ng > left || ng > group_max) ng >>= 1;
+            m[b].gaze = d_gaze + (size_t)g0 * gaze_stride;
+            m[b].partial = work + (size_t)g0 * row + off[b];
+            m[b].store_coarse = g0 == 0 ? 1 : 0;     // the later groups of a level read the same rows and leave the next level alone
+            if (c->P == 4) launch_multigaze<4>(m[b], ng, st);
+            else launch_multigaze<2>(m[b], ng, st);
+            g0 += ng;
+        }
+    }
+    const long long q_stride_g = (long long)c->n_bands * 2 * q_stride;
+    fa.f.partial = work;
+    fa.f.Q = d_Q;
+    fa.f.n_bands = c->n_bands;
+    fa.f.n = n;
+    fa.f.q_stride = q_stride;
+    fa.f.q_col0 = q_col0;
+    fa.f.tc = c->P / 2;
+    fa.f.inv_beta = 1.0f / c->prm.beta;
+    fa.partial_stride = (long long)row;
+    fa.q_stride_g = q_stride_g;
+    {
+        Timed tm(c, 1 + c->n_bands, st);
+        hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_gazes), dim3(64), 0, st, fa);
+    }
+    if (pool && q_col0 + n == q_stride) {
+        for (int g = 0; g < n_gazes; ++g) {          // the single-gaze pooling kernel, once per gaze
+            PoolArgs pa;
+            fill_pool_args(pa, d_Q + (size_t)g * q_stride_g, c->n_bands, 2, q_stride, q_stride, pool, d_jod + g);
+            hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_bands_forward_gazes(fvvdp_ctx* c, int n, int n_gazes, const float* d_gaze, size_t gaze_stride, float* d_Q,
+                                         int q_stride, int q_col0, const fvvdp_geom* geom, void* d_work, size_t work_bytes,
+                                         void* stream) {
+    return bands_forward_gazes_core(c, n, n_gazes, d_gaze, gaze_stride, d_Q, q_stride, q_col0, geom, d_work, work_bytes, nullptr,
+                                    nullptr, stream);
+}
+
+extern "C" int fvvdp_bands_forward_gazes_pool(fvvdp_ctx* c, int n, int n_gazes, const float* d_gaze, size_t gaze_stride,
+                                              float* d_Q, int q_stride, int q_col0, const fvvdp_geom* geom, void* d_work,
+                                              size_t work_bytes, const fvvdp_pool_params* pool, float* d_jod, void* stream) {
+    if (!pool) return fail(FVVDP_EINVAL, "null argument");
+    return bands_forward_gazes_core(c, n, n_gazes, d_gaze, gaze_stride, d_Q, q_stride, q_col0, geom, d_work, work_bytes, pool, d_jod,
+                                    stream);
 }
 
 // ---- placement of level 0, at context creation ------------------------------------------------------------------------------

@@ -331,6 +331,21 @@ class fvvdp:
         from .video_grad import jod_video
         return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point)
 
+    def predict_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
+        """Extension: one (test, reference) clip or image scored under G gaze traces in one pass (foveated metric, stock
+        display geometry).  `fixation_points`: [G, 2] (one fixed gaze per row) or [G, N_frames, 2] (one trace per gaze), in
+        frame pixels as predict's `fixation_point`.  Returns (Q_JOD, stats): Q_JOD a [G] fp32 device tensor,
+        stats['Q_per_ch'] [G, bands, 2, frames] (numpy), the other keys as predict makes them.  Row g is bit-identical to
+        predict(test, reference, dim_order, frames_per_second, fixation_point=fixation_points[g]) on this metric, whatever
+        the other gazes are: the temporal channels are made once per batch of frames and the pyramid pass evaluates what
+        does not depend on the gaze once per group of up to 8 gazes (include/fvvdp_hip_gaze.h).  Every source predict
+        accepts (uint8 / uint16 / float32, C = 1 or 3, a single frame, batch_frames shorter than the clip).  Refused: a metric
+        that is not foveated or makes heat maps, a user display_geometry class, inputs that require grad.  A band whose slice
+        of the CSF table does not fit the LDS (every band of standard_hmd or htc_vive_pro, band 0 of a 2160-row frame on
+        sdr_4k_30) runs the single-gaze kernel once per gaze: same results, only the temporal channels are shared."""
+        from .gazes import predict_gazes
+        return predict_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
+
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
         or with them of size 1).  The pairs are grouped by (shape, dtypes) and every group is scored in batches by
@@ -516,7 +531,12 @@ class fvvdp:
                 logging.warning("Pixel outside the valid range 0-1")
         return stats
 
-    def _predict_on_device(self, vid_source, fixation_point, frame_range, pool, sync=True):
+    def _clip_plan(self, vid_source, frame_range=None):
+        """How a call walks a clip -- shared by predict and predict_gazes, whose results are bit-identical only on the same plan:
+        frame size and range [f0, f1), bands, planes, temporal filter and window index list, the feeder that fills level 0 (host
+        sources upload only the frames the range needs; resets self.last_h2d_bytes), the frames per batch (= the context's
+        size) and the batch schedule, whose chunk heights group the partial sums."""
+        from types import SimpleNamespace
         height, width, N_frames = vid_source.get_video_size()
         f0, f1 = (0, N_frames) if frame_range is None else frame_range
         if not (0 <= f0 < f1 <= N_frames):
@@ -530,8 +550,6 @@ class fvvdp:
             fl, taps = self._temporal_taps(vid_source.get_frames_per_second())
             if fl > nat.MAX_TAPS:
                 raise RuntimeError("frame rate too high: temporal filter longer than %d taps" % nat.MAX_TAPS)
-        fix = self._fixation(fixation_point, width, height, N_frames) if self.foveated else None
-
         n_out = f1 - f0
         wkey = (N_frames, fl, self.temp_padding, f0, f1, is_image)
         wc = self._filters.get(wkey)
@@ -552,9 +570,22 @@ class fvvdp:
             batch = max(1, min(batch, feeder.preferred_batch))
             if not self.do_heatmap:
                 schedule = feeder.batch_schedule(n_out, batch)
-        heatmap = None
         if self.do_heatmap:
             batch = max(1, min(batch, int(2e9 // (width * height * 4 * 12))))     # D maps + context image per frame
+        if schedule is None:
+            schedule = [min(batch, f1 - b0) for b0 in range(f0, f1, batch)]
+        return SimpleNamespace(height=height, width=width, N_frames=N_frames, f0=f0, f1=f1, n_bands=n_bands, rho_band=rho_band,
+                               planes=planes, fl=fl, taps=taps, widx=widx, feeder=feeder, batch=batch, schedule=schedule)
+
+    def _predict_on_device(self, vid_source, fixation_point, frame_range, pool, sync=True):
+        height, width, N_frames = vid_source.get_video_size()
+        fix = self._fixation(fixation_point, width, height, N_frames) if self.foveated else None
+        pl = self._clip_plan(vid_source, frame_range)
+        f0, f1, n_bands, rho_band, planes, fl, taps, widx = pl.f0, pl.f1, pl.n_bands, pl.rho_band, pl.planes, pl.fl, pl.taps, pl.widx
+        feeder, batch, schedule = pl.feeder, pl.batch, pl.schedule
+        n_out = f1 - f0
+        heatmap = None
+        if self.do_heatmap:
             dmap_channels = 1 if self.heatmap == "raw" else 3
             # fp16 on the host like the reference (fvvdp.py:216-221); every element is written below, and page-locked
             # memory lets the batches stream back at link speed while the next batch is computed
@@ -567,8 +598,6 @@ class fvvdp:
         Q = res[:nq].view(n_bands, 2, n_out)
         oob = res[nq:nq + 1].view(torch.int32)
 
-        if schedule is None:
-            schedule = [min(batch, f1 - b0) for b0 in range(f0, f1, batch)]
         # pooling + JOD regression (do_pooling_and_jods, fvvdp.py:337-357) ride on the last batch
         pp = self._pool_params()
         b0 = f0

@@ -69,6 +69,13 @@ static void grad_layout(int width, int height, int n_bands, int n, int planes, G
     L.total = off;
 }
 
+// video_coef_kernel for the n frames [f0, f0 + n) of a clip of n_frames (coefficients [n][2][n_bands] into d_coef) and
+// video_level0_kernel on the batch's 2n planes (level 0 of the workspace `ws` into d_g0_batch).  The kernels are defined in
+// video_grad_launch.hip only, so are these functions
+hipError_t video_coef_launch(const float* d_Q, const float* d_gamma, float* d_coef, int n, int n_bands, int n_frames, int f0,
+                             const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st);
+hipError_t video_level0_launch(const float* ws, const GradLayout& L, float* d_g0_batch, int n, hipStream_t st);
+
 // `unit`: what n counts in the message ("pairs", "frames"); max_n, max_height: what the caller's launch grids reach
 static int grad_check_dims(int width, int height, int n_bands, int n, int max_n, int max_height, const char* unit) {
     if (width < 1 || height < 1 || n < 1 || n > max_n || n_bands < 1 || n_bands > FVVDP_MAX_BANDS || height > max_height)

@@ -23,6 +23,42 @@ static int check_dims(int width, int height, int n_bands, int n) {
     return grad_check_dims(width, height, n_bands, n, 16384, 65535, "frames");
 }
 
+hipError_t video_coef_launch(const float* d_Q, const float* d_gamma, float* d_coef, int n, int n_bands, int n_frames, int f0,
+                             const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st) {
+    VideoCoefArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.Q = d_Q;
+    ca.gamma = d_gamma;
+    ca.coef = d_coef;
+    ca.n = n;
+    ca.n_bands = n_bands;
+    ca.N = n_frames;
+    ca.f0 = f0;
+    ca.beta = prm->beta;
+    ca.beta_sch = pool->beta_sch;
+    ca.beta_tch = pool->beta_tch;
+    ca.beta_t = pool->beta_t;
+    ca.w_transient = pool->w_transient;
+    ca.jod_a = pool->jod_a;
+    ca.beta_jod = pool->beta_jod;
+    for (int b = 0; b < n_bands; ++b) ca.inv_npx[b] = (float)(1.0 / ((double)L.w[b] * L.h[b]));
+    hipLaunchKernelGGL(video_coef_kernel, dim3(1), dim3(256), 0, st, ca);
+    return hipGetLastError();
+}
+
+hipError_t video_level0_launch(const float* ws, const GradLayout& L, float* d_g0_batch, int n, hipStream_t st) {
+    VideoLevel0Args za;
+    za.GL0 = ws + L.gl[0];
+    za.GG1 = ws + L.gg[1];
+    za.g0 = d_g0_batch;
+    za.w = L.w[0];
+    za.h = L.h[0];
+    za.wc = L.w[1];
+    za.hc = L.h[1];
+    hipLaunchKernelGGL(video_level0_kernel, dim3((L.w[0] + 255) / 256, L.h[0], 2 * n), dim3(256), 0, st, za);
+    return hipGetLastError();
+}
+
 extern "C" int fvvdp_video_grad_workspace(int width, int height, int n_bands, int n, size_t* bytes) {
     if (!bytes) return grad_fail(FVVDP_EINVAL, "null argument");
     GRAD_CHECK(check_dims(width, height, n_bands, n));
@@ -51,25 +87,7 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
     const size_t HW = (size_t)width * height;
 
     // 1. coefficients of the batch's frames (the clip-level factor needs every column of Q)
-    VideoCoefArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.Q = d_Q;
-    ca.gamma = d_gamma;
-    ca.coef = ws + L.coef;
-    ca.n = n;
-    ca.n_bands = n_bands;
-    ca.N = n_frames;
-    ca.f0 = f0;
-    ca.beta = prm->beta;
-    ca.beta_sch = pool->beta_sch;
-    ca.beta_tch = pool->beta_tch;
-    ca.beta_t = pool->beta_t;
-    ca.w_transient = pool->w_transient;
-    ca.jod_a = pool->jod_a;
-    ca.beta_jod = pool->beta_jod;
-    for (int b = 0; b < n_bands; ++b) ca.inv_npx[b] = (float)(1.0 / ((double)L.w[b] * L.h[b]));
-    hipLaunchKernelGGL(video_coef_kernel, dim3(1), dim3(256), 0, st, ca);
-    GRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(video_coef_launch(d_Q, d_gamma, ws + L.coef, n, n_bands, n_frames, f0, prm, pool, L, st));
 
     // 2. layer gradients of every band, both temporal channels
     VideoLayerArgs la;
@@ -84,16 +102,7 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
     GRAD_HIP_TRY(grad_sweep_levels(ws, L, n_bands, 2 * n, st));
 
     // 4. level 0 into the clip-long buffer
-    VideoLevel0Args za;
-    za.GL0 = ws + L.gl[0];
-    za.GG1 = ws + L.gg[1];
-    za.g0 = d_g0 + (size_t)f0 * 2 * HW;
-    za.w = width;
-    za.h = height;
-    za.wc = L.w[1];
-    za.hc = L.h[1];
-    hipLaunchKernelGGL(video_level0_kernel, dim3((width + 255) / 256, height, 2 * n), dim3(256), 0, st, za);
-    GRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(video_level0_launch(ws, L, d_g0 + (size_t)f0 * 2 * HW, n, st));
     return FVVDP_OK;
 }
 

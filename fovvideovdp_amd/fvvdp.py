@@ -346,6 +346,23 @@ class fvvdp:
         from .gazes import predict_gazes
         return predict_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
 
+    def jod_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
+        """Extension: the JODs of one clip under G gaze traces as a differentiable [G] fp32 tensor on the metric's device, for
+        losses over a gaze distribution such as `(10 - metric.jod_gazes(x, ref, grid, frames_per_second=30)).mean()` or the
+        worst case over a fixation grid.  `fixation_points` as predict_gazes takes them: [G, 2] or [G, N_frames, 2] in frame
+        pixels.  Row g is bit-identical to predict_gazes(test.detach(), reference, fixation_points, ...)[0][g], and so to
+        predict(..., fixation_point=fixation_points[g]).  backward() puts sum_g grad[g] dJOD_g/dtest into `test`, whatever its
+        layout or device; the reference and the gazes are constants.  The backward shares among the gazes whatever does not
+        depend on the gaze -- the ingest, the map-writing pyramid pass, the coarse-to-fine sweep, level 0 and the temporal
+        transpose run once per backward batch or clip, only the pooling coefficients and the pointwise layer gradient once
+        per gaze (include/fvvdp_hip_gaze_grad.h) -- and its memory does not grow with G.  Accepted: what jod_video accepts
+        (float32 samples, C = 1 or 3, one clip of at least 2 frames, closed-form display models, every temporal padding,
+        filters of up to 64 taps).  Refused: what predict_gazes refuses (a metric that is not foveated or makes heat maps,
+        a user display_geometry class).  Nothing is synchronised with the host: no out-of-range warning.  Double backward
+        is not supported.  The gradient does not depend on `self.grad_batch` nor on the grouping of the gazes, bit for bit."""
+        from .gaze_grad import jod_gazes
+        return jod_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
+
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
         or with them of size 1).  The pairs are grouped by (shape, dtypes) and every group is scored in batches by

@@ -88,45 +88,66 @@ def _forward(metric, t, r, fps, fix):
     return res[nq + 1], Q
 
 
+class _Buffers:
+    """What a backward pass over the clip t allocates, shared by jod_video and jod_gazes (`name`): the result, the clip-long
+    level-0 gradient, the head's side buffer, the maps and scratch of a backward batch of gb frames and a workspace of
+    `work_bytes`.  Checked against the free device memory first: a sentence instead of an out-of-memory error."""
+
+    def __init__(self, name, metric, s, t, gb, work_bytes):
+        N, dev, HW = s.N, metric.device, s.H * s.W
+        px = sum(w * h for w, h in metric._level_sizes(s.W, s.H, s.n_bands)[:s.n_bands])
+        need = gb * px * 4 * 9 + work_bytes + N * HW * 8 + t.numel() * 4 + s.fl * HW * 4
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise RuntimeError("%s: the backward of this clip needs %.1f GB of device memory (maps and workspace of %d "
+                               "frames, the clip-long level-0 gradient and the result) and %.1f GB are free; set a smaller "
+                               "metric.grad_batch or a shorter clip" % (name, need / 1e9, gb, free / 1e9))
+        self.grad = torch.empty_like(t)
+        self.g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
+        self.head = torch.empty((s.fl, s.H, s.W), dtype=torch.float32, device=dev)
+        self.maps_arr, self._maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=4)
+        self.work = torch.empty((work_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        self.work_bytes = work_bytes
+        self.q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
+        self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def maps_pass(self, lib, metric, s, t, r, fix, b0, nb):
+        """Ingest of frames [b0, b0 + nb) and the pyramid pass that writes every band's maps, under the gaze trace `fix`."""
+        s.ingest(lib, t, r, b0, nb, self.oob)
+        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
+        nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(self.q_scratch.data_ptr()), nb, 0, fx, g, self.maps_arr,
+                                          s.stream))
+
+    def input_grad(self, lib, s, t):
+        """The clip-long level-0 gradient -> the gradient of the clip: temporal transpose and the display model's derivative."""
+        N, HW = s.N, s.H * s.W
+        ff, fp = _fold_arrays(fold_list(s.widx, s.fl, N))
+        nat.check(lib.fvvdp_video_grad_input(s.W, s.H, N, C.c_void_p(self.g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
+                                             C.c_void_p(t.data_ptr()), C.c_void_p(self.grad.data_ptr()), s.C, N * HW, HW,
+                                             C.byref(s.e), nat.fptr(s.w), C.c_void_p(self.head.data_ptr()), self.head.numel() * 4,
+                                             s.stream))
+        return self.grad
+
+
 def _backward(metric, t, r, fps, fix, Q, gamma):
     """gamma * dJOD/dt for the contiguous device clip t [1, C, N, H, W]."""
     s = _Setup(metric, t, fps)
-    N, dev, HW = s.N, metric.device, s.H * s.W
+    N, dev = s.N, metric.device
     gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, GRAD_PLANES)
     lib = nat.lib()
     nbytes = C.c_size_t()
     nat.check(lib.fvvdp_video_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
-    # everything this pass allocates, against the free device memory: a sentence instead of an out-of-memory error
-    px = sum(w * h for w, h in metric._level_sizes(s.W, s.H, s.n_bands)[:s.n_bands])
-    need = gb * px * 4 * 9 + nbytes.value + N * HW * 8 + t.numel() * 4 + s.fl * HW * 4
-    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-    if need > free:
-        raise RuntimeError("jod_video: the backward of this clip needs %.1f GB of device memory (maps and workspace of %d "
-                           "frames, the clip-long level-0 gradient and the result) and %.1f GB are free; set a smaller "
-                           "metric.grad_batch or a shorter clip" % (need / 1e9, gb, free / 1e9))
-    grad = torch.empty_like(t)
-    g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
-    head = torch.empty((s.fl, s.H, s.W), dtype=torch.float32, device=dev)
-    maps_arr, _maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=4)
-    work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
-    q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
-    oob = torch.zeros(1, dtype=torch.int32, device=dev)
+    buf = _Buffers("jod_video", metric, s, t, gb, nbytes.value)
     prm = metric.native_params()
     gamma = gamma.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
     for b0 in range(0, N, gb):
         nb = min(gb, N - b0)
-        s.ingest(lib, t, r, b0, nb, oob)
-        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(q_scratch.data_ptr()), nb, 0, fx, g, maps_arr, s.stream))
+        buf.maps_pass(lib, metric, s, t, r, fix, b0, nb)
         nat.check(lib.fvvdp_video_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), N,
-                                              b0, C.c_void_p(gamma.data_ptr()), maps_arr, C.c_void_p(g0.data_ptr()),
-                                              C.c_void_p(work.data_ptr()), nbytes.value, s.stream))
-    ff, fp = _fold_arrays(fold_list(s.widx, s.fl, N))
-    nat.check(lib.fvvdp_video_grad_input(s.W, s.H, N, C.c_void_p(g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
-                                         C.c_void_p(t.data_ptr()), C.c_void_p(grad.data_ptr()), s.C, N * HW, HW, C.byref(s.e),
-                                         nat.fptr(s.w), C.c_void_p(head.data_ptr()), head.numel() * 4, s.stream))
-    return grad
+                                              b0, C.c_void_p(gamma.data_ptr()), buf.maps_arr, C.c_void_p(buf.g0.data_ptr()),
+                                              C.c_void_p(buf.work.data_ptr()), buf.work_bytes, s.stream))
+    return buf.input_grad(lib, s, t)
 
 
 class JodVideoFunction(torch.autograd.Function):
@@ -151,9 +172,11 @@ class JodVideoFunction(torch.autograd.Function):
         return grad, None, None, None, None
 
 
-def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
-    """fvvdp.jod_video (see there)."""
-    refuse_unsupported("jod_video", metric, reference)
+def clip_arguments(name, metric, test, reference, dim_order, frames_per_second):
+    """What jod_video and jod_gazes (`name`) accept: one float32 clip pair of at least 2 frames, C = 1 or 3, a closed-form display
+    model, a temporal filter of at most VIDEO_GRAD_MAX_TAPS taps.  Returns test and reference as [1, C, N, H, W] tensors, not yet
+    placed on the device."""
+    refuse_unsupported(name, metric, reference)
     if tuple(test.shape) != tuple(reference.shape):
         raise RuntimeError('Test and reference image/video tensors must be exactly the same shape')
     d = dim_order.upper()
@@ -164,20 +187,26 @@ def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, f
     t = fvvdp_video_source_array._as_tensor(test)
     r = fvvdp_video_source_array._as_tensor(reference)
     if "F" not in d or t.shape[d.index("F")] < 2:
-        raise RuntimeError("jod_video needs a clip: an F axis of at least 2 frames in dim_order (a single frame is a still "
-                           "image: use jod_images)")
+        raise RuntimeError("%s needs a clip: an F axis of at least 2 frames in dim_order (a single frame is a still "
+                           "image: use jod_images)" % name)
     if "B" in d and t.shape[d.index("B")] != 1:
-        raise RuntimeError("jod_video takes one clip per call (B must be 1)")
-    need_float32("jod_video", "clips", t, r)
+        raise RuntimeError("%s takes one clip per call (B must be 1)" % name)
+    need_float32(name, "clips", t, r)
     if not frames_per_second > 0:
         raise RuntimeError("When passing video sequences, you must set frames_per_second parameter")
     fl = filter_length(frames_per_second)
     if fl > nat.VIDEO_GRAD_MAX_TAPS:
-        raise RuntimeError("jod_video: frame rate too high for the backward: its temporal filter has %d taps, the transpose "
-                           "kernel covers %d (256 frames per second)" % (fl, nat.VIDEO_GRAD_MAX_TAPS))
+        raise RuntimeError("%s: frame rate too high for the backward: its temporal filter has %d taps, the transpose "
+                           "kernel covers %d (256 frames per second)" % (name, fl, nat.VIDEO_GRAD_MAX_TAPS))
     t, r = reshuffle_dims(t, d, "BCFHW"), reshuffle_dims(r, d, "BCFHW")
     if t.shape[1] != 1 and t.shape[1] != 3:
         raise RuntimeError('The content must have either 1 or 3 colour channels.')
+    return t, r
+
+
+def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+    """fvvdp.jod_video (see there)."""
+    t, r = clip_arguments("jod_video", metric, test, reference, dim_order, frames_per_second)
     t, r = place(metric, t, r)
     fix = None
     if metric.foveated:

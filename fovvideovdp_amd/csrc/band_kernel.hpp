@@ -159,6 +159,13 @@ struct BandArgs {
     int frame_w, frame_h;
 };
 
+// Argument block of the map-writing variants (DBG): one more optional plane after the block every variant reads, so the
+// pooling variants' arguments -- and their code -- stay as they are.
+struct BandMapArgs : BandArgs {
+    float* dK;              // [n][2][h][w] plane cc: d log2 S_cc / d log2 L_bkg, the slope of the CSF interpolation along its Y axis
+                            //   (0 where the Y clamp binds or interp.py:17 zeroes the fraction); nullptr: not written
+};
+
 
 // Foveated mode, frame-invariant part of the CSF query: the spatial frequency of a pixel is rho_band times the
 // resolution magnification at its view angle (fvvdp.py:424-442, fvvdp_display_model.py:475-526) -- a function of the
@@ -400,6 +407,9 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         const float llb = fast_log2(lb);
         const float yq = __builtin_amdgcn_fmed3f(llb, a.ly_lo, a.ly_hi);          // = log2(clamp(lb, Y[0], Y[-1]))  (fvvdp.py:530)
         float slog[2] = {0.0f, 0.0f};
+        [[maybe_unused]] float kap[2] = {0.0f, 0.0f};      // DBG: slope of slog along log2(lb), per unit of the Y axis
+        [[maybe_unused]] float* dK = nullptr;
+        if constexpr (DBG) dK = static_cast<const BandMapArgs&>(a).dK;
         if constexpr (!FOV) {
             // 1-D table over log2(L_bkg) (uniform knots): interval from the grid, value = v[i] + f*(v[i+1]-v[i])
             const float t = fmaf(yq, a.y_inv_step, y_off);               // (yq - y_first) * y_inv_step
@@ -408,6 +418,13 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
             const float f = t - fi;
             slog[0] = fmaf(f, r.z, r.x);
             slog[1] = fmaf(f, r.w, r.y);
+            if constexpr (DBG) {
+                if (dK) {                                              // (v[i+1] - v[i]) / (knot step + 1e-6): interp.py:16
+                    const float ks = a.y_inv_step / fmaf(0.000001f, a.y_inv_step, 1.0f);
+                    kap[0] = r.z * ks;
+                    kap[1] = r.w * ks;
+                }
+            }
         } else {
             // eccentricity and resolution magnification (fvvdp.py:424-437, fvvdp_display_model.py:475-526).
             // (tan(a+d)-tan(a))/tan(d) == cos(d)/(cos(a)cos(a+d)): evaluated in this form it needs no slow tan and
@@ -453,6 +470,15 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
                       (fmaf(v01.z, fR, v01.x) * gY + fmaf(v11.z, fR, v11.x) * fY) * fE;
             slog[1] = (fmaf(v00.w, fR, v00.y) * gY + fmaf(v10.w, fR, v10.y) * fY) * gE +
                       (fmaf(v01.w, fR, v01.y) * gY + fmaf(v11.w, fR, v11.y) * fY) * fE;
+            if constexpr (DBG) {
+                if (dK) {                                              // d slog / d fY, times d fY / d yq = 1 / (knot step + 1e-6)
+                    const float ky = s_ax[kY].y;
+                    kap[0] = ((fmaf(v10.z, fR, v10.x) - fmaf(v00.z, fR, v00.x)) * gE +
+                              (fmaf(v11.z, fR, v11.x) - fmaf(v01.z, fR, v01.x)) * fE) * ky;
+                    kap[1] = ((fmaf(v10.w, fR, v10.y) - fmaf(v00.w, fR, v00.y)) * gE +
+                              (fmaf(v11.w, fR, v11.y) - fmaf(v01.w, fR, v01.y)) * fE) * ky;
+                }
+            }
         }
         const float vm = valid ? 1.0f : 0.0f;
         const float lcn = lg_bm - llb;                                   // log2(m / lb)
@@ -493,6 +519,10 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
                     const size_t o = (((size_t)frame * 2 + cc) * h + y) * w + x;
                     if (a.dD) a.dD[o] = fast_exp2(ldd_dbg[cc]);
                     if (a.dS) a.dS[o] = fast_exp2(slog[cc]);
+                    // no slope where torch.clamp passes no gradient (L_bkg outside the table's Y range) or get_interpolants_v1
+                    // overwrites the fraction (the query on the first knot).  On an interior knot exactly the reference takes the
+                    // slope of the cell below (bucketize: x[i-1] < q <= x[i]), this kernel the cell above: a set of measure zero
+                    if (dK) dK[o] = (llb > a.ly_lo && llb <= a.ly_hi) ? kap[cc] : 0.0f;
                 }
             }
         }
@@ -767,7 +797,7 @@ __device__ __forceinline__ void band_load_tables(const BandArgs& a, float4* s_cs
 // memory (slice too large, or the map-writing variant).  A compile-time choice: with a run-time flag the compiler
 // merges the two look-ups into one flat load, which is slower than ds_read_b128.
 template <int P, bool DBG, int FOVM>
-__global__ __launch_bounds__(FOVM ? 64 * FOV_WPB : 64, FOVM ? (FOVM == 1 ? FOV_MINW_LEAN : FOV_MINW) : (DBG ? 2 : 4)) void band_kernel(const BandArgs a_byval) {
+__global__ __launch_bounds__(FOVM ? 64 * FOV_WPB : 64, FOVM ? (FOVM == 1 ? FOV_MINW_LEAN : FOV_MINW) : (DBG ? 2 : 4)) void band_kernel(const std::conditional_t<DBG, BandMapArgs, BandArgs> a_byval) {
     // the argument block is read from the kernel-argument segment where it is needed (scalar loads) instead of being held in
     // scalar registers from the top of the kernel: the variants with many arguments in use (difference maps, caller-built view
     // maps) otherwise keep 13-48 of them in vector-register lanes

@@ -17,11 +17,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_images.h"
 #include "fvvdp_hip_gaze.h"
+#include "fvvdp_hip_ref_grad.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // errors
@@ -157,6 +159,7 @@ struct fvvdp_ctx {
     const float* map_rm[FVVDP_MAX_BANDS]{};
     float map_rm_max[FVVDP_MAX_BANDS]{}, map_rm_min[FVVDP_MAX_BANDS]{};
     bool maps_set = false;
+    float* slope[FVVDP_MAX_BANDS]{};           // fvvdp_ctx_set_slope_maps: one more plane of the map-writing pass (owned by the caller)
     bool sub_valid = false;
     float rho_lo = 0, rho_hi = 0, ecc_lo = 0, ecc_hi = 0;
     bool lut3_set[2] = {false, false};
@@ -1213,19 +1216,26 @@ static int build_sublut(fvvdp_ctx* c, const fvvdp_geom* g, hipStream_t st) {
 }
 
 template <int P>
-static void launch_band(const BandArgs& a, int nblocks, bool dbg, bool fov, hipStream_t st) {
+static void launch_band(const BandArgs& a, int nblocks, bool dbg, bool fov, hipStream_t st, float* d_slope = nullptr) {
     dim3 grid(nblocks), block(64);
+    // the map-writing variants' block: `a` and the optional slope plane (built for those launches only)
+    auto with_slope = [&]() {
+        BandMapArgs am;
+        static_cast<BandArgs&>(am) = a;
+        am.dK = d_slope;
+        return am;
+    };
     if (fov) {
         const dim3 gridf((nblocks + FOV_WPB - 1) / FOV_WPB), blockf(64 * FOV_WPB);
         // dynamic LDS: [LUT slice of the band (mode 1)] + vertical view angle of every band row
         const size_t lds_vy = (size_t)a.h * sizeof(float);
         const size_t lds_lut = (size_t)FOV_PLANE * a.rw * sizeof(float4);
-        if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 2>), gridf, blockf, lds_vy, st, a);
+        if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 2>), gridf, blockf, lds_vy, st, with_slope());
         else if (a.lut_lds && a.rmap && !a.mvx) hipLaunchKernelGGL((band_kernel<P, false, 1>), gridf, blockf, lds_lut + lds_vy, st, a);
         else if (a.lut_lds) hipLaunchKernelGGL((band_kernel<P, false, 3>), gridf, blockf, lds_lut + lds_vy, st, a);
         else hipLaunchKernelGGL((band_kernel<P, false, 2>), gridf, blockf, lds_vy, st, a);
     } else {
-        if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 0>), grid, block, 0, st, a);
+        if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 0>), grid, block, 0, st, with_slope());
         else hipLaunchKernelGGL((band_kernel<P, false, 0>), grid, block, 0, st, a);
     }
 }
@@ -1487,8 +1497,8 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
         a.n_items = nblk * n;
         {
             Timed tm(c, 1 + b, st);
-            if (c->P == 4) launch_band<4>(a, nblk * n, dbg, fov, st);
-            else launch_band<2>(a, nblk * n, dbg, fov, st);
+            if (c->P == 4) launch_band<4>(a, nblk * n, dbg, fov, st, c->slope[b]);
+            else launch_band<2>(a, nblk * n, dbg, fov, st, c->slope[b]);
         }
         fa.nblk[b] = nblk;
         fa.off[b] = c->partial_off[b];
@@ -1874,6 +1884,20 @@ extern "C" int fvvdp_ctx_set_view_maps(fvvdp_ctx* c, int band, const float* d_vi
     for (int b = 0; b < c->n_bands; ++b)
         if (!c->map_vx[b]) c->maps_set = false;      // complete only when every band has its maps
     c->sub_valid = false;
+    return FVVDP_OK;
+}
+
+// include/fvvdp_hip_ref_grad.h.  Host state only: no launch, no synchronisation
+extern "C" int fvvdp_ctx_set_slope_maps(fvvdp_ctx* c, float* const* h_slope_ptrs) {
+    if (!c) return fail(FVVDP_EINVAL, "null context");
+    for (int b = 0; b < FVVDP_MAX_BANDS; ++b) {
+        float* p = (h_slope_ptrs && b < c->n_bands) ? h_slope_ptrs[b] : nullptr;
+        if (reinterpret_cast<uintptr_t>(p) % 4 != 0) {
+            for (int k = 0; k < FVVDP_MAX_BANDS; ++k) c->slope[k] = nullptr;
+            return fail(FVVDP_EINVAL, "slope plane of band %d must be aligned to 4 bytes", b);
+        }
+        c->slope[b] = p;
+    }
     return FVVDP_OK;
 }
 

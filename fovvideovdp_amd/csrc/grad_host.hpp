@@ -76,6 +76,13 @@ hipError_t video_coef_launch(const float* d_Q, const float* d_gamma, float* d_co
                              const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st);
 hipError_t video_level0_launch(const float* ws, const GradLayout& L, float* d_g0_batch, int n, hipStream_t st);
 
+// grad_coef_kernel for n pairs (coefficients [n][n_bands] into d_coef) and grad_input_kernel on the n planes of level 0 of the
+// workspace `ws`.  The kernels are defined in grad_launch.hip only, so are these functions
+hipError_t grad_coef_launch(const float* d_Q, int q_stride, int q_col0, const float* d_gamma, float* d_coef, int n, int n_bands,
+                            const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st);
+hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const void* const* h_img_ptrs, void* const* h_grad_ptrs,
+                             int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st);
+
 // `unit`: what n counts in the message ("pairs", "frames"); max_n, max_height: what the caller's launch grids reach
 static int grad_check_dims(int width, int height, int n_bands, int n, int max_n, int max_height, const char* unit) {
     if (width < 1 || height < 1 || n < 1 || n > max_n || n_bands < 1 || n_bands > FVVDP_MAX_BANDS || height > max_height)
@@ -146,12 +153,15 @@ static int grad_fill_layer(LayerArgs& la, const fvvdp_band_maps* maps, float* ws
     return blocks;
 }
 
-// coarse to fine on `planes` planes per level: G_{n_bands} (base band) ... G_1
-static hipError_t grad_sweep_levels(float* ws, const GradLayout& L, int n_bands, int planes, hipStream_t st) {
+// coarse to fine on `planes` planes per level: G_{n_bands} (base band) ... G_1.  gl_fine: where the map that goes back through
+// Expand lives, per band, when it is not the layer gradient itself (the reference's backward: GX, ref_grad_kernels.hpp)
+static hipError_t grad_sweep_levels(float* ws, const GradLayout& L, int n_bands, int planes, hipStream_t st,
+                                    const size_t* gl_fine = nullptr) {
+    if (!gl_fine) gl_fine = L.gl;
     for (int lv = n_bands; lv >= 1; --lv) {
         GradSweepArgs sa;
         sa.GL = lv < n_bands ? ws + L.gl[lv] : nullptr;
-        sa.GLf = ws + L.gl[lv - 1];
+        sa.GLf = ws + gl_fine[lv - 1];
         sa.GGc = lv < n_bands ? ws + L.gg[lv + 1] : nullptr;
         sa.GG = ws + L.gg[lv];
         sa.w = L.w[lv];

@@ -22,6 +22,57 @@ hipError_t grad_sweep_launch(const GradSweepArgs& sa, int planes, hipStream_t st
     return hipGetLastError();
 }
 
+// grad_coef_kernel and grad_input_kernel are defined here only as well: the backward with respect to the reference
+// (ref_grad_launch.hip) launches them through these two functions
+hipError_t grad_coef_launch(const float* d_Q, int q_stride, int q_col0, const float* d_gamma, float* d_coef, int n, int n_bands,
+                            const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st) {
+    GradCoefArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.Q = d_Q;
+    ca.gamma = d_gamma;
+    ca.coef = d_coef;
+    ca.n = n;
+    ca.n_bands = n_bands;
+    ca.q_stride = q_stride;
+    ca.q_col0 = q_col0;
+    ca.beta = prm->beta;
+    ca.beta_sch = pool->beta_sch;
+    ca.beta_tch = pool->beta_tch;
+    ca.jod_a = pool->jod_a;
+    ca.beta_jod = pool->beta_jod;
+    for (int b = 0; b < n_bands; ++b) ca.inv_npx[b] = (float)(1.0 / ((double)L.w[b] * L.h[b]));
+    hipLaunchKernelGGL(grad_coef_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ca);
+    return hipGetLastError();
+}
+
+// level 0 of the sweep (ws + L.gl[0], ws + L.gg[1]) and the display model's derivative at the samples `h_img_ptrs`
+hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const void* const* h_img_ptrs, void* const* h_grad_ptrs,
+                             int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st) {
+    const size_t HW = (size_t)L.w[0] * L.h[0];
+    GradInputArgs ia;
+    memset(&ia, 0, sizeof(ia));
+    ia.chan_stride = C == 3 ? chan_stride : HW;
+    ia.C = C;
+    ia.w = L.w[0];
+    ia.h = L.h[0];
+    ia.wc = L.w[1];
+    ia.hc = L.h[1];
+    grad_fill_eotf(ia.e, ia.wgt, eotf, C, h_rgb2y);
+    for (int k0 = 0; k0 < n; k0 += GRAD_MAX_PAIRS) {
+        const int nk = (n - k0) < GRAD_MAX_PAIRS ? (n - k0) : GRAD_MAX_PAIRS;
+        for (int k = 0; k < GRAD_MAX_PAIRS; ++k) {
+            ia.test[k] = k < nk ? static_cast<const float*>(h_img_ptrs[k0 + k]) : nullptr;
+            ia.grad[k] = k < nk ? static_cast<float*>(h_grad_ptrs[k0 + k]) : nullptr;
+        }
+        ia.GL0 = ws + L.gl[0] + (size_t)k0 * HW;
+        ia.GG1 = ws + L.gg[1] + (size_t)k0 * L.w[1] * L.h[1];
+        hipLaunchKernelGGL(grad_input_kernel, dim3((unsigned int)((HW + 255) / 256), nk), dim3(256), 0, st, ia);
+        const hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 // an image pair is one plane of the workspace; n is a grid dimension of its own, so the shape has no limit beyond int
 static int check_dims(int width, int height, int n_bands, int n) {
     return grad_check_dims(width, height, n_bands, n, INT_MAX, INT_MAX, "pairs");
@@ -63,23 +114,7 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     // 1. per-band coefficients
-    GradCoefArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.Q = d_Q;
-    ca.gamma = d_gamma;
-    ca.coef = ws + L.coef;
-    ca.n = n;
-    ca.n_bands = n_bands;
-    ca.q_stride = q_stride;
-    ca.q_col0 = q_col0;
-    ca.beta = prm->beta;
-    ca.beta_sch = pool->beta_sch;
-    ca.beta_tch = pool->beta_tch;
-    ca.jod_a = pool->jod_a;
-    ca.beta_jod = pool->beta_jod;
-    for (int b = 0; b < n_bands; ++b) ca.inv_npx[b] = (float)(1.0 / ((double)L.w[b] * L.h[b]));
-    hipLaunchKernelGGL(grad_coef_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ca);
-    GRAD_HIP_TRY(hipGetLastError());
+    GRAD_HIP_TRY(grad_coef_launch(d_Q, q_stride, q_col0, d_gamma, ws + L.coef, n, n_bands, prm, pool, L, st));
 
     // 2. layer gradients of every band
     GradLayerArgs la;
@@ -93,25 +128,6 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
     GRAD_HIP_TRY(grad_sweep_levels(ws, L, n_bands, n, st));
 
     // 4. level 0 and the display model, 128 pairs per launch (pointer tables in the kernel arguments)
-    GradInputArgs ia;
-    memset(&ia, 0, sizeof(ia));
-    ia.chan_stride = C == 3 ? chan_stride : HW;
-    ia.C = C;
-    ia.w = width;
-    ia.h = height;
-    ia.wc = L.w[1];
-    ia.hc = L.h[1];
-    grad_fill_eotf(ia.e, ia.wgt, eotf, C, h_rgb2y);
-    for (int k0 = 0; k0 < n; k0 += GRAD_MAX_PAIRS) {
-        const int nk = (n - k0) < GRAD_MAX_PAIRS ? (n - k0) : GRAD_MAX_PAIRS;
-        for (int k = 0; k < GRAD_MAX_PAIRS; ++k) {
-            ia.test[k] = k < nk ? static_cast<const float*>(h_test_ptrs[k0 + k]) : nullptr;
-            ia.grad[k] = k < nk ? static_cast<float*>(h_grad_ptrs[k0 + k]) : nullptr;
-        }
-        ia.GL0 = ws + L.gl[0] + (size_t)k0 * HW;
-        ia.GG1 = ws + L.gg[1] + (size_t)k0 * L.w[1] * L.h[1];
-        hipLaunchKernelGGL(grad_input_kernel, dim3((unsigned int)((HW + 255) / 256), nk), dim3(256), 0, st, ia);
-        GRAD_HIP_TRY(hipGetLastError());
-    }
+    GRAD_HIP_TRY(grad_input_launch(ws, L, n, h_test_ptrs, h_grad_ptrs, C, chan_stride, eotf, h_rgb2y, st));
     return FVVDP_OK;
 }

@@ -301,7 +301,7 @@ class fvvdp:
         with torch.cuda.device(self.device):
             return self._predict_image_group([t[k] for k in range(B)], [r[k] for k in range(B)], fix, sync)
 
-    def jod_images(self, test, reference, dim_order="BCHW", fixation_point=None):
+    def jod_images(self, test, reference, dim_order="BCHW", fixation_point=None, wrt="test"):
         """Extension: the JOD of B still-image pairs as a differentiable [B] fp32 tensor on the metric's device, for losses
         such as `10 - metric.jod_images(x, ref)`.  Values are bit-identical to predict_images(test.detach(), reference, ...)[0].
         When `test` requires grad (and grad mode is on), backward() puts dJOD_k/dtest_k into `test`, whatever its layout or
@@ -310,11 +310,17 @@ class fvvdp:
         [0, 1], or beyond a luminance clip) get a zero gradient.  Foveated metrics take `fixation_point` as predict_images.
         Nothing is synchronised with the host (a user geometry model's gaze conversion aside): the out-of-range warning of predict_images is not issued and no heat maps are
         made, whatever `heatmap` the metric was built with.  Double backward is not supported.  The backward re-runs the
-        forward with per-band maps in batches of up to `self.grad_batch` pairs (None: as many as about 4 GB of maps allow)."""
+        forward with per-band maps in batches of up to `self.grad_batch` pairs (None: as many as about 4 GB of maps allow).
+        `wrt` names the input(s) the gradient is taken for.  "test" (default): as above.  "reference": backward() puts
+        dJOD_k/dreference_k into `reference` (any layout or device, as `test` above), `test` is a constant and one that requires
+        grad is refused.  "both": one backward delivers both gradients to whichever of the two inputs require grad, from one
+        re-ingest and one map-writing pass; the test gradient is bit-identical to wrt="test".  Anything else: ValueError.  The
+        reference gradient covers its own band contrast, its role as the adaptation luminance L_bkg and, through L_bkg, the
+        CSF look-up (the slope of the LUT's interpolation); reference samples the display model clamps get zeros."""
         from .image_grad import jod_images
-        return jod_images(self, test, reference, dim_order, fixation_point)
+        return jod_images(self, test, reference, dim_order, fixation_point, wrt)
 
-    def jod_video(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+    def jod_video(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, wrt="test"):
         """Extension: the JOD of one clip as a differentiable 0-d fp32 tensor on the metric's device, for losses such as
         `10 - metric.jod_video(x, ref, frames_per_second=30)`.  The value is bit-identical to
         predict(test.detach(), reference, dim_order, frames_per_second, fixation_point)[0].  When `test` requires grad (and grad
@@ -327,9 +333,13 @@ class fvvdp:
         synchronised with the host (a user geometry model's gaze conversion aside): no out-of-range warning, no heat maps.
         Double backward is not supported.
         The backward re-runs the forward with per-band maps in batches of up to `self.grad_batch` frames (None: as many as
-        about 4 GB of maps allow); the gradient does not depend on the batching, bit for bit."""
+        about 4 GB of maps allow); the gradient does not depend on the batching, bit for bit.
+        `wrt` as jod_images takes it: "test" (default), "reference" (dJOD/dreference into `reference`; `test` is a constant
+        and one that requires grad is refused) or "both" (one backward, both gradients, one re-ingest and one map-writing
+        pass per backward batch; the test gradient is bit-identical to wrt="test").  The reference side accepts what the test
+        side accepts; a frame no temporal window shows gets zeros there too."""
         from .video_grad import jod_video
-        return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point)
+        return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point, wrt)
 
     def predict_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
         """Extension: one (test, reference) clip or image scored under G gaze traces in one pass (foveated metric, stock

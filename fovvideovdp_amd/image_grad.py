@@ -1,9 +1,11 @@
-"""Differentiable still-image JOD: fvvdp.jod_images and its autograd function (include/fvvdp_hip_grad.h).
+"""Differentiable still-image JOD: fvvdp.jod_images and its autograd function (include/fvvdp_hip_grad.h, and
+include/fvvdp_hip_ref_grad.h for the gradient with respect to the reference, `wrt=`).
 
 The forward makes the launches of fvvdp.predict_images (fvvdp_images_channels + fvvdp_images_forward_pool) with arguments from
 the same methods of the metric, so the JODs are bit-identical to it.  The backward re-runs them per backward batch with every
 band's maps written (band contrast, L_bkg, S, D), then fvvdp_images_grad turns the maps and the forward's Q_per_ch into
-dJOD/dtest on the device.  Neither pass reads context scratch left by the other, and neither synchronises with the host."""
+dJOD/dtest on the device; with wrt="reference" / "both" the same maps plus the slope planes of the CSF look-up go to
+fvvdp_images_ref_grad for dJOD/dreference -- one ingest and one pyramid pass whatever `wrt`.  Neither pass reads context scratch left by the other, and neither synchronises with the host."""
 import ctypes as C
 
 import torch
@@ -20,6 +22,32 @@ from .fvvdp import _image_stack
 GRAD_BYTES_BUDGET = 4e9
 # fp32 planes per pyramid pixel and pair: maps (D 2 + contrast 2 + L_bkg 1 + S 2) and workspace (layer + sweep gradients)
 GRAD_PLANES = 7 + 2
+WRT = ("test", "reference", "both")
+
+
+def check_wrt(wrt):
+    if wrt not in WRT:
+        raise ValueError('wrt must be "test", "reference" or "both", got %r' % (wrt,))
+    return wrt
+
+
+def grad_planes(wrt, planes_test=GRAD_PLANES, maps=7, per_plane=1):
+    """fp32 values per pyramid pixel and batch entry that the backward with respect to `wrt` holds in maps and workspace: the
+    reference's backward adds the slope planes (2, as S) and a workspace of GLR + GX + GG to the maps.
+    planes_test: what the test side's backward holds (maps included); maps: the maps' share of it; per_plane: planes per entry
+    of the reference's workspace (1: an image pair, 2: a video frame)."""
+    if wrt == "test":
+        return planes_test
+    ref = maps + 2 + 3 * per_plane
+    return ref if wrt == "reference" else ref + (planes_test - maps)
+
+
+def slope_planes(metric, n, width, height, n_bands):
+    """The slope planes kappa [n][2][h_b][w_b] of every band (fvvdp_ctx_set_slope_maps) and the pointer array both entry points
+    take; the caller keeps the tensors alive."""
+    keep = [torch.empty((n, 2, h, w), dtype=torch.float32, device=metric.device)
+            for w, h in metric._level_sizes(width, height, n_bands)[:n_bands]]
+    return (C.c_void_p * n_bands)(*[k.data_ptr() for k in keep]), keep
 
 
 class _Setup:
@@ -70,17 +98,25 @@ def grad_batch_size(metric, W, H, n_bands, batch, planes):
     return max(1, min(batch, int(GRAD_BYTES_BUDGET // (px * 4 * planes))))
 
 
-def _backward(metric, t, r, fix, Q, gamma):
-    """gamma[k] * dJOD_k/dt_k for the contiguous device stack t [B, C, H, W]."""
+def _backward(metric, t, r, fix, Q, gamma, need_t=True, need_r=False):
+    """(gamma[k] * dJOD_k/dt_k, gamma[k] * dJOD_k/dr_k) for the contiguous device stacks t, r [B, C, H, W]; None for the one
+    not asked for.  The ingest and the map-writing pyramid pass run once per backward batch, whichever gradients follow."""
     s = _Setup(metric, t)
     B, dev = s.B, metric.device
-    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, GRAD_PLANES)
-    grad = torch.empty_like(t)
+    wrt = "both" if need_t and need_r else ("reference" if need_r else "test")
+    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, grad_planes(wrt))
+    grad_t = torch.empty_like(t) if need_t else None
+    grad_r = torch.empty_like(r) if need_r else None
     maps_arr, _maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=2)
     lib = nat.lib()
-    nbytes = C.c_size_t()
-    nat.check(lib.fvvdp_images_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
-    work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    nbytes, rbytes = C.c_size_t(), C.c_size_t()
+    if need_t:
+        nat.check(lib.fvvdp_images_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
+        work = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+    if need_r:
+        nat.check(lib.fvvdp_ref_grad_workspace(s.W, s.H, s.n_bands, gb, 1, C.byref(rbytes)))
+        rwork = torch.empty((rbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+        slopes, _slopes = slope_planes(metric, gb, s.W, s.H, s.n_bands)
     q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
     jod_scratch = torch.empty(gb, dtype=torch.float32, device=dev)
     prm = metric.native_params()
@@ -89,17 +125,32 @@ def _backward(metric, t, r, fix, Q, gamma):
         nb = min(gb, B - b0)
         tp = s.ingest(lib, t, r, b0, nb)
         fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        nat.check(lib.fvvdp_images_forward_pool(s.ctx.handle, nb, C.c_void_p(q_scratch.data_ptr()), nb, 0, fx, g, maps_arr,
-                                                C.byref(s.pp), C.c_void_p(jod_scratch.data_ptr()), s.stream))
-        gp = (C.c_void_p * nb)(*[grad[k].data_ptr() for k in range(b0, b0 + nb)])
-        nat.check(lib.fvvdp_images_grad(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B, b0,
-                                        C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, tp, s.C, s.H * s.W, C.byref(s.e),
-                                        nat.fptr(s.w), gp, C.c_void_p(work.data_ptr()), nbytes.value, s.stream))
-    return grad
+        if need_r:
+            nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, slopes))
+        try:
+            nat.check(lib.fvvdp_images_forward_pool(s.ctx.handle, nb, C.c_void_p(q_scratch.data_ptr()), nb, 0, fx, g, maps_arr,
+                                                    C.byref(s.pp), C.c_void_p(jod_scratch.data_ptr()), s.stream))
+        finally:
+            if need_r:
+                nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, None))
+        if need_t:
+            gp = (C.c_void_p * nb)(*[grad_t[k].data_ptr() for k in range(b0, b0 + nb)])
+            nat.check(lib.fvvdp_images_grad(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B, b0,
+                                            C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, tp, s.C, s.H * s.W, C.byref(s.e),
+                                            nat.fptr(s.w), gp, C.c_void_p(work.data_ptr()), nbytes.value, s.stream))
+        if need_r:
+            rp = (C.c_void_p * nb)(*[r[k].data_ptr() for k in range(b0, b0 + nb)])
+            gp = (C.c_void_p * nb)(*[grad_r[k].data_ptr() for k in range(b0, b0 + nb)])
+            nat.check(lib.fvvdp_images_ref_grad(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B,
+                                                b0, C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, slopes, rp, s.C, s.H * s.W,
+                                                C.byref(s.e), nat.fptr(s.w), gp, C.c_void_p(rwork.data_ptr()), rbytes.value,
+                                                s.stream))
+    return grad_t, grad_r
 
 
 class JodImagesFunction(torch.autograd.Function):
-    """test [B, C, H, W] (contiguous fp32 on the metric's device), reference (the same, constant) -> JOD [B]."""
+    """test, reference [B, C, H, W] (contiguous fp32 on the metric's device) -> JOD [B].  place() detaches the input that
+    `wrt` treats as a constant, so needs_input_grad names the gradients to make."""
 
     @staticmethod
     def forward(ctx, test, reference, metric, fix):
@@ -113,17 +164,24 @@ class JodImagesFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_jod):
         test, reference, Q = ctx.saved_tensors
-        grad = None
-        if ctx.needs_input_grad[0]:
+        grad_t = grad_r = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             with torch.cuda.device(ctx.metric.device):
-                grad = _backward(ctx.metric, test, reference, ctx.fix, Q, grad_jod)
-        return grad, None, None, None
+                grad_t, grad_r = _backward(ctx.metric, test, reference, ctx.fix, Q, grad_jod, ctx.needs_input_grad[0],
+                                           ctx.needs_input_grad[1])
+        return grad_t, grad_r, None, None
 
 
-def refuse_unsupported(name, metric, reference):
-    """What jod_images and jod_video (`name`) refuse before they look at the shapes."""
-    if isinstance(reference, torch.Tensor) and reference.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("%s: gradients with respect to the reference are not supported; detach the reference" % name)
+def refuse_unsupported(name, metric, test, reference, wrt="test"):
+    """What jod_images, jod_video and jod_gazes (`name`) refuse before they look at the shapes.  wrt None: `name` has no wrt=."""
+    grad_on = torch.is_grad_enabled()
+    if wrt in ("test", None) and isinstance(reference, torch.Tensor) and reference.requires_grad and grad_on:
+        hint = (' (wrt= exists on jod_images and jod_video only)' if wrt is None else
+                ', or ask for its gradient with wrt="reference" or wrt="both"')
+        raise RuntimeError("%s: gradients with respect to the reference are not supported; detach the reference%s" % (name, hint))
+    if wrt == "reference" and isinstance(test, torch.Tensor) and test.requires_grad and grad_on:
+        raise RuntimeError('%s: wrt="reference" treats the test as a constant and this one requires grad; detach it, or ask '
+                           'for both gradients with wrt="both"' % name)
     if native_eotf(metric.display_photometry) is None:
         raise RuntimeError("%s needs a display model with a closed form for float input (sRGB, gamma, PQ, linear or "
                            "absolute); a user photometry class has none" % name)
@@ -134,19 +192,24 @@ def need_float32(name, what, t, r):
         raise RuntimeError("%s needs float32 test and reference %s (got %s and %s)" % (name, what, t.dtype, r.dtype))
 
 
-def place(metric, t, r):
-    """Test and reference contiguous on the metric's device, the reference detached.  The layout change and the move to the
-    device stay visible to autograd: the gradient reaches the caller's own tensor."""
+def place(metric, t, r, wrt="test"):
+    """Test and reference contiguous on the metric's device, the one `wrt` treats as a constant detached.  The layout change
+    and the move to the device stay visible to autograd: the gradient reaches the caller's own tensor."""
     metric._check_device()
-    return t.to(metric.device).contiguous(), r.detach().to(metric.device).contiguous()
+    if wrt == "test":
+        r = r.detach()
+    elif wrt == "reference":
+        t = t.detach()
+    return t.to(metric.device).contiguous(), r.to(metric.device).contiguous()
 
 
-def jod_images(metric, test, reference, dim_order="BCHW", fixation_point=None):
+def jod_images(metric, test, reference, dim_order="BCHW", fixation_point=None, wrt="test"):
     """fvvdp.jod_images (see there)."""
-    refuse_unsupported("jod_images", metric, reference)
+    check_wrt(wrt)
+    refuse_unsupported("jod_images", metric, test, reference, wrt)
     t, r = _image_stack(test, reference, dim_order)
     need_float32("jod_images", "images", t, r)
-    t, r = place(metric, t, r)
+    t, r = place(metric, t, r, wrt)
     fix = None
     if metric.foveated:
         fix = metric._fixation(fixation_point, t.shape[3], t.shape[2], t.shape[0])

@@ -5,7 +5,9 @@ fvvdp_bands_forward, the pooling of fvvdp_bands_forward_pool on the last batch) 
 metric, so the JOD is bit-identical to it.  The backward re-runs them per backward batch with every band's maps written,
 fvvdp_video_grad_frames turns the maps and the forward's Q_per_ch into the gradient of level 0's two test planes (a clip-long
 buffer), and one fvvdp_video_grad_input applies the transpose of the sliding-window temporal filter and the display model's
-derivative.  Neither pass reads context scratch left by the other, and neither synchronises with the host."""
+derivative.  With wrt="reference" / "both" the same maps plus the slope planes of the CSF look-up go to
+fvvdp_video_ref_grad_frames (include/fvvdp_hip_ref_grad.h) and a second fvvdp_video_grad_input runs on the reference clip: one
+ingest and one pyramid pass per backward batch whatever `wrt`.  Neither pass reads context scratch left by the other, and neither synchronises with the host."""
 import ctypes as C
 
 import numpy as np
@@ -14,12 +16,23 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .fvvdp import filter_length, window_frame_indices      # filter_length: imported from here by tools
-from .image_grad import grad_batch_size, need_float32, place, refuse_unsupported
+from .image_grad import check_wrt, grad_batch_size, grad_planes, need_float32, place, refuse_unsupported, slope_planes
 from .video_source import fvvdp_video_source_array, reshuffle_dims
 
 # fp32 planes per pyramid pixel and frame: maps (D 2 + contrast 4 + L_bkg 1 + S 2) and workspace (layer + sweep gradients of
 # both channels)
 GRAD_PLANES = 9 + 4
+
+
+def video_grad_planes(wrt):
+    """fp32 values per pyramid pixel and frame of a backward batch, per `wrt` (image_grad.grad_planes): 13, 17, 21."""
+    return grad_planes(wrt, GRAD_PLANES, 9, 2)
+
+
+def backward_bytes(gb, px, work_bytes, N, HW, numel, fl, n_inputs=1, slopes=False):
+    """Device memory a backward pass allocates: the maps (and slope planes) of gb frames at px pyramid pixels each, the
+    workspaces, the side buffer of the head, and per differentiated input the clip-long level-0 gradient and the result."""
+    return gb * px * 4 * (9 + (2 if slopes else 0)) + work_bytes + fl * HW * 4 + n_inputs * (N * HW * 8 + numel * 4)
 
 
 def fold_list(idx, fl, N):
@@ -89,25 +102,34 @@ def _forward(metric, t, r, fps, fix):
 
 
 class _Buffers:
-    """What a backward pass over the clip t allocates, shared by jod_video and jod_gazes (`name`): the result, the clip-long
-    level-0 gradient, the head's side buffer, the maps and scratch of a backward batch of gb frames and a workspace of
-    `work_bytes`.  Checked against the free device memory first: a sentence instead of an out-of-memory error."""
+    """What a backward pass over the clip t allocates, shared by jod_video and jod_gazes (`name`): per differentiated input the
+    result and the clip-long level-0 gradient, the head's side buffer, the maps and scratch of a backward batch of gb frames and
+    a workspace of `work_bytes` (with `ref_bytes` > 0 the slope planes and the workspace of the reference's backward as well).
+    Checked against the free device memory first: a sentence instead of an out-of-memory error."""
 
-    def __init__(self, name, metric, s, t, gb, work_bytes):
+    def __init__(self, name, metric, s, t, gb, work_bytes, need_t=True, ref_bytes=0):
         N, dev, HW = s.N, metric.device, s.H * s.W
+        need_r = ref_bytes > 0
         px = sum(w * h for w, h in metric._level_sizes(s.W, s.H, s.n_bands)[:s.n_bands])
-        need = gb * px * 4 * 9 + work_bytes + N * HW * 8 + t.numel() * 4 + s.fl * HW * 4
+        need = backward_bytes(gb, px, work_bytes + ref_bytes, N, HW, t.numel(), s.fl, int(need_t) + int(need_r), need_r)
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
         if need > free:
             raise RuntimeError("%s: the backward of this clip needs %.1f GB of device memory (maps and workspace of %d "
                                "frames, the clip-long level-0 gradient and the result) and %.1f GB are free; set a smaller "
                                "metric.grad_batch or a shorter clip" % (name, need / 1e9, gb, free / 1e9))
-        self.grad = torch.empty_like(t)
-        self.g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
+        self.grad = self.g0 = self.work = self.grad_r = self.g0_r = self.work_r = None
+        if need_t:
+            self.grad = torch.empty_like(t)
+            self.g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
+            self.work = torch.empty((work_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        if need_r:
+            self.grad_r = torch.empty_like(t)
+            self.g0_r = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
+            self.work_r = torch.empty((ref_bytes + 3) // 4, dtype=torch.float32, device=dev)
+            self.slopes, self._slopes = slope_planes(metric, gb, s.W, s.H, s.n_bands)
         self.head = torch.empty((s.fl, s.H, s.W), dtype=torch.float32, device=dev)
         self.maps_arr, self._maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=4)
-        self.work = torch.empty((work_bytes + 3) // 4, dtype=torch.float32, device=dev)
-        self.work_bytes = work_bytes
+        self.work_bytes, self.ref_bytes = work_bytes, ref_bytes
         self.q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
         self.oob = torch.zeros(1, dtype=torch.int32, device=dev)
 
@@ -115,43 +137,67 @@ class _Buffers:
         """Ingest of frames [b0, b0 + nb) and the pyramid pass that writes every band's maps, under the gaze trace `fix`."""
         s.ingest(lib, t, r, b0, nb, self.oob)
         fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(self.q_scratch.data_ptr()), nb, 0, fx, g, self.maps_arr,
-                                          s.stream))
+        if self.ref_bytes:
+            nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, self.slopes))
+        try:
+            nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(self.q_scratch.data_ptr()), nb, 0, fx, g,
+                                              self.maps_arr, s.stream))
+        finally:
+            if self.ref_bytes:
+                nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, None))
 
-    def input_grad(self, lib, s, t):
-        """The clip-long level-0 gradient -> the gradient of the clip: temporal transpose and the display model's derivative."""
+    def input_grad(self, lib, s, t, g0=None, grad=None):
+        """A clip-long level-0 gradient (default: the test's) -> the gradient of the clip t: temporal transpose and the display
+        model's derivative at t's samples."""
+        g0 = self.g0 if g0 is None else g0
+        grad = self.grad if grad is None else grad
         N, HW = s.N, s.H * s.W
         ff, fp = _fold_arrays(fold_list(s.widx, s.fl, N))
-        nat.check(lib.fvvdp_video_grad_input(s.W, s.H, N, C.c_void_p(self.g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
+        nat.check(lib.fvvdp_video_grad_input(s.W, s.H, N, C.c_void_p(g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
                                              fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
-                                             C.c_void_p(t.data_ptr()), C.c_void_p(self.grad.data_ptr()), s.C, N * HW, HW,
+                                             C.c_void_p(t.data_ptr()), C.c_void_p(grad.data_ptr()), s.C, N * HW, HW,
                                              C.byref(s.e), nat.fptr(s.w), C.c_void_p(self.head.data_ptr()), self.head.numel() * 4,
                                              s.stream))
-        return self.grad
+        return grad
 
 
-def _backward(metric, t, r, fps, fix, Q, gamma):
-    """gamma * dJOD/dt for the contiguous device clip t [1, C, N, H, W]."""
+def _backward(metric, t, r, fps, fix, Q, gamma, need_t=True, need_r=False):
+    """(gamma * dJOD/dt, gamma * dJOD/dr) for the contiguous device clips t, r [1, C, N, H, W]; None for the one not asked for.
+    The ingest and the map-writing pyramid pass run once per backward batch, whichever gradients follow."""
     s = _Setup(metric, t, fps)
     N, dev = s.N, metric.device
-    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, GRAD_PLANES)
+    wrt = "both" if need_t and need_r else ("reference" if need_r else "test")
+    gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, video_grad_planes(wrt))
     lib = nat.lib()
-    nbytes = C.c_size_t()
-    nat.check(lib.fvvdp_video_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
-    buf = _Buffers("jod_video", metric, s, t, gb, nbytes.value)
+    nbytes, rbytes = C.c_size_t(0), C.c_size_t(0)
+    if need_t:
+        nat.check(lib.fvvdp_video_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(nbytes)))
+    if need_r:
+        nat.check(lib.fvvdp_ref_grad_workspace(s.W, s.H, s.n_bands, gb, 2, C.byref(rbytes)))
+    buf = _Buffers("jod_video", metric, s, t, gb, nbytes.value, need_t, rbytes.value)
     prm = metric.native_params()
     gamma = gamma.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
     for b0 in range(0, N, gb):
         nb = min(gb, N - b0)
         buf.maps_pass(lib, metric, s, t, r, fix, b0, nb)
-        nat.check(lib.fvvdp_video_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), N,
-                                              b0, C.c_void_p(gamma.data_ptr()), buf.maps_arr, C.c_void_p(buf.g0.data_ptr()),
-                                              C.c_void_p(buf.work.data_ptr()), buf.work_bytes, s.stream))
-    return buf.input_grad(lib, s, t)
+        if need_t:
+            nat.check(lib.fvvdp_video_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()),
+                                                  N, b0, C.c_void_p(gamma.data_ptr()), buf.maps_arr,
+                                                  C.c_void_p(buf.g0.data_ptr()), C.c_void_p(buf.work.data_ptr()), buf.work_bytes,
+                                                  s.stream))
+        if need_r:
+            nat.check(lib.fvvdp_video_ref_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp),
+                                                      C.c_void_p(Q.data_ptr()), N, b0, C.c_void_p(gamma.data_ptr()), buf.maps_arr,
+                                                      buf.slopes, C.c_void_p(buf.g0_r.data_ptr()),
+                                                      C.c_void_p(buf.work_r.data_ptr()), buf.ref_bytes, s.stream))
+    grad_t = buf.input_grad(lib, s, t) if need_t else None
+    grad_r = buf.input_grad(lib, s, r, buf.g0_r, buf.grad_r) if need_r else None
+    return grad_t, grad_r
 
 
 class JodVideoFunction(torch.autograd.Function):
-    """test [1, C, N, H, W] (contiguous fp32 on the metric's device), reference (the same, constant) -> JOD (0-d)."""
+    """test, reference [1, C, N, H, W] (contiguous fp32 on the metric's device) -> JOD (0-d).  place() detaches the input that
+    `wrt` treats as a constant, so needs_input_grad names the gradients to make."""
 
     @staticmethod
     def forward(ctx, test, reference, metric, fps, fix):
@@ -165,18 +211,19 @@ class JodVideoFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_jod):
         test, reference, Q = ctx.saved_tensors
-        grad = None
-        if ctx.needs_input_grad[0]:
+        grad_t = grad_r = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             with torch.cuda.device(ctx.metric.device):
-                grad = _backward(ctx.metric, test, reference, ctx.fps, ctx.fix, Q, grad_jod)
-        return grad, None, None, None, None
+                grad_t, grad_r = _backward(ctx.metric, test, reference, ctx.fps, ctx.fix, Q, grad_jod, ctx.needs_input_grad[0],
+                                           ctx.needs_input_grad[1])
+        return grad_t, grad_r, None, None, None
 
 
-def clip_arguments(name, metric, test, reference, dim_order, frames_per_second):
+def clip_arguments(name, metric, test, reference, dim_order, frames_per_second, wrt=None):
     """What jod_video and jod_gazes (`name`) accept: one float32 clip pair of at least 2 frames, C = 1 or 3, a closed-form display
     model, a temporal filter of at most VIDEO_GRAD_MAX_TAPS taps.  Returns test and reference as [1, C, N, H, W] tensors, not yet
-    placed on the device."""
-    refuse_unsupported(name, metric, reference)
+    placed on the device.  wrt: which input the gradient is taken for (None: `name` has no wrt=, the test)."""
+    refuse_unsupported(name, metric, test, reference, wrt)
     if tuple(test.shape) != tuple(reference.shape):
         raise RuntimeError('Test and reference image/video tensors must be exactly the same shape')
     d = dim_order.upper()
@@ -204,10 +251,11 @@ def clip_arguments(name, metric, test, reference, dim_order, frames_per_second):
     return t, r
 
 
-def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+def jod_video(metric, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, wrt="test"):
     """fvvdp.jod_video (see there)."""
-    t, r = clip_arguments("jod_video", metric, test, reference, dim_order, frames_per_second)
-    t, r = place(metric, t, r)
+    check_wrt(wrt)
+    t, r = clip_arguments("jod_video", metric, test, reference, dim_order, frames_per_second, wrt)
+    t, r = place(metric, t, r, wrt)
     fix = None
     if metric.foveated:
         fix = metric._fixation(fixation_point, t.shape[4], t.shape[3], t.shape[2])

@@ -8,6 +8,7 @@ line also gets the new kernels' mean time per launch, their bytes-model rate and
 
     python tools/bench_images_grad.py                              # 256 x 512^2 RGB and 8 x 4K RGB
     python tools/bench_images_grad.py --case 8x2160x3840 --kernel-stats prof/grad_kernel_stats.csv
+    python tools/bench_images_grad.py --wrt both                   # the gradient with respect to the reference, or to both inputs
 """
 import argparse
 import csv
@@ -32,11 +33,26 @@ def levels(W, H, n_bands):
     return out
 
 
-def bytes_model(B, C, H, W, n_bands):
-    """Bytes each kernel of one backward call must move (fp32; neighbour re-reads served by caches are not counted)."""
+def bytes_model(B, C, H, W, n_bands, wrt="test"):
+    """Bytes each kernel of one backward call must move (fp32; neighbour re-reads served by caches are not counted).  The sweep
+    and the input kernel run once per differentiated input (wrt="both": twice)."""
     lv = levels(W, H, n_bands)
     band_px = sum(w * h for w, h in lv[:n_bands])            # band-pass levels 0 .. n_bands - 1
     sweep_px = sum(w * h for w, h in lv[1:])                 # levels 1 .. n_bands
+    out = _bytes_model_test(B, C, H, W, n_bands, band_px, sweep_px)
+    if wrt != "test":
+        # maps D, test / reference contrast, L_bkg, S, slope (24 B) read, GLR and GX written (8 B)
+        out["ref_layer_kernel"] = B * band_px * 32
+        out["maps_written"] = B * band_px * 24              # the slope plane on top of the five maps
+    if wrt == "reference":
+        del out["adj_layer_kernel"]
+    if wrt == "both":
+        for k in ("adj_sweep_kernel", "grad_input_kernel", "grad_coef_kernel"):
+            out[k] *= 2
+    return out
+
+
+def _bytes_model_test(B, C, H, W, n_bands, band_px, sweep_px):
     return {
         # maps D, test / reference contrast, L_bkg, S (20 B) read, layer gradient written (4 B)
         "adj_layer_kernel": B * band_px * 24,
@@ -57,6 +73,8 @@ def kernel_stats(path):
         for row in csv.DictReader(f):
             name = row.get("Name") or row.get("KernelName") or ""
             base = name.split("(")[0].split("<")[0].strip()
+            if base.startswith("void "):
+                base = base[5:]
             calls = int(float(row.get("Calls", 0)))
             mean = float(row.get("AverageNs", row.get("Average", 0)))
             if base:
@@ -81,8 +99,9 @@ def run_case(key, a, stats):
         m.predict_images(test, ref, sync=False)
 
     def fwd_bwd():
-        x = test.detach().requires_grad_(True)
-        m.jod_images(x, ref).sum().backward()
+        x = test.detach().requires_grad_(a.wrt != "reference")
+        y = ref.detach().requires_grad_(a.wrt != "test")
+        m.jod_images(x, y, wrt=a.wrt).sum().backward()
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -101,20 +120,22 @@ def run_case(key, a, stats):
         tg.append(timed(fwd_bwd))
     ms_f, ms_g = float(np.median(tf)), float(np.median(tg))
     n_bands = band_frequencies(W, H, m.pix_per_deg)[0]
-    bm = bytes_model(B, C, H, W, n_bands)
+    bm = bytes_model(B, C, H, W, n_bands, a.wrt)
     px = 2.0 * B * H * W
     out = {"case": key, "pairs": B, "height": H, "width": W, "channels": C, "display": a.display, "n_bands": n_bands,
+           "wrt": a.wrt,
            "forward_ms": round(ms_f, 3), "forward_gpix_per_s": round(px / (ms_f * 1e-3) / 1e9, 2),
            "fwd_bwd_ms": round(ms_g, 3), "fwd_bwd_gpix_per_s": round(px / (ms_g * 1e-3) / 1e9, 2),
            "fwd_bwd_over_forward": round(ms_g / ms_f, 2), "bytes_model": bm,
            "forward_ms_spread": [round(min(tf), 3), round(max(tf), 3)],
            "fwd_bwd_ms_spread": [round(min(tg), 3), round(max(tg), 3)]}
     if stats:
-        calls_per_bwd = {"adj_layer_kernel": 1, "grad_coef_kernel": 1, "adj_sweep_kernel": n_bands,
-                         "grad_input_kernel": (B + 127) // 128}
+        sides = 2 if a.wrt == "both" else 1
+        calls_per_bwd = {"adj_layer_kernel": 1, "ref_layer_kernel": 1, "grad_coef_kernel": sides, "adj_sweep_kernel": sides * n_bands,
+                         "grad_input_kernel": sides * ((B + 127) // 128)}
         kern = {}
         for k, per in calls_per_bwd.items():
-            if k in stats:
+            if k in stats and k in bm:
                 calls, mean_ns = stats[k]
                 t_bwd = mean_ns * per * 1e-9                  # seconds per backward call
                 kern[k] = {"calls": calls, "mean_us": round(mean_ns / 1e3, 2), "us_per_backward": round(t_bwd * 1e6, 1),
@@ -129,6 +150,7 @@ def main():
     ap.add_argument("--display", default="standard_4k")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=7)
+    ap.add_argument("--wrt", default="test", choices=["test", "reference", "both"], help="the input(s) the backward differentiates")
     ap.add_argument("--kernel-stats", default=None, help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run")
     a = ap.parse_args()
     stats = kernel_stats(a.kernel_stats) if a.kernel_stats else None

@@ -8,6 +8,7 @@ line also gets the new kernels' mean time per launch, their bytes-model rate and
 
     python tools/bench_video_grad.py                              # 1920x1080x30 and 3840x2160x60 RGB at 30 fps
     python tools/bench_video_grad.py --case 60x2160x3840 --kernel-stats prof/kernel_stats.csv
+    python tools/bench_video_grad.py --wrt both                   # the gradient with respect to the reference, or to both inputs
 """
 import argparse
 import csv
@@ -32,11 +33,26 @@ def levels(W, H, n_bands):
     return out
 
 
-def bytes_model(N, C, H, W, n_bands, fl):
-    """Bytes each kernel of one backward call must move (fp32; neighbour re-reads served by caches are not counted)."""
+def bytes_model(N, C, H, W, n_bands, fl, wrt="test"):
+    """Bytes each kernel of one backward call must move (fp32; neighbour re-reads served by caches are not counted).  The sweep,
+    level 0 and the transpose run once per differentiated input (wrt="both": twice)."""
     lv = levels(W, H, n_bands)
     band_px = sum(w * h for w, h in lv[:n_bands])            # band-pass levels 0 .. n_bands - 1
     sweep_px = sum(w * h for w, h in lv[1:])                 # levels 1 .. n_bands
+    out = _bytes_model_test(N, C, H, W, fl, band_px, sweep_px)
+    if wrt != "test":
+        # 11 map values read (D 2, contrast 4, L_bkg 1, S 2, slope 2), GLR and GX of both channels written
+        out["ref_layer_kernel"] = N * band_px * 60
+        out["maps_written"] = N * band_px * 44              # the slope planes on top of the 9 maps
+    if wrt == "reference":
+        del out["video_layer_kernel"]
+    if wrt == "both":
+        for k in ("adj_sweep_kernel", "video_level0_kernel", "video_input_kernel"):
+            out[k] *= 2
+    return out
+
+
+def _bytes_model_test(N, C, H, W, fl, band_px, sweep_px):
     return {
         # 9 map values read (D 2, contrast 4, L_bkg 1, S 2), 2 layer gradients written
         "video_layer_kernel": N * band_px * 44,
@@ -72,7 +88,7 @@ def kernel_stats(path):
 def run_case(key, a, stats):
     import fovvideovdp_amd as fv
     from fovvideovdp_amd.fvvdp import band_frequencies
-    from fovvideovdp_amd.video_grad import GRAD_PLANES, filter_length, grad_batch_size
+    from fovvideovdp_amd.video_grad import filter_length, grad_batch_size, video_grad_planes
     N, H, W = CASES[key]
     C = 3
     dev = torch.device("cuda:0")
@@ -86,8 +102,9 @@ def run_case(key, a, stats):
         m.predict(test, ref, frames_per_second=a.fps, sync=False)
 
     def fwd_bwd():
-        x = test.detach().requires_grad_(True)
-        m.jod_video(x, ref, frames_per_second=a.fps).backward()
+        x = test.detach().requires_grad_(a.wrt != "reference")
+        y = ref.detach().requires_grad_(a.wrt != "test")
+        m.jod_video(x, y, frames_per_second=a.fps, wrt=a.wrt).backward()
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -107,11 +124,11 @@ def run_case(key, a, stats):
     ms_f, ms_g = float(np.median(tf)), float(np.median(tg))
     n_bands = band_frequencies(W, H, m.pix_per_deg)[0]
     fl = filter_length(a.fps)
-    bm = bytes_model(N, C, H, W, n_bands, fl)
-    gb = grad_batch_size(m, W, H, n_bands, m._batch_size(W, H, 4, N, fl), GRAD_PLANES)
+    bm = bytes_model(N, C, H, W, n_bands, fl, a.wrt)
+    gb = grad_batch_size(m, W, H, n_bands, m._batch_size(W, H, 4, N, fl), video_grad_planes(a.wrt))
     px = 2.0 * N * H * W
     out = {"case": key, "frames": N, "height": H, "width": W, "channels": C, "fps": a.fps, "taps": fl, "display": a.display,
-           "n_bands": n_bands, "grad_batch": gb,
+           "n_bands": n_bands, "grad_batch": gb, "wrt": a.wrt,
            "forward_ms": round(ms_f, 3), "forward_gpix_per_s": round(px / (ms_f * 1e-3) / 1e9, 2),
            "fwd_bwd_ms": round(ms_g, 3), "fwd_bwd_gpix_per_s": round(px / (ms_g * 1e-3) / 1e9, 2),
            "fwd_bwd_over_forward": round(ms_g / ms_f, 2), "bytes_model": bm,
@@ -119,8 +136,10 @@ def run_case(key, a, stats):
            "fwd_bwd_ms_spread": [round(min(tg), 3), round(max(tg), 3)]}
     if stats:
         n_batches = (N + gb - 1) // gb
-        calls_per_bwd = {"video_layer_kernel": n_batches, "video_coef_kernel": n_batches, "adj_sweep_kernel": n_bands * n_batches,
-                         "video_level0_kernel": n_batches, "video_input_kernel": 1}
+        sides = 2 if a.wrt == "both" else 1
+        calls_per_bwd = {"video_layer_kernel": n_batches, "ref_layer_kernel": n_batches, "video_coef_kernel": sides * n_batches,
+                         "adj_sweep_kernel": sides * n_bands * n_batches, "video_level0_kernel": sides * n_batches,
+                         "video_input_kernel": sides}
         kern = {}
         for k, per in calls_per_bwd.items():
             if k in stats:
@@ -140,6 +159,7 @@ def main():
     ap.add_argument("--fps", type=float, default=30.0)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=7)
+    ap.add_argument("--wrt", default="test", choices=["test", "reference", "both"], help="the input(s) the backward differentiates")
     ap.add_argument("--kernel-stats", default=None, help="kernel_stats.csv of a rocprofv3 --kernel-trace --stats run")
     a = ap.parse_args()
     stats = kernel_stats(a.kernel_stats) if a.kernel_stats else None

@@ -162,19 +162,29 @@ REF_GRAD_SYMBOLS = {
                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# include/fvvdp_hip_params.h: the model parameters of a live context and the sums their gradients need (bound by lib() as well)
+PARAM_SYMBOLS = {
+    "fvvdp_ctx_set_params": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
+    "fvvdp_param_sums_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fvvdp_param_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(BandMaps), C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+PARAM_SUMS = 5                           # FVVDP_PARAM_SUMS
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Ten translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Eleven translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..3), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
-    video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip) and the gradients with
-    respect to the reference (ref_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
+    respect to the reference (ref_grad_launch.hip) and the sums for the gradients with respect to the model parameters
+    (param_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
-                                                                                                                              "fvvdp_hip_ref_grad.h")]
+                                                                                                                              "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -197,6 +207,8 @@ def build(force=False, verbose=False):
     units += [(os.path.join(csrc, "gaze_grad_launch.hip"), [], os.path.join(objdir, "gaze_grad_launch.o"))]
     # gradients with respect to the reference (include/fvvdp_hip_ref_grad.h)
     units += [(os.path.join(csrc, "ref_grad_launch.hip"), [], os.path.join(objdir, "ref_grad_launch.o"))]
+    # the sums for the gradients with respect to the model parameters (include/fvvdp_hip_params.h)
+    units += [(os.path.join(csrc, "param_launch.hip"), [], os.path.join(objdir, "param_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -223,7 +235,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()) + list(GRAD_SYMBOLS.items()) + \
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
-                list(REF_GRAD_SYMBOLS.items()):
+                list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -24,6 +24,7 @@
 #include "fvvdp_hip_images.h"
 #include "fvvdp_hip_gaze.h"
 #include "fvvdp_hip_ref_grad.h"
+#include "fvvdp_hip_params.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // errors
@@ -1898,6 +1899,20 @@ extern "C" int fvvdp_ctx_set_slope_maps(fvvdp_ctx* c, float* const* h_slope_ptrs
         }
         c->slope[b] = p;
     }
+    return FVVDP_OK;
+}
+
+// include/fvvdp_hip_params.h.  Host state only: every launch derives what it needs from c->prm when it fills its arguments
+// (band_args, the finalisation's 1 / beta, clamps_never_bind), so there is nothing else to refresh
+extern "C" int fvvdp_ctx_set_params(fvvdp_ctx* c, const fvvdp_params* prm) {
+    if (!c || !prm) return fail(FVVDP_EINVAL, "null argument");
+    for (float x : {prm->mask_p, prm->mask_q[0], prm->mask_q[1], prm->mask_k, prm->beta, prm->sens_gain, prm->lbkg_min,
+                    prm->contrast_max, prm->d_max})
+        if (!std::isfinite(x)) return fail(FVVDP_EINVAL, "model constants must be finite");
+    if (!(prm->mask_p > 0.0f) || !(prm->beta > 0.0f) || !(prm->mask_k > 0.0f) || !(prm->sens_gain > 0.0f) ||
+        !(prm->contrast_max > 0.0f) || !(prm->d_max > 0.0f) || prm->lbkg_min < 0.0f)
+        return fail(FVVDP_EINVAL, "mask_p, beta, mask_k, sens_gain, contrast_max and d_max must be positive, lbkg_min not negative");
+    c->prm = *prm;
     return FVVDP_OK;
 }
 

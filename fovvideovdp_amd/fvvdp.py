@@ -373,6 +373,44 @@ class fvvdp:
         from .gaze_grad import jod_gazes
         return jod_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
 
+    # ---- the model parameters as variables (extension; include/fvvdp_hip_params.h, param_grad.py) ---------------------
+    # the parameters a calibration can fit, in the order of the vectors below: the first six act per band pixel (masking model,
+    # sensitivity gain, spatial pooling exponent), the last six in do_pooling_and_jods
+    PARAMETER_NAMES = ("mask_p", "mask_q_sust", "mask_q_trans", "mask_c", "sensitivity_correction", "beta",
+                       "beta_sch", "beta_tch", "beta_t", "w_transient", "jod_a", "log_jod_exp")
+
+    def parameter_tensor(self):
+        """Extension: the current values of PARAMETER_NAMES as a 1-D float64 host tensor."""
+        from .param_grad import parameter_tensor
+        return parameter_tensor(self)
+
+    def set_parameters(self, theta):
+        """Extension: writes a vector laid out as PARAMETER_NAMES into the metric's attributes (what load_config sets)."""
+        from .param_grad import set_parameters
+        set_parameters(self, theta)
+
+    def calibration_jod_images(self, test, reference, theta, dim_order="BCHW", fixation_point=None):
+        """Extension: the JODs of B still-image pairs evaluated UNDER the parameter vector `theta` (laid out as
+        PARAMETER_NAMES), as a [B] fp32 tensor on the metric's device, for fitting the model to subjective data.  The metric's
+        own attributes are not touched, also when the call raises, and its native context is reused whatever theta is.  The
+        values are bit-identical to predict_images on a metric whose attributes hold theta.  When `theta` requires grad (and
+        grad mode is on), backward() puts sum_k grad[k] dJOD_k/dtheta into theta.grad, in theta's dtype and on its device;
+        theta may be float32 or float64, on the host (read without synchronising the GPU) or on a device.  Sources: what
+        predict_images accepts as arrays (uint8 / uint16 / float32, C = 1 or 3); they are constants (one that requires grad is
+        refused: jod_images), no out-of-range warning is issued and no heat maps are made (a heat-map metric is refused).
+        With a gradient the forward costs a plain pass plus a map-writing pass and one reduction kernel over the maps
+        (fvvdp_param_sums), in batches of up to `self.grad_batch` pairs; backward() is arithmetic on [bands, 2, B] arrays."""
+        from .param_grad import calibration_jod_images
+        return calibration_jod_images(self, test, reference, theta, dim_order, fixation_point)
+
+    def calibration_jod_video(self, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+        """Extension: the JOD of one clip evaluated under the parameter vector `theta`, a 0-d fp32 tensor on the metric's
+        device; as calibration_jod_images, with predict in the place of predict_images (one clip, B = 1; every temporal padding;
+        `fixation_point` as predict takes it) and jod_video for gradients with respect to the frames.  The gradient does not
+        depend on `self.grad_batch`, bit for bit."""
+        from .param_grad import calibration_jod_video
+        return calibration_jod_video(self, test, reference, theta, dim_order, frames_per_second, fixation_point)
+
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
         or with them of size 1).  The pairs are grouped by (shape, dtypes) and every group is scored in batches by

@@ -936,6 +936,9 @@ extern "C" int fvvdp_temporal_channels_yuv(fvvdp_ctx* c, const void* d_test, con
         for (int k = 0; k < nu; ++k) la.fr[k] = uniq[k];
         k1_launch_yuv_luminance(fmt->bit_depth > 8 ? 2 : 1, la, st);
         HIP_TRY(hipGetLastError());
+        if (c->env.debug_variant)                        // tests: which ingest path ran (the per-pixel arithmetic takes the nine-term matrix)
+            fprintf(stderr, "fvvdp: yuv ingest: two-pass, FL 64, fl %d, bytes %d, chroma_420 %d, eotf kind %d, matrix nine-term\n",
+                    fl, fmt->bit_depth > 8 ? 2 : 1, a.chroma420, eotf->kind);
         std::vector<int32_t> pos(total);
         for (int u = 0; u < total; ++u) pos[u] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), h_frame_idx[u]) - uniq.begin());
         fvvdp_eotf none;
@@ -989,6 +992,13 @@ extern "C" int fvvdp_temporal_channels_yuv(fvvdp_ctx* c, const void* d_test, con
             k1_launch_yuv_vec(FL, bytes, a.chroma420 != 0, c->env.yuv_general, a, st);
         } else {
             k1_launch_yuv(FL, bytes, a, st);
+        }
+        if (c->env.debug_variant) {                      // tests: which instantiation was launched
+            // the ITU shape that selects the four-term matrix (yuv_matrix_is_standard, temporal_launch.hip); the per-pixel kernel has the nine-term form only
+            const bool itu = a.m[0] == 1.0f && a.m[3] == 1.0f && a.m[6] == 1.0f && a.m[1] == 0.0f && a.m[8] == 0.0f;
+            fprintf(stderr, "fvvdp: yuv ingest: %s, FL %d, fl %d, bytes %d, chroma_420 %d, eotf kind %d, matrix %s\n",
+                    vec_ok ? "vector" : "per-pixel", FL, fl, bytes, a.chroma420, eotf->kind,
+                    (vec_ok && itu && !c->env.yuv_general) ? "four-term" : "nine-term");
         }
     }
     HIP_TRY(hipGetLastError());

@@ -568,6 +568,7 @@ static EotfDev make_eotf(const fvvdp_eotf* e) {
     }
     return d;
 }
+EotfDev fvvdp_eotf_dev(const fvvdp_eotf* e) { return make_eotf(e); }      // for tap_grad_launch.hip (fvvdp_luminance_frames)
 
 // context-owned buffer of fp32 luminance frames for the two-pass temporal paths (33..64 taps), grown on demand
 static int grow_lum_buf(fvvdp_ctx* c, size_t need_floats, int fl, hipStream_t st) {

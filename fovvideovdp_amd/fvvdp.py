@@ -66,6 +66,22 @@ def filter_length(fps):
     return int(np.ceil(250.0 / (1000.0 / fps)))
 
 
+def temporal_filters(frames_per_s, filter_len, sigma, beta):
+    """Sustained (log-Gaussian) and transient (its scaled derivative) temporal filters, fp32 [2, filter_len], for the frame rate,
+    filter length, sustained_sigma and sustained_beta given (Python floats): the body of fvvdp.get_temporal_filters
+    (fvvdp.py:609-630 of the reference), which calibration_jod_video(temporal=...) evaluates under values of its own."""
+    t = torch.linspace(0.0, filter_len / frames_per_s, filter_len)
+    F = torch.zeros((2, t.shape[0]))
+    sigma = torch.tensor([sigma])
+    beta = torch.tensor([beta])
+    F[0] = torch.exp(-torch.pow(torch.log(t + 1e-4) - torch.log(beta), 2.0) / (2.0 * (sigma ** 2.0)))
+    F[0] = F[0] / torch.sum(F[0])
+    k2 = 0.062170507756932
+    Fdiff = F[0, 1:] - F[0, :-1]
+    F[1] = k2 * torch.cat([Fdiff / (t[1] - t[0]), torch.tensor([0.0])], 0)
+    return F
+
+
 def window_frame_indices(N, fl, temp_padding):
     """Source frame for every virtual time step: fl-1 history entries (temporal padding before frame 0) followed
     by the newest frame of each of the N outputs.  Matches the window the reference builds at frame 0 and then
@@ -403,13 +419,39 @@ class fvvdp:
         from .param_grad import calibration_jod_images
         return calibration_jod_images(self, test, reference, theta, dim_order, fixation_point)
 
-    def calibration_jod_video(self, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+    def calibration_jod_video(self, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None,
+                              temporal=None):
         """Extension: the JOD of one clip evaluated under the parameter vector `theta`, a 0-d fp32 tensor on the metric's
         device; as calibration_jod_images, with predict in the place of predict_images (one clip, B = 1; every temporal padding;
-        `fixation_point` as predict takes it) and jod_video for gradients with respect to the frames.  The gradient does not
-        depend on `self.grad_batch`, bit for bit."""
+        `fixation_point` as predict takes it) and jod_video for gradients with respect to the frames.  The gradient with respect
+        to theta does not depend on `self.grad_batch`, bit for bit.
+        temporal: None (the metric's own temporal filters: the launches and the bits of a call without it), or a vector `phi`
+        laid out as TEMPORAL_PARAMETER_NAMES (sustained_sigma, sustained_beta; float32 or float64, host or device): the clip is
+        evaluated under temporal filters made from phi by the expressions of get_temporal_filters, so the JOD is bit-identical to
+        predict on a metric whose attributes hold theta and phi; the metric's attributes are not touched and its context is
+        reused.  When phi requires grad, backward() puts dJOD/dphi into phi.grad, in phi's dtype and on its device; theta and phi
+        may require grad together or either alone, and theta's gradient is bit-identical whether or not phi is given.  With a
+        gradient for phi every backward batch makes one ingest and one map-writing pass (shared with theta's sums), the two
+        level-0 backward passes of jod_video(wrt="both"), the luminance of the frames under the batch's windows and the
+        tap-gradient kernel (include/fvvdp_hip_taps.h); only dJOD/dtaps [2, filter_len] is kept.  phi.grad depends on
+        `self.grad_batch` through the grouping of fp32 sums only (see fvvdp_tap_grad).  Filters above 64 taps are refused when
+        phi requires grad."""
         from .param_grad import calibration_jod_video
-        return calibration_jod_video(self, test, reference, theta, dim_order, frames_per_second, fixation_point)
+        return calibration_jod_video(self, test, reference, theta, dim_order, frames_per_second, fixation_point, temporal)
+
+    # the two continuous parameters of the temporal filters (extension; include/fvvdp_hip_taps.h, param_grad.py): not part of
+    # PARAMETER_NAMES -- they enter through the host-side taps, and only a clip has a temporal filter
+    TEMPORAL_PARAMETER_NAMES = ("sustained_sigma", "sustained_beta")
+
+    def temporal_parameter_tensor(self):
+        """Extension: the current values of TEMPORAL_PARAMETER_NAMES as a 1-D float64 host tensor."""
+        from .param_grad import temporal_parameter_tensor
+        return temporal_parameter_tensor(self)
+
+    def set_temporal_parameters(self, phi):
+        """Extension: writes a vector laid out as TEMPORAL_PARAMETER_NAMES into the metric's attributes, as Python floats."""
+        from .param_grad import set_temporal_parameters
+        set_temporal_parameters(self, phi)
 
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
@@ -814,15 +856,7 @@ class fvvdp:
     def get_temporal_filters(self, frames_per_s):
         """Sustained (log-Gaussian) and transient (its scaled derivative) temporal filters, fp32 [2, filter_len];
         tap k weights the frame k steps in the past.  Evaluated on the host."""
-        t = torch.linspace(0.0, self.filter_len / frames_per_s, self.filter_len)
-        F = torch.zeros((2, t.shape[0]))
-        sigma = torch.tensor([self.sustained_sigma])
-        beta = torch.tensor([self.sustained_beta])
-        F[0] = torch.exp(-torch.pow(torch.log(t + 1e-4) - torch.log(beta), 2.0) / (2.0 * (sigma ** 2.0)))
-        F[0] = F[0] / torch.sum(F[0])
-        k2 = 0.062170507756932
-        Fdiff = F[0, 1:] - F[0, :-1]
-        F[1] = k2 * torch.cat([Fdiff / (t[1] - t[0]), torch.tensor([0.0])], 0)
+        F = temporal_filters(frames_per_s, self.filter_len, self.sustained_sigma, self.sustained_beta)
         omega = torch.tensor([0, 5])
         return F, omega
 
@@ -1153,6 +1187,18 @@ class fvvdp:
                         ctx.handle, C.c_void_p(test_d.data_ptr()), C.c_void_p(ref_d.data_ptr()), dtype, C_ch,
                         N * HW, HW, C.byref(e), nat.fptr(w), idx.ctypes.data_as(C.POINTER(C.c_int32)),
                         nat.fptr(taps), fl, n_out, slot0, C.c_void_p(oob.data_ptr()), stream))
+
+                def luminance(frames, out, oob, stream):
+                    """fp32 luminance of the source frames `frames` (int32 array) of both clips into out [2, len, H, W]: the
+                    values feed's temporal kernel filters (fvvdp_luminance_frames)."""
+                    if remap is not None:
+                        frames = remap[frames]
+                    frames = np.ascontiguousarray(frames, dtype=np.int32)
+                    nat.check(lib.fvvdp_luminance_frames(
+                        C.c_void_p(test_d.data_ptr()), C.c_void_p(ref_d.data_ptr()), dtype, C_ch, width, height, N * HW, HW,
+                        C.byref(e), nat.fptr(w), frames.ctypes.data_as(C.POINTER(C.c_int32)), len(frames),
+                        C.c_void_p(out.data_ptr()), C.c_void_p(oob.data_ptr()), stream))
+                feed.luminance = luminance
                 return feed
         if (isinstance(vs, fvvdp_video_source_yuv_frames) and native_eotf(vs.dm_photometry) is not None
                 and not (hasattr(vs, "_resizing") and vs._resizing())

@@ -11,8 +11,16 @@ band's maps written, per backward batch of frames (image_grad.grad_batch_size), 
 sums per (band, temporal channel, frame); only Q_per_ch and the sums are kept.  backward() is `chain` alone: float64 tensor
 operations on [bands, 2, frames] arrays.
 
-Not part of the vector: k_cm and csf_sigma (they select a precomputed CSF table), sustained_sigma, sustained_beta and filter_len
-(they enter through the host-side temporal taps) and the enumerated model variants."""
+Not part of the vector: k_cm and csf_sigma (they select a precomputed CSF table), filter_len (an integer) and the enumerated
+model variants.
+
+sustained_sigma and sustained_beta (TEMPORAL_PARAMETER_NAMES) are a vector of their own, `phi`, that calibration_jod_video takes
+as temporal=: they enter only through the taps of the temporal filters, which are a per-call argument of the ingest, so the
+clip is evaluated under taps made from phi (fvvdp.temporal_filters, the expressions of get_temporal_filters).  When phi needs a
+gradient, every backward batch also makes the two level-0 backward passes of jod_video(wrt="both") with gamma = 1 from the same
+maps (slope planes on), the luminance of the source frames under the batch's windows (fvvdp_luminance_frames) and the
+tap-gradient kernel (fvvdp_tap_grad, include/fvvdp_hip_taps.h); the batches' dJOD/dtaps [2, fl] are added in frame order in
+float64 and are all that is kept.  backward() is `tap_chain`: the float64 Jacobian of the taps with respect to phi."""
 import ctypes as C
 import math
 
@@ -25,6 +33,8 @@ from .fvvdp import fvvdp as _fvvdp
 from .image_grad import grad_batch_size
 
 PARAMETER_NAMES = _fvvdp.PARAMETER_NAMES
+TEMPORAL_PARAMETER_NAMES = _fvvdp.TEMPORAL_PARAMETER_NAMES
+K2 = 0.062170507756932                   # scale of the transient filter (get_temporal_filters)
 _IDX = {name: i for i, name in enumerate(PARAMETER_NAMES)}
 _POSITIVE = ("beta", "beta_sch", "beta_tch", "beta_t", "mask_p")
 LN10 = math.log(10.0)
@@ -63,6 +73,65 @@ def theta_values(theta):
     if vals[_IDX["jod_a"]] == 0:
         raise RuntimeError("theta: jod_a must not be 0 (the JOD would not depend on the images)")
     return vals
+
+
+def temporal_parameter_tensor(metric):
+    """The metric's current values of TEMPORAL_PARAMETER_NAMES as a 1-D float64 host tensor."""
+    return torch.tensor([float(getattr(metric, name)) for name in TEMPORAL_PARAMETER_NAMES], dtype=torch.float64)
+
+
+def set_temporal_parameters(metric, phi):
+    """Writes a vector laid out as TEMPORAL_PARAMETER_NAMES into the metric's attributes, as Python floats.  The taps are an
+    argument of every call: the native context stays."""
+    for name, v in zip(TEMPORAL_PARAMETER_NAMES, phi_values(phi)):
+        setattr(metric, name, v)
+
+
+def phi_values(phi):
+    """phi (a 1-D tensor or sequence of the 2 values of TEMPORAL_PARAMETER_NAMES) -> list of Python floats; refuses what no
+    temporal filter can be made from.  A host tensor is read without touching the GPU."""
+    t = phi.detach() if isinstance(phi, torch.Tensor) else torch.as_tensor(np.asarray(phi, dtype=np.float64))
+    if t.dim() != 1 or t.shape[0] != len(TEMPORAL_PARAMETER_NAMES):
+        raise RuntimeError("temporal must be a 1-D vector of the %d parameters of TEMPORAL_PARAMETER_NAMES, got shape %s"
+                           % (len(TEMPORAL_PARAMETER_NAMES), tuple(t.shape)))
+    if not t.is_floating_point():
+        raise RuntimeError("temporal must be a float32 or float64 tensor, got %s" % t.dtype)
+    vals = [float(v) for v in t.to(device="cpu", dtype=torch.float64).tolist()]
+    bad = [TEMPORAL_PARAMETER_NAMES[i] for i, v in enumerate(vals) if not math.isfinite(v)]
+    if bad:
+        raise RuntimeError("temporal has non-finite entries: %s" % ", ".join(bad))
+    for name, v in zip(TEMPORAL_PARAMETER_NAMES, vals):
+        if not v > 0:
+            raise RuntimeError("temporal: %s must be positive (a width and a time of the log-Gaussian filter), got %g" % (name, v))
+    return vals
+
+
+def taps_jacobian(fps, fl, sigma, beta):
+    """(taps [2, fl], d taps / d(sigma, beta) [2, fl, 2]) in float64, by hand.
+    F0 = e / sum e with e_k = exp(-(ln(t_k + 1e-4) - ln beta)^2 / (2 sigma^2)), t = linspace(0, fl / fps, fl);
+    F1_k = K2 (F0_{k+1} - F0_k) / dt for k < fl - 1 and F1_{fl-1} = 0, a constant: its derivative is exactly 0.
+    With d = ln(t + 1e-4) - ln beta:  dln e / dsigma = d^2 / sigma^3,  dln e / dbeta = d / (sigma^2 beta), and
+    dF0_k / dp = F0_k (a_k - sum_j F0_j a_j) for a = dln e / dp."""
+    t = torch.linspace(0.0, fl / fps, fl, dtype=torch.float64)
+    d = torch.log(t + 1e-4) - math.log(beta)
+    e = torch.exp(-d * d / (2.0 * sigma * sigma))
+    F0 = e / e.sum()
+    a = torch.stack([d * d / sigma ** 3, d / (sigma * sigma * beta)], dim=1)          # [fl, 2]
+    dF0 = F0[:, None] * (a - (F0[:, None] * a).sum(0, keepdim=True))
+    F = torch.zeros((2, fl), dtype=torch.float64)
+    J = torch.zeros((2, fl, 2), dtype=torch.float64)
+    F[0], J[0] = F0, dF0
+    if fl > 1:
+        dt = t[1] - t[0]
+        F[1, :-1] = K2 * (F0[1:] - F0[:-1]) / dt
+        J[1, :-1] = K2 * (dF0[1:] - dF0[:-1]) / dt
+    return F, J
+
+
+def tap_chain(dtaps, fps, fl, sigma, beta):
+    """dJOD/dphi [2] float64 from dJOD/dtaps [2, fl] (any device and float dtype)."""
+    _, J = taps_jacobian(fps, fl, sigma, beta)
+    return (dtaps.to(device="cpu", dtype=torch.float64)[:, :, None] * J).sum(dim=(0, 1))
 
 
 def native_params_of(vals):
@@ -272,10 +341,84 @@ def _images_forward(metric, t, r, fix, vals, want_sums):
     return jod, Q, sums
 
 
-def _video_forward(metric, vs, fixation_point, vals, want_sums):
+class _TapGrad:
+    """Buffers of the tap gradient for a clip of N frames in backward batches of up to gb: the clip-long level-0 gradients of
+    both sides, the workspaces of the two level-0 backward passes, the slope planes, the luminance frames under a batch's
+    windows, workspace and result of fvvdp_tap_grad, and the running dJOD/dtaps [2, fl] (float64, added in frame order).
+    Checked against the free device memory first: a sentence instead of an out-of-memory error."""
+
+    def __init__(self, metric, W, H, n_bands, gb, N, fl, with_scale=False):
+        from .image_grad import slope_planes
+        dev, HW = metric.device, H * W
+        lib = nat.lib()
+        vb, rb, tb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        nat.check(lib.fvvdp_video_grad_workspace(W, H, n_bands, gb, C.byref(vb)))
+        nat.check(lib.fvvdp_ref_grad_workspace(W, H, n_bands, gb, 2, C.byref(rb)))
+        nat.check(lib.fvvdp_tap_grad_workspace(W, H, fl, C.byref(tb)))
+        n_lum = min(N, fl - 1 + gb)
+        px = sum(w * h for w, h in metric._level_sizes(W, H, n_bands)[:n_bands])
+        lum_bytes = 2 * n_lum * HW * 4
+        need = gb * px * 4 * (9 + 2) + vb.value + rb.value + tb.value + 2 * N * HW * 8 + lum_bytes
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        if need > free:
+            raise RuntimeError("calibration_jod_video: the gradient for the temporal parameters of this clip needs %.1f GB of "
+                               "device memory (maps and workspace of %d frames, the clip-long level-0 gradients of both sides "
+                               "and %.2f GB of luminance frames under a batch's windows) and %.1f GB are free; set a smaller "
+                               "metric.grad_batch or a shorter clip" % (need / 1e9, gb, lum_bytes / 1e9, free / 1e9))
+        self.W, self.H, self.n_bands, self.N, self.fl, self.n_lum = W, H, n_bands, N, fl, n_lum
+        self.g0 = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
+        self.g0_r = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
+        self.work = torch.empty((vb.value + 3) // 4, dtype=torch.float32, device=dev)
+        self.work_r = torch.empty((rb.value + 3) // 4, dtype=torch.float32, device=dev)
+        self.work_bytes, self.ref_bytes, self.tap_bytes = vb.value, rb.value, tb.value
+        self.slopes, self._slopes = slope_planes(metric, gb, W, H, n_bands)
+        self.lum = torch.empty((2, n_lum, H, W), dtype=torch.float32, device=dev)
+        self.tap_work = torch.empty((tb.value + 7) // 8, dtype=torch.float64, device=dev)
+        self.out = torch.empty((2, fl), dtype=torch.float64, device=dev)
+        self.dtaps = torch.zeros((2, fl), dtype=torch.float64, device=dev)
+        self.gamma = torch.ones(1, dtype=torch.float32, device=dev)
+        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.scale = torch.zeros((2, fl), dtype=torch.float64, device=dev) if with_scale else None
+
+    def batch(self, feeder, prm, pp, Q, maps_arr, idx, b0, nb, stream):
+        """The maps of output frames [b0, b0 + nb) (slope planes included) -> their share of dJOD/dtaps, added to self.dtaps.
+        idx: the batch's slice of the window index list (fl - 1 + nb source frames, oldest first)."""
+        lib = nat.lib()
+        W, H, HW = self.W, self.H, self.H * self.W
+        nat.check(lib.fvvdp_video_grad_frames(W, H, self.n_bands, nb, C.byref(prm), C.byref(pp), C.c_void_p(Q.data_ptr()), self.N, b0,
+                                              C.c_void_p(self.gamma.data_ptr()), maps_arr, C.c_void_p(self.g0.data_ptr()),
+                                              C.c_void_p(self.work.data_ptr()), self.work_bytes, stream))
+        nat.check(lib.fvvdp_video_ref_grad_frames(W, H, self.n_bands, nb, C.byref(prm), C.byref(pp), C.c_void_p(Q.data_ptr()), self.N,
+                                                  b0, C.c_void_p(self.gamma.data_ptr()), maps_arr, self.slopes,
+                                                  C.c_void_p(self.g0_r.data_ptr()), C.c_void_p(self.work_r.data_ptr()),
+                                                  self.ref_bytes, stream))
+        frames = np.unique(idx)
+        nu = len(frames)
+        pos = np.ascontiguousarray(np.searchsorted(frames, idx), dtype=np.int32)
+        lum = self.lum.view(-1)[:2 * nu * HW]
+        feeder.luminance(frames, lum, self.flag, stream)
+        nat.check(lib.fvvdp_tap_grad(W, H, nb, self.fl, C.c_void_p(self.g0.data_ptr() + b0 * 2 * HW * 4),
+                                     C.c_void_p(self.g0_r.data_ptr() + b0 * 2 * HW * 4), C.c_void_p(lum.data_ptr()),
+                                     C.c_void_p(lum.data_ptr() + nu * HW * 4), pos.ctypes.data_as(C.POINTER(C.c_int32)), nu,
+                                     C.c_void_p(self.out.data_ptr()), C.c_void_p(self.tap_work.data_ptr()), self.tap_bytes, stream))
+        self.dtaps += self.out
+        if self.scale is not None:
+            # the yardstick of the kernel's rounding: sum |g0 Y| per entry, with torch, in float64
+            widx = torch.as_tensor(pos.astype(np.int64), device=self.out.device)
+            t = torch.arange(nb, device=self.out.device)
+            for k in range(self.fl):
+                q = widx[t + self.fl - 1 - k]
+                for g, y in ((self.g0, self.lum.view(-1)[:nu * HW].view(nu, H, W)),
+                             (self.g0_r, self.lum.view(-1)[nu * HW:2 * nu * HW].view(nu, H, W))):
+                    self.scale[:, k] += (g[b0:b0 + nb].abs().double() * y[q].double()[:, None].abs()).sum(dim=(0, 2, 3))
+
+
+def _video_pass(metric, vs, fixation_point, vals, want_sums, pvals=None, want_taps=False, with_scale=False):
     """The launches of fvvdp._predict_on_device (sync=False, no heat maps) under theta -> (JOD 0-d, Q [bands, 2, N], _Sums or
-    None, number of temporal channels)."""
-    from .fvvdp import _PipelinedSourceFeeder
+    None, number of temporal channels, dJOD/dtaps [2, fl] float64 or None).  pvals: the values of TEMPORAL_PARAMETER_NAMES the
+    taps are made from (None: the metric's own taps); want_taps: also the gradient of the JOD with respect to the taps."""
+    from .fvvdp import _PipelinedSourceFeeder, temporal_filters
+    from .video_grad import video_grad_planes
     height, width, N = vs.get_video_size()
     dev = metric.device
     fix = metric._fixation(fixation_point, width, height, N) if metric.foveated else None
@@ -284,6 +427,12 @@ def _video_forward(metric, vs, fixation_point, vals, want_sums):
         raise RuntimeError("calibration_jod_video needs a display model with a closed form for float input (sRGB, gamma, PQ, "
                            "linear or absolute); a user photometry class has none")
     n_bands, planes, fl, taps, widx = pl.n_bands, pl.planes, pl.fl, pl.taps, pl.widx
+    if pvals is not None:
+        if planes != 4:
+            raise RuntimeError("calibration_jod_video: temporal= needs a clip of at least 2 frames (a single frame has no "
+                               "temporal filter)")
+        # the taps under phi: never cached (an optimiser makes a new phi per step), never written to the metric
+        taps = np.ascontiguousarray(temporal_filters(vs.get_frames_per_second(), fl, pvals[0], pvals[1]).numpy(), dtype=np.float32)
     ctx = metric._context(width, height, n_bands, planes, pl.batch, pl.rho_band)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     nq = n_bands * 2 * N
@@ -305,6 +454,31 @@ def _video_forward(metric, vs, fixation_point, vals, want_sums):
             else:
                 nat.check(lib.fvvdp_bands_forward(ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None, stream))
             b0 += nb
+        if want_taps:
+            # one ingest and one map-writing pass per backward batch (slope planes on, as jod_video(wrt="both")): theta's sums
+            # and the two level-0 backward passes read the same maps
+            gb = grad_batch_size(metric, width, height, n_bands, pl.batch, video_grad_planes("both"))
+            gb = max(1, min(gb, nat.TAPS_MAX_POSITIONS - (fl - 1)))
+            tg = _TapGrad(metric, width, height, n_bands, gb, N, fl, with_scale)
+            sums = _Sums(metric, width, height, n_bands, planes, gb, N)
+            for b0 in range(0, N, gb):
+                nb = min(gb, N - b0)
+                idx = np.ascontiguousarray(widx[b0:b0 + fl - 1 + nb])
+                pl.feeder(ctx, idx, taps, fl, nb, tg.flag, stream)
+                fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
+                nat.check(lib.fvvdp_ctx_set_slope_maps(ctx.handle, tg.slopes))
+                try:
+                    nat.check(lib.fvvdp_bands_forward(ctx.handle, nb, C.c_void_p(sums.q_scratch.data_ptr()), nb, 0, fx, g,
+                                                      sums.maps_arr, stream))
+                finally:
+                    nat.check(lib.fvvdp_ctx_set_slope_maps(ctx.handle, None))
+                if want_sums:
+                    sums.reduce(prm, b0, nb, stream)
+                tg.batch(pl.feeder, prm, pp, Q, sums.maps_arr, idx, b0, nb, stream)
+            sums._maps = sums.maps_arr = None
+            if not want_sums:
+                sums = None
+            return res[nq + 1], Q, sums, planes // 2, (tg.dtaps, tg.scale) if with_scale else tg.dtaps
         if want_sums:
             gb = grad_batch_size(metric, width, height, n_bands, pl.batch, 9 if planes == 4 else 7)
             sums = _Sums(metric, width, height, n_bands, planes, gb, N)
@@ -318,7 +492,26 @@ def _video_forward(metric, vs, fixation_point, vals, want_sums):
                                                   sums.maps_arr, stream))
                 sums.reduce(prm, b0, nb, stream)
             sums._maps = sums.maps_arr = None
-    return res[nq + 1], Q, sums, planes // 2
+    return res[nq + 1], Q, sums, planes // 2, None
+
+
+def _video_forward(metric, vs, fixation_point, vals, want_sums):
+    """_video_pass under the metric's own temporal filters -> (JOD 0-d, Q [bands, 2, N], _Sums or None, temporal channels)."""
+    return _video_pass(metric, vs, fixation_point, vals, want_sums)[:4]
+
+
+def tap_gradient(metric, test, reference, theta, temporal, dim_order="BCFHW", frames_per_second=0, fixation_point=None,
+                 with_scale=False):
+    """dJOD/dtaps [2, fl] (float64, on the metric's device) of one clip under theta and phi: what the forward of
+    calibration_jod_video keeps when phi requires grad.  For tests and tools.  with_scale: also sum |g0 Y| of every entry, the
+    yardstick of the tap-gradient kernel's rounding (include/fvvdp_hip_taps.h), made with torch."""
+    from .video_source import fvvdp_video_source_array
+    vals, pvals = theta_values(theta), phi_values(temporal)
+    vs = fvvdp_video_source_array(test, reference, frames_per_second, dim_order=dim_order,
+                                  display_photometry=metric.display_photometry, color_space_name=metric.color_space)
+    metric._check_device()
+    with torch.cuda.device(metric.device):
+        return _video_pass(metric, vs, fixation_point, vals, False, pvals, True, with_scale)[4]
 
 
 class _CalibrationFunction(torch.autograd.Function):
@@ -343,6 +536,43 @@ class _CalibrationFunction(torch.autograd.Function):
         g = grad_jod.to(device=J.device, dtype=torch.float64).reshape(-1, 1)
         grad = (g * J).sum(0)
         return grad.to(device=ctx.theta_device, dtype=ctx.theta_dtype), None, None, None, None
+
+
+class _TemporalCalibrationFunction(torch.autograd.Function):
+    """(theta, phi) -> the JOD of a clip.  `run(want_sums, want_taps)` makes the forward under their values; dJOD/dtaps does
+    not depend on the upstream gradient, so the forward forms it and keeps [2, fl] values."""
+
+    @staticmethod
+    def forward(ctx, theta, phi, metric, vals, run, tap_args):
+        want_theta, want_phi = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        with torch.cuda.device(metric.device):
+            jod, Q, sums, channels, dtaps = run(want_theta, want_phi)
+        ctx.want_theta, ctx.want_phi, ctx.tap_args = want_theta, want_phi, tap_args
+        ctx.phi_device, ctx.phi_dtype = phi.device, phi.dtype
+        keep = []
+        if want_theta:
+            ctx.vals, ctx.channels, ctx.npx = vals, channels, sums.npx
+            ctx.theta_device, ctx.theta_dtype = theta.device, theta.dtype
+            keep += [Q, sums.sums]
+        if want_phi:
+            keep.append(dtaps)
+        ctx.save_for_backward(*keep)
+        return jod.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_jod):
+        saved = list(ctx.saved_tensors)
+        g_theta = g_phi = None
+        if ctx.want_theta:
+            Q, sums = saved[0], saved[1]
+            J = chain(Q, sums, ctx.npx, ctx.vals, ctx.channels, False)
+            g = grad_jod.to(device=J.device, dtype=torch.float64).reshape(-1, 1)
+            g_theta = (g * J).sum(0).to(device=ctx.theta_device, dtype=ctx.theta_dtype)
+        if ctx.want_phi:
+            J = tap_chain(saved[-1], *ctx.tap_args)                                         # [2] float64, host
+            g_phi = (grad_jod.to(device="cpu", dtype=torch.float64).reshape(()) * J).to(device=ctx.phi_device, dtype=ctx.phi_dtype)
+        return g_theta, g_phi, None, None, None, None
 
 
 def _refuse(name, metric, test, reference, other):
@@ -377,10 +607,19 @@ def calibration_jod_images(metric, test, reference, theta, dim_order="BCHW", fix
     return _apply(metric, theta, vals, run, True)
 
 
-def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None,
+                          temporal=None):
     """fvvdp.calibration_jod_video (see there)."""
+    from .fvvdp import filter_length
     from .video_source import fvvdp_video_source_array
     vals = theta_values(theta)
+    pvals = None if temporal is None else phi_values(temporal)
+    phi_grad = isinstance(temporal, torch.Tensor) and temporal.requires_grad and torch.is_grad_enabled()
+    if phi_grad and frames_per_second > 0 and filter_length(frames_per_second) > nat.VIDEO_GRAD_MAX_TAPS:
+        raise RuntimeError("calibration_jod_video: frame rate too high for the gradient of the temporal parameters: the temporal "
+                           "filter has %d taps, the tap-gradient kernel covers %d (256 frames per second); the forward runs "
+                           "with a temporal= that does not require grad"
+                           % (filter_length(frames_per_second), nat.VIDEO_GRAD_MAX_TAPS))
     _refuse("calibration_jod_video", metric, test, reference, "jod_video")
     d = dim_order.upper()
     if "B" in d and len(d) == len(test.shape) and test.shape[d.index("B")] != 1:
@@ -389,7 +628,17 @@ def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", fra
                                   display_photometry=metric.display_photometry, color_space_name=metric.color_space)
     metric._check_device()
 
-    def run(want_sums):
-        return _video_forward(metric, vs, fixation_point, vals, want_sums)
+    if temporal is None:
+        def run(want_sums):
+            return _video_forward(metric, vs, fixation_point, vals, want_sums)
 
-    return _apply(metric, theta, vals, run, False)
+        return _apply(metric, theta, vals, run, False)
+
+    def run_phi(want_sums, want_taps=False):
+        return _video_pass(metric, vs, fixation_point, vals, want_sums, pvals, want_taps)
+
+    if not phi_grad:
+        return _apply(metric, theta, vals, lambda want_sums: run_phi(want_sums)[:4], False)
+    fps = float(vs.get_frames_per_second())
+    return _TemporalCalibrationFunction.apply(theta, temporal, metric, vals, run_phi,
+                                              (fps, filter_length(fps), pvals[0], pvals[1]))

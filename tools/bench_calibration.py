@@ -6,6 +6,11 @@ Prints one JSON line per case: median ms per call with min .. max, the ratios, a
 
     python tools/bench_calibration.py                       # 1920x1080x60 RGB at 30 fps
     python tools/bench_calibration.py --case 30x2160x3840
+    python tools/bench_calibration.py --temporal            # also the gradients for sustained_sigma / sustained_beta
+
+--temporal adds calibration_jod_video(temporal=phi) forward + backward with phi alone and with theta and phi requiring grad to the
+alternation, and fvvdp_tap_grad alone at 8 and 15 taps against its bytes model (include/fvvdp_hip_taps.h: per tap group of 8, 16 B
+of level-0 gradients and 8 B of luminance per pixel and frame).
 """
 import argparse
 import ctypes as C
@@ -59,7 +64,17 @@ def run_case(key, a):
         e1.synchronize()
         return e0.elapsed_time(e1)
 
-    fns = (fwd, calib_fwd, calib, video_grad)
+    phi0 = m.temporal_parameter_tensor()
+
+    def calib_phi():
+        phi = phi0.clone().requires_grad_(True)
+        m.calibration_jod_video(test, ref, theta, frames_per_second=a.fps, temporal=phi).backward()
+
+    def calib_both():
+        th, phi = theta.clone().requires_grad_(True), phi0.clone().requires_grad_(True)
+        m.calibration_jod_video(test, ref, th, frames_per_second=a.fps, temporal=phi).backward()
+
+    fns = (fwd, calib_fwd, calib, video_grad) + ((calib_phi, calib_both) if a.temporal else ())
     for _ in range(a.warmup):
         for fn in fns:
             timed(fn)
@@ -105,7 +120,40 @@ def run_case(key, a):
                           "tb_per_s": round(nbytes / (ms_k * 1e-3) / 1e12, 2),
                           "hbm_peak_share": round(nbytes / (ms_k * 1e-3) / HBM_PEAK, 3),
                           "ms_per_clip": round(ms_k * N / gb, 3)}}
+    if a.temporal:
+        out["calibration_phi_fwd_bwd_ms"] = round(med[4], 3)
+        out["calibration_theta_phi_fwd_bwd_ms"] = round(med[5], 3)
+        out["phi_over_theta"] = round(med[4] / med[2], 2)
+        out["tap_grad"] = [tap_grad_alone(nat, stream, timed, H, W, fl_k, a) for fl_k in (8, 15)]
     print(json.dumps(out), flush=True)
+
+
+def tap_grad_alone(nat, stream, timed, H, W, fl, a, n=16):
+    """fvvdp_tap_grad on n frames of random planes under a replicate window, against its bytes model."""
+    dev = torch.device("cuda:0")
+    HW = H * W
+    g0, g0r = (torch.randn((n, 2, H, W), device=dev) for _ in range(2))
+    lum = torch.rand((2, n, H, W), device=dev) * 100.0
+    pos = np.ascontiguousarray(np.concatenate([np.zeros(fl - 1, np.int32), np.arange(n, dtype=np.int32)]))
+    nbytes = C.c_size_t(0)
+    lib = nat.lib()
+    nat.check(lib.fvvdp_tap_grad_workspace(W, H, fl, C.byref(nbytes)))
+    work = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty((2, fl), dtype=torch.float64, device=dev)
+    st = C.c_void_p(stream.cuda_stream)
+
+    def run():
+        nat.check(lib.fvvdp_tap_grad(W, H, n, fl, C.c_void_p(g0.data_ptr()), C.c_void_p(g0r.data_ptr()), C.c_void_p(lum.data_ptr()),
+                                     C.c_void_p(lum.data_ptr() + n * HW * 4), pos.ctypes.data_as(C.POINTER(C.c_int32)), n,
+                                     C.c_void_p(out.data_ptr()), C.c_void_p(work.data_ptr()), nbytes.value, st))
+
+    ts = [timed(run) for _ in range(a.warmup + a.steps)][a.warmup:]
+    groups = (fl + nat.TAP_GROUP - 1) // nat.TAP_GROUP
+    model = groups * n * HW * 24
+    ms = float(np.median(ts))
+    return {"taps": fl, "frames": n, "tap_groups": groups, "bytes_model": model, "ms": round(ms, 4),
+            "spread_ms": [round(min(ts), 4), round(max(ts), 4)], "tb_per_s": round(model / (ms * 1e-3) / 1e12, 2),
+            "hbm_peak_share": round(model / (ms * 1e-3) / HBM_PEAK, 3)}
 
 
 def main():
@@ -115,6 +163,7 @@ def main():
     ap.add_argument("--fps", type=float, default=30.0)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--steps", type=int, default=7)
+    ap.add_argument("--temporal", action="store_true", help="also the gradients for the temporal filters' sigma and beta")
     a = ap.parse_args()
     for key in a.case or ["60x1080x1920"]:
         run_case(key, a)

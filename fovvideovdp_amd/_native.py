@@ -183,20 +183,37 @@ TAP_SYMBOLS = {
 TAPS_MAX_POSITIONS = 320                 # FVVDP_TAPS_MAX_POSITIONS
 TAP_GROUP = 8                            # FVVDP_TAP_GROUP
 
+# include/fvvdp_hip_display.h: the sums behind the gradient with respect to the display's photometry (bound by lib() as well)
+DISPLAY_SYMBOLS = {
+    "fvvdp_video_display_sums_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fvvdp_video_display_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_size_t,
+                                           C.POINTER(Eotf), C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.c_void_p]),
+    "fvvdp_images_display_sums_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fvvdp_images_display_sums": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(PoolParams), C.c_void_p,
+                                            C.c_int, C.c_int, C.c_void_p, C.POINTER(BandMaps), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.POINTER(Eotf), C.POINTER(C.c_float),
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+DISPLAY_SUMS = 3                         # FVVDP_DISPLAY_SUMS
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twelve translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Thirteen translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..3), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
-    (param_launch.hip) and the gradient with respect to the temporal taps (tap_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip) and the sums for the gradient with
+    respect to the display's photometry (display_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
-                                                                                                                              "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h")]
+                                                                                                                              "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
+                                                                                                                              "fvvdp_hip_display.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -225,6 +242,8 @@ def build(force=False, verbose=False):
     # multiply-adds want the rotating ring slots in aligned register pairs; the moves that arrange them cost more than the packing
     # saves and push the kernel past the registers of two waves per SIMD
     units += [(os.path.join(csrc, "tap_grad_launch.hip"), ["-fno-slp-vectorize"], os.path.join(objdir, "tap_grad_launch.o"))]
+    # the sums behind the gradient with respect to the display's photometry (include/fvvdp_hip_display.h)
+    units += [(os.path.join(csrc, "display_grad_launch.hip"), [], os.path.join(objdir, "display_grad_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -251,7 +270,8 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()) + list(GRAD_SYMBOLS.items()) + \
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
-                list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()):
+                list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
+                list(DISPLAY_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

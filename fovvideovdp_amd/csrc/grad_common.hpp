@@ -1,6 +1,7 @@
 // Device functions and argument blocks that the still-image backward (grad_kernels.hpp, grad_launch.hip) and the video
 // backward (video_grad_kernels.hpp, video_grad_launch.hip) share: the transposes of the pyramid's reduce / expand stencils, the
-// arguments of adj_sweep_kernel and the display model's derivative.  No kernel is defined here: the four kernels of
+// arguments of adj_sweep_kernel and the display model's derivative -- for the sample (eotf_grad) and, for the sums of
+// display_grad_kernels.hpp, for the display's own parameters (eotf_display_sens).  No kernel is defined here: the four kernels of
 // grad_kernels.hpp stay in the one translation unit that compiles them.
 #pragma once
 
@@ -122,5 +123,47 @@ __device__ __forceinline__ float eotf_grad(float V, const EotfDev& e) {
             return (V >= e.l_min && V <= e.l_max) ? 1.0f : 0.0f;
         default:
             return 0.0f;
+    }
+}
+
+// The luminance of a channel sample differentiated for the display instead of the sample (display_grad_kernels.hpp).  With
+// Y_black = E_ambient k_refl / pi + Y_peak / contrast and scale = Y_peak - Y_black the sample's luminance is
+// scale f(clamp01 V) + Y_black (SRGB, GAMMA) or clip(g(V), 0.005, Y_peak) + Y_black (PQ, LINEAR); dL/dY_black = 1 throughout.
+//   a1  SRGB / GAMMA: f(clamp01 V) = dL/dscale -- not zero at a clamped sample, unlike eotf_grad;
+//       PQ / LINEAR: 1 where the upper luminance clip binds = dL/dY_peak at fixed Y_black, else 0;
+//   a2  GAMMA: scale V^gamma ln V = dL/dgamma, exactly 0 at V <= 0 (and at V >= 1); 0 for every other model.
+// powf / logf, not the forward's fast log2 / exp2 pair: the value is a factor of a sum that is compared with float64.
+__device__ __forceinline__ void eotf_display_sens(float V, const EotfDev& e, float& a1, float& a2) {
+    a1 = 0.0f;
+    a2 = 0.0f;
+    switch (e.kind) {
+        case FVVDP_EOTF_SRGB: {
+            const float v = fminf(fmaxf(V, 0.0f), 1.0f);
+            a1 = v > 0.04045f ? powf((v + 0.055f) * (1.0f / 1.055f), 2.4f) : v * (1.0f / 12.92f);
+            break;
+        }
+        case FVVDP_EOTF_GAMMA: {
+            const float v = fminf(fmaxf(V, 0.0f), 1.0f);
+            if (v > 0.0f) {
+                a1 = powf(v, e.gamma);
+                a2 = e.scale * a1 * logf(v);
+            }
+            break;
+        }
+        case FVVDP_EOTF_PQ: {
+            const float v = fminf(fmaxf(V, 0.0f), 1.0f);
+            const float m = 78.843750000000000f, n = 0.15930175781250000f;
+            const float c1 = 0.83593750000000000f, c2 = 18.851562500000000f, c3 = 18.687500000000000f;
+            const float t = v > 0.0f ? powf(v, 1.0f / m) : 0.0f;
+            const float r = fmaxf(t - c1, 0.0f) / (c2 - c3 * t);
+            const float L = r > 0.0f ? 10000.0f * powf(r, 1.0f / n) : 0.0f;
+            a1 = L > e.y_peak ? 1.0f : 0.0f;
+            break;
+        }
+        case FVVDP_EOTF_LINEAR:
+            a1 = V > e.y_peak ? 1.0f : 0.0f;
+            break;
+        default:
+            break;
     }
 }

@@ -83,6 +83,17 @@ hipError_t grad_coef_launch(const float* d_Q, int q_stride, int q_col0, const fl
 hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const void* const* h_img_ptrs, void* const* h_grad_ptrs,
                              int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st);
 
+// fvvdp_images_grad's launches before its last, in a workspace laid out as L (defined in grad_launch.hip, with adj_layer_kernel),
+// and the reference side's counterpart with the size of its workspace in floats (defined in ref_grad_launch.hip, with
+// ref_layer_kernel; *layout receives the test side's part of the layout: coefficients, GLR in the place of GL, GG)
+int grad_images_sweep(int n_bands, int n, const fvvdp_params* prm, const fvvdp_pool_params* pool, const float* d_Q, int q_stride,
+                      int q_col0, const float* d_gamma, const fvvdp_band_maps* maps, float* ws, const GradLayout& L,
+                      hipStream_t st);
+size_t ref_images_workspace_floats(int width, int height, int n_bands, int n);
+int ref_images_sweep(int width, int height, int n_bands, int n, const fvvdp_params* prm, const fvvdp_pool_params* pool,
+                     const float* d_Q, int q_stride, int q_col0, const float* d_gamma, const fvvdp_band_maps* maps,
+                     const float* const* h_slope_ptrs, float* ws, GradLayout* layout, hipStream_t st);
+
 // `unit`: what n counts in the message ("pairs", "frames"); max_n, max_height: what the caller's launch grids reach
 static int grad_check_dims(int width, int height, int n_bands, int n, int max_n, int max_height, const char* unit) {
     if (width < 1 || height < 1 || n < 1 || n > max_n || n_bands < 1 || n_bands > FVVDP_MAX_BANDS || height > max_height)

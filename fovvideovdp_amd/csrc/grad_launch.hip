@@ -73,6 +73,28 @@ hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const 
     return hipSuccess;
 }
 
+// Steps 1 to 3 of fvvdp_images_grad in the workspace `ws` laid out as L: the per-band coefficients, the layer gradients of every
+// band and the sweep from the base band down to G_1.  adj_layer_kernel is defined here only: the sums for the display's gradient
+// (display_grad_launch.hip) make the same launches through this function
+int grad_images_sweep(int n_bands, int n, const fvvdp_params* prm, const fvvdp_pool_params* pool, const float* d_Q, int q_stride,
+                      int q_col0, const float* d_gamma, const fvvdp_band_maps* maps, float* ws, const GradLayout& L,
+                      hipStream_t st) {
+    // 1. per-band coefficients
+    GRAD_HIP_TRY(grad_coef_launch(d_Q, q_stride, q_col0, d_gamma, ws + L.coef, n, n_bands, prm, pool, L, st));
+
+    // 2. layer gradients of every band
+    GradLayerArgs la;
+    memset(&la, 0, sizeof(la));
+    const int blocks = grad_fill_layer(la, maps, ws, L, n_bands, prm);
+    la.q = prm->mask_q[0];
+    hipLaunchKernelGGL(adj_layer_kernel, dim3(blocks, n), dim3(256), 0, st, la);
+    GRAD_HIP_TRY(hipGetLastError());
+
+    // 3. coarse to fine: G_{n_bands} (base band) ... G_1
+    GRAD_HIP_TRY(grad_sweep_levels(ws, L, n_bands, n, st));
+    return FVVDP_OK;
+}
+
 // an image pair is one plane of the workspace; n is a grid dimension of its own, so the shape has no limit beyond int
 static int check_dims(int width, int height, int n_bands, int n) {
     return grad_check_dims(width, height, n_bands, n, INT_MAX, INT_MAX, "pairs");
@@ -113,19 +135,8 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
     float* ws = static_cast<float*>(d_work);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
-    // 1. per-band coefficients
-    GRAD_HIP_TRY(grad_coef_launch(d_Q, q_stride, q_col0, d_gamma, ws + L.coef, n, n_bands, prm, pool, L, st));
-
-    // 2. layer gradients of every band
-    GradLayerArgs la;
-    memset(&la, 0, sizeof(la));
-    const int blocks = grad_fill_layer(la, maps, ws, L, n_bands, prm);
-    la.q = prm->mask_q[0];
-    hipLaunchKernelGGL(adj_layer_kernel, dim3(blocks, n), dim3(256), 0, st, la);
-    GRAD_HIP_TRY(hipGetLastError());
-
-    // 3. coarse to fine: G_{n_bands} (base band) ... G_1
-    GRAD_HIP_TRY(grad_sweep_levels(ws, L, n_bands, n, st));
+    // 1. - 3. coefficients, layer gradients, sweep down to G_1
+    GRAD_CHECK(grad_images_sweep(n_bands, n, prm, pool, d_Q, q_stride, q_col0, d_gamma, maps, ws, L, st));
 
     // 4. level 0 and the display model, 128 pairs per launch (pointer tables in the kernel arguments)
     GRAD_HIP_TRY(grad_input_launch(ws, L, n, h_test_ptrs, h_grad_ptrs, C, chan_stride, eotf, h_rgb2y, st));

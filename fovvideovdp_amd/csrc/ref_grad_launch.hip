@@ -61,6 +61,26 @@ static int ref_layers_and_sweep(const fvvdp_band_maps* maps, const float* const*
     return FVVDP_OK;
 }
 
+// The reference side of the still-image sums for the display's gradient (display_grad_launch.hip): the layout of
+// fvvdp_images_ref_grad's workspace and its launches down to G_1.  ref_layer_kernel is instantiated here only
+size_t ref_images_workspace_floats(int width, int height, int n_bands, int n) {
+    RefGradLayout R;
+    ref_grad_layout(width, height, n_bands, n, 1, R);
+    return R.L.total;
+}
+
+int ref_images_sweep(int width, int height, int n_bands, int n, const fvvdp_params* prm, const fvvdp_pool_params* pool,
+                     const float* d_Q, int q_stride, int q_col0, const float* d_gamma, const fvvdp_band_maps* maps,
+                     const float* const* h_slope_ptrs, float* ws, GradLayout* layout, hipStream_t st) {
+    GRAD_CHECK(check_slopes(h_slope_ptrs, n_bands));
+    RefGradLayout R;
+    ref_grad_layout(width, height, n_bands, n, 1, R);
+    GRAD_HIP_TRY(grad_coef_launch(d_Q, q_stride, q_col0, d_gamma, ws + R.L.coef, n, n_bands, prm, pool, R.L, st));
+    GRAD_CHECK(ref_layers_and_sweep<1>(maps, h_slope_ptrs, ws, R, n_bands, n, prm, st));
+    *layout = R.L;
+    return FVVDP_OK;
+}
+
 extern "C" int fvvdp_ref_grad_workspace(int width, int height, int n_bands, int n, int planes, size_t* bytes) {
     if (!bytes) return grad_fail(FVVDP_EINVAL, "null argument");
     if (planes != 1 && planes != 2) return grad_fail(FVVDP_EINVAL, "planes must be 1 (image pairs) or 2 (video frames), got %d", planes);

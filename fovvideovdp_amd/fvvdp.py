@@ -453,6 +453,48 @@ class fvvdp:
         from .param_grad import set_temporal_parameters
         set_temporal_parameters(self, phi)
 
+    # the numeric constructor arguments of fvvdp_display_photo_eotf (extension; include/fvvdp_hip_display.h, display_grad.py): a
+    # vector of their own, `psi` -- they enter through the display block, a per-call argument of every ingest
+    DISPLAY_PARAMETER_NAMES = ("Y_peak", "contrast", "E_ambient", "k_refl", "gamma")
+
+    def display_parameter_tensor(self):
+        """Extension: the values of DISPLAY_PARAMETER_NAMES of the metric's fvvdp_display_photo_eotf as a 1-D float64 host
+        tensor."""
+        from .display_grad import display_parameter_tensor
+        return display_parameter_tensor(self)
+
+    def set_display_parameters(self, psi):
+        """Extension: gives the metric a new fvvdp_display_photo_eotf with the values of `psi` (laid out as
+        DISPLAY_PARAMETER_NAMES) and the metric's own EOTF kind, through set_display_model; the geometry stays."""
+        from .display_grad import set_display_parameters
+        set_display_parameters(self, psi)
+
+    def display_jod_images(self, test, reference, psi, dim_order="BCHW", fixation_point=None):
+        """Extension: the JODs of B still-image pairs shown on a display whose photometry is fvvdp_display_photo_eotf(**psi) with
+        the metric's own EOTF kind (psi laid out as DISPLAY_PARAMETER_NAMES), as a [B] fp32 tensor on the metric's device.  The
+        geometry and the colour space are the metric's.  The metric's photometry object and its native context are not touched,
+        also when the call raises, and nothing is cached per psi.  The values are bit-identical to predict_images on a metric
+        built with that photometry from the same Python floats.  When `psi` requires grad (and grad mode is on), backward()
+        puts sum_k grad[k] dJOD_k/dpsi into psi.grad, in psi's dtype (float32 or float64) and on its device (host or GPU).
+        Sources: float32, C = 1 or 3; they are constants (one that requires grad is refused: jod_images); integer sources, a
+        photometry other than the stock fvvdp_display_photo_eotf and a heat-map metric are refused; no out-of-range warning is
+        issued.  Without a gradient the call makes the launches of predict_images only.  With one the forward adds, per batch
+        of up to `self.grad_batch` pairs, an ingest, a map-writing pass and the two backward passes of jod_images(wrt="both")
+        with a reduction in the place of their last kernel (fvvdp_images_display_sums); backward() is arithmetic on
+        [B, 2, 3] doubles."""
+        from .display_grad import display_jod_images
+        return display_jod_images(self, test, reference, psi, dim_order, fixation_point)
+
+    def display_jod_video(self, test, reference, psi, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+        """Extension: the JOD of one clip shown on a display with the photometry psi, a 0-d fp32 tensor on the metric's device;
+        as display_jod_images, with predict in the place of predict_images and what jod_video accepts: one float32 clip of at
+        least 2 frames, every temporal padding, temporal filters of up to 64 taps.  With a gradient the forward adds the backward
+        batches of jod_video(wrt="both") without its two gradient-writing launches: the clip-long level-0 gradients of both
+        sides are reduced to three sums each by fvvdp_video_display_sums (include/fvvdp_hip_display.h).  psi.grad does not
+        depend on `self.grad_batch`, bit for bit."""
+        from .display_grad import display_jod_video
+        return display_jod_video(self, test, reference, psi, dim_order, frames_per_second, fixation_point)
+
     def predict_image_pairs(self, pairs, dim_order="HWC", sync=True, fixation_points=None):
         """Extension: a list of (test, reference) image pairs of arbitrary sizes and sample types (`dim_order` without B and F,
         or with them of size 1).  The pairs are grouped by (shape, dtypes) and every group is scored in batches by

@@ -105,13 +105,15 @@ class _Buffers:
     """What a backward pass over the clip t allocates, shared by jod_video and jod_gazes (`name`): per differentiated input the
     result and the clip-long level-0 gradient, the head's side buffer, the maps and scratch of a backward batch of gb frames and
     a workspace of `work_bytes` (with `ref_bytes` > 0 the slope planes and the workspace of the reference's backward as well).
-    Checked against the free device memory first: a sentence instead of an out-of-memory error."""
+    Checked against the free device memory first: a sentence instead of an out-of-memory error.  results False: a caller that
+    reduces the level-0 gradients instead of mapping them to the clip (display_grad.py) needs no result tensors."""
 
-    def __init__(self, name, metric, s, t, gb, work_bytes, need_t=True, ref_bytes=0):
+    def __init__(self, name, metric, s, t, gb, work_bytes, need_t=True, ref_bytes=0, results=True):
         N, dev, HW = s.N, metric.device, s.H * s.W
         need_r = ref_bytes > 0
         px = sum(w * h for w, h in metric._level_sizes(s.W, s.H, s.n_bands)[:s.n_bands])
-        need = backward_bytes(gb, px, work_bytes + ref_bytes, N, HW, t.numel(), s.fl, int(need_t) + int(need_r), need_r)
+        need = backward_bytes(gb, px, work_bytes + ref_bytes, N, HW, t.numel() if results else 0, s.fl,
+                              int(need_t) + int(need_r), need_r)
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
         if need > free:
             raise RuntimeError("%s: the backward of this clip needs %.1f GB of device memory (maps and workspace of %d "
@@ -119,11 +121,11 @@ class _Buffers:
                                "metric.grad_batch or a shorter clip" % (name, need / 1e9, gb, free / 1e9))
         self.grad = self.g0 = self.work = self.grad_r = self.g0_r = self.work_r = None
         if need_t:
-            self.grad = torch.empty_like(t)
+            self.grad = torch.empty_like(t) if results else None
             self.g0 = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
             self.work = torch.empty((work_bytes + 3) // 4, dtype=torch.float32, device=dev)
         if need_r:
-            self.grad_r = torch.empty_like(t)
+            self.grad_r = torch.empty_like(t) if results else None
             self.g0_r = torch.empty((N, 2, s.H, s.W), dtype=torch.float32, device=dev)
             self.work_r = torch.empty((ref_bytes + 3) // 4, dtype=torch.float32, device=dev)
             self.slopes, self._slopes = slope_planes(metric, gb, s.W, s.H, s.n_bands)

@@ -12,7 +12,7 @@ BUILD_FLAGS_NOTE = "hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ml
 SRC_PATH = os.path.join(_HERE, "csrc", "fvvdp_hip.hip")
 INCLUDE_DIR = os.path.join(ROOT, "include")
 
-FVVDP_U8, FVVDP_U16, FVVDP_F32 = 0, 1, 2
+FVVDP_U8, FVVDP_U16, FVVDP_F32, FVVDP_F16, FVVDP_BF16 = 0, 1, 2, 3, 4
 FVVDP_EUNSUPPORTED = -5
 EOTF_LUT, EOTF_SRGB, EOTF_GAMMA, EOTF_PQ, EOTF_LINEAR, EOTF_ABSOLUTE, EOTF_NONE = range(7)
 PSNR_SLICES = 256            # FVVDP_PSNR_SLICES
@@ -198,13 +198,25 @@ DISPLAY_SYMBOLS = {
 }
 DISPLAY_SUMS = 3                         # FVVDP_DISPLAY_SUMS
 
+# include/fvvdp_hip_half.h: fvvdp_images_grad, fvvdp_images_ref_grad and fvvdp_video_grad_input with an `int dtype` (FVVDP_F32 /
+# F16 / BF16) for the samples and the gradient, after the sample pointers (bound by lib() as well)
+def _with_dtype(args, at):
+    return args[:at] + [C.c_int] + args[at:]
+
+
+HALF_SYMBOLS = {
+    "fvvdp_images_grad_st": (C.c_int, _with_dtype(GRAD_SYMBOLS["fvvdp_images_grad"][1], 12)),
+    "fvvdp_images_ref_grad_st": (C.c_int, _with_dtype(REF_GRAD_SYMBOLS["fvvdp_images_ref_grad"][1], 13)),
+    "fvvdp_video_grad_input_st": (C.c_int, _with_dtype(VIDEO_GRAD_SYMBOLS["fvvdp_video_grad_input"][1], 10)),
+}
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Thirteen translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Fifteen translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
-    per sample type (temporal_launch.hip with -DK1_PART=0..3), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
+    per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
     (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip) and the sums for the gradient with
@@ -213,7 +225,7 @@ def build(force=False, verbose=False):
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
-                                                                                                                              "fvvdp_hip_display.h")]
+                                                                                                                              "fvvdp_hip_display.h", "fvvdp_hip_half.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -225,7 +237,7 @@ def build(force=False, verbose=False):
     os.makedirs(objdir, exist_ok=True)
     units = [(SRC_PATH, [], os.path.join(objdir, "fvvdp_hip.o"))]
     units += [(os.path.join(csrc, "temporal_launch.hip"), ["-DK1_PART=%d" % k], os.path.join(objdir, "temporal_part%d.o" % k))
-              for k in range(4)]
+              for k in range(6)]
     # the batched still-image ingest: per-pixel arithmetic identical to the single-image kernel (see still_launch.hip)
     units += [(os.path.join(csrc, "still_launch.hip"), ["-fno-slp-vectorize"], os.path.join(objdir, "still_launch.o"))]
     # gradients of the still-image JOD (include/fvvdp_hip_grad.h)
@@ -271,7 +283,7 @@ def lib():
         for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()) + list(GRAD_SYMBOLS.items()) + \
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
-                list(DISPLAY_SYMBOLS.items()):
+                list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -672,13 +672,13 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                                   const float* h_rgb2y, const int32_t* h_frame_idx, const int32_t* h_frame_idx1,
                                   const float* h_taps, int fl, int n_out, int slot0, int32_t* d_oob_flag, void* stream) {
     if (!c || !d_test || !d_ref || !eotf || !h_frame_idx || !h_taps) return fail(FVVDP_EINVAL, "null argument");
-    if (dtype < FVVDP_U8 || dtype > FVVDP_F32) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 is currently supported");
+    if (dtype < FVVDP_U8 || dtype > FVVDP_BF16) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 (and float16, bfloat16 read as float32) is currently supported");
     if (C != 1 && C != 3) return fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (C == 3 && !h_rgb2y) return fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
     if (fl < 1 || fl > FVVDP_MAX_TAPS) return fail(FVVDP_EINVAL, "filter length %d out of range", fl);
     if (c->P == 2 && fl != 1) return fail(FVVDP_EINVAL, "still-image context (planes == 2) needs fl == 1");
     if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n_out, c->max_frames);
-    if (eotf->kind == FVVDP_EOTF_LUT && (dtype == FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
+    if (eotf->kind == FVVDP_EOTF_LUT && (dtype >= FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
     if (eotf->kind != FVVDP_EOTF_LUT && dtype == FVVDP_U8) return fail(FVVDP_EINVAL, "uint8 sources need FVVDP_EOTF_LUT (uint16: table or closed form)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int HW = c->W * c->H;
@@ -722,7 +722,7 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                 }
                 // vector path needs the lane's PX consecutive samples to be naturally aligned
                 const int PXv = k1_px(FL);        // temporal_launch.hpp
-                const int es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
+                const int es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
                 const bool vec_ok = !c->env.temporal_scalar && (HW % PXv == 0) && (HW >= PXv) &&
                                     (chan_stride % PXv == 0) && (frame_stride % PXv == 0) &&
                                     (reinterpret_cast<uintptr_t>(d_test) % (size_t)(es * PXv) == 0) &&
@@ -843,10 +843,10 @@ extern "C" int fvvdp_temporal_channels_frames(fvvdp_ctx* c, const void* const* h
                                               int n_out, int slot0, int32_t* d_oob_flag, void* stream) {
     if (!c || !h_test_frames || !h_ref_frames || !h_frame_idx) return fail(FVVDP_EINVAL, "null argument");
     if (n_frames < 1 || n_frames > 65536) return fail(FVVDP_EINVAL, "n_frames out of range");
-    if (dtype < FVVDP_U8 || dtype > FVVDP_F32) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 is currently supported");
+    if (dtype < FVVDP_U8 || dtype > FVVDP_BF16) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 (and float16, bfloat16 read as float32) is currently supported");
     if (fl < 1 || fl > ((eotf && k1_ring64_ok(dtype, C, eotf->kind)) ? 64 : 32) || c->P != 4)
         return fail(FVVDP_EUNSUPPORTED, "per-frame source pointers: video contexts with fl <= 32 (uint8, float luminance: 64) only");
-    const size_t es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
+    const size_t es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
     // every frame is addressed as base + index * frame_stride with ONE base per stream: base = lowest frame address,
     // frame_stride = the coarsest granule (4 elements, else 1) that divides every distance; indices are 31-bit
     const void* const* fr[2] = {h_test_frames, h_ref_frames};
@@ -2042,16 +2042,16 @@ extern "C" int fvvdp_images_channels(fvvdp_ctx* c, const void* const* h_test_ptr
                                      int slot0, int32_t* d_oob_flags, void* stream) {
     if (!c || !h_test_ptrs || !h_ref_ptrs || !eotf) return fail(FVVDP_EINVAL, "null argument");
     if (c->P != 2) return fail(FVVDP_EINVAL, "fvvdp_images_channels needs a still-image context (planes == 2)");
-    if (dtype < FVVDP_U8 || dtype > FVVDP_F32) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 is currently supported");
+    if (dtype < FVVDP_U8 || dtype > FVVDP_BF16) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 (and float16, bfloat16 read as float32) is currently supported");
     if (C != 1 && C != 3) return fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (C == 3 && !h_rgb2y) return fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
     if (n < 1 || slot0 < 0 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n, c->max_frames);
-    if (eotf->kind == FVVDP_EOTF_LUT && (dtype == FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
+    if (eotf->kind == FVVDP_EOTF_LUT && (dtype >= FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
     if (eotf->kind != FVVDP_EOTF_LUT && dtype == FVVDP_U8) return fail(FVVDP_EINVAL, "uint8 sources need FVVDP_EOTF_LUT (uint16: table or closed form)");
     if (eotf->kind == FVVDP_EOTF_NONE) return fail(FVVDP_EINVAL, "images need a display model (kind != FVVDP_EOTF_NONE)");
     const int HW = c->W * c->H;
     if (C == 3 && chan_stride < (size_t)HW) return fail(FVVDP_EINVAL, "chan_stride %zu is below the image size %d", chan_stride, HW);
-    const size_t es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
+    const size_t es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
     // PX = 4 when every group of four pixels is one naturally aligned load per channel
     bool vec = HW % 4 == 0 && (C == 1 || chan_stride % 4 == 0);
     for (int k = 0; k < n; ++k) {

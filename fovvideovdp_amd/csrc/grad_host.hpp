@@ -80,8 +80,9 @@ hipError_t video_level0_launch(const float* ws, const GradLayout& L, float* d_g0
 // workspace `ws`.  The kernels are defined in grad_launch.hip only, so are these functions
 hipError_t grad_coef_launch(const float* d_Q, int q_stride, int q_col0, const float* d_gamma, float* d_coef, int n, int n_bands,
                             const fvvdp_params* prm, const fvvdp_pool_params* pool, const GradLayout& L, hipStream_t st);
+// dtype: the type of the samples and of the gradient (FVVDP_F32, FVVDP_F16 or FVVDP_BF16; grad_check_sample_type)
 hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const void* const* h_img_ptrs, void* const* h_grad_ptrs,
-                             int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st);
+                             int dtype, int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st);
 
 // fvvdp_images_grad's launches before its last, in a workspace laid out as L (defined in grad_launch.hip, with adj_layer_kernel),
 // and the reference side's counterpart with the size of its workspace in floats (defined in ref_grad_launch.hip, with
@@ -124,6 +125,14 @@ static int grad_check_workspace(const void* d_work, size_t work_bytes, const Gra
 static int grad_check_channels(int C, const float* h_rgb2y) {
     if (C != 1 && C != 3) return grad_fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (C == 3 && !h_rgb2y) return grad_fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
+    return FVVDP_OK;
+}
+
+// the sample types the *_st entry points take; *es receives the bytes per sample
+static int grad_check_sample_type(int dtype, size_t* es) {
+    if (dtype != FVVDP_F32 && dtype != FVVDP_F16 && dtype != FVVDP_BF16)
+        return grad_fail(FVVDP_EINVAL, "gradients are written for float32, float16 and bfloat16 samples (dtype %d)", dtype);
+    *es = dtype == FVVDP_F32 ? 4 : 2;
     return FVVDP_OK;
 }
 

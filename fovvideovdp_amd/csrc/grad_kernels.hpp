@@ -136,7 +136,10 @@ struct GradInputArgs {
     float wgt[3];
 };
 
-__global__ __launch_bounds__(256) void grad_input_kernel(const GradInputArgs a) {
+// ST: the type of the caller's samples and gradient (SRC_F32; SRC_F16 / SRC_BF16: the pointer tables hold 16-bit samples).  The
+// arithmetic is fp32 whatever ST; a 16-bit result is rounded once, to nearest even (float16 subnormals kept).
+template <int ST>
+__device__ __forceinline__ void grad_input_body(const GradInputArgs& a) {
     const int k = blockIdx.y;
     const size_t hw = (size_t)a.w * a.h;
     const size_t px = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -148,6 +151,21 @@ __global__ __launch_bounds__(256) void grad_input_kernel(const GradInputArgs a) 
     float* out = a.grad[k];
     for (int c = 0; c < a.C; ++c) {
         const size_t o = (size_t)c * a.chan_stride + px;
-        out[o] = a.wgt[c] * eotf_grad(V[o], a.e) * g0;
+        if constexpr (ST == SRC_F32) {
+            out[o] = a.wgt[c] * eotf_grad(V[o], a.e) * g0;
+        } else {
+            const float v = half_widen<ST>(reinterpret_cast<const unsigned short*>(V)[o]);
+            reinterpret_cast<unsigned short*>(out)[o] = half_narrow<ST>(a.wgt[c] * eotf_grad(v, a.e) * g0);
+        }
     }
+}
+
+__global__ __launch_bounds__(256) void grad_input_kernel(const GradInputArgs a) {
+    grad_input_body<SRC_F32>(a);
+}
+// float16 / bfloat16 samples and gradient: an entry point of its own on the same body
+template <int ST>
+__global__ __launch_bounds__(256) void grad_input_half_kernel(const GradInputArgs a) {
+    static_assert(src_is_half(ST), "float16 / bfloat16");
+    grad_input_body<ST>(a);
 }

@@ -10,6 +10,7 @@
 
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_grad.h"
+#include "fvvdp_hip_half.h"
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"
 #include "grad_kernels.hpp"
@@ -47,7 +48,7 @@ hipError_t grad_coef_launch(const float* d_Q, int q_stride, int q_col0, const fl
 
 // level 0 of the sweep (ws + L.gl[0], ws + L.gg[1]) and the display model's derivative at the samples `h_img_ptrs`
 hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const void* const* h_img_ptrs, void* const* h_grad_ptrs,
-                             int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st) {
+                             int dtype, int C, size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, hipStream_t st) {
     const size_t HW = (size_t)L.w[0] * L.h[0];
     GradInputArgs ia;
     memset(&ia, 0, sizeof(ia));
@@ -66,7 +67,10 @@ hipError_t grad_input_launch(const float* ws, const GradLayout& L, int n, const 
         }
         ia.GL0 = ws + L.gl[0] + (size_t)k0 * HW;
         ia.GG1 = ws + L.gg[1] + (size_t)k0 * L.w[1] * L.h[1];
-        hipLaunchKernelGGL(grad_input_kernel, dim3((unsigned int)((HW + 255) / 256), nk), dim3(256), 0, st, ia);
+        const dim3 grid((unsigned int)((HW + 255) / 256), nk);
+        if (dtype == FVVDP_F16) hipLaunchKernelGGL(grad_input_half_kernel<SRC_F16>, grid, dim3(256), 0, st, ia);
+        else if (dtype == FVVDP_BF16) hipLaunchKernelGGL(grad_input_half_kernel<SRC_BF16>, grid, dim3(256), 0, st, ia);
+        else hipLaunchKernelGGL(grad_input_kernel, grid, dim3(256), 0, st, ia);
         const hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
@@ -114,9 +118,20 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
                                  const fvvdp_band_maps* maps, const void* const* h_test_ptrs, int C, size_t chan_stride,
                                  const fvvdp_eotf* eotf, const float* h_rgb2y, void* const* h_grad_ptrs, void* d_work,
                                  size_t work_bytes, void* stream) {
+    return fvvdp_images_grad_st(width, height, n_bands, n, prm, pool, d_Q, q_stride, q_col0, d_gamma, maps, h_test_ptrs, FVVDP_F32,
+                                C, chan_stride, eotf, h_rgb2y, h_grad_ptrs, d_work, work_bytes, stream);
+}
+
+extern "C" int fvvdp_images_grad_st(int width, int height, int n_bands, int n, const fvvdp_params* prm,
+                                    const fvvdp_pool_params* pool, const float* d_Q, int q_stride, int q_col0, const float* d_gamma,
+                                    const fvvdp_band_maps* maps, const void* const* h_test_ptrs, int dtype, int C,
+                                    size_t chan_stride, const fvvdp_eotf* eotf, const float* h_rgb2y, void* const* h_grad_ptrs,
+                                    void* d_work, size_t work_bytes, void* stream) {
     if (!prm || !pool || !d_Q || !d_gamma || !maps || !h_test_ptrs || !eotf || !h_grad_ptrs || !d_work)
         return grad_fail(FVVDP_EINVAL, "null argument");
     GRAD_CHECK(check_dims(width, height, n_bands, n));
+    size_t es = 4;
+    GRAD_CHECK(grad_check_sample_type(dtype, &es));
     if (q_col0 < 0 || q_stride < 1 || q_col0 + n > q_stride) return grad_fail(FVVDP_EINVAL, "Q columns out of range");
     GRAD_CHECK(grad_check_channels(C, h_rgb2y));
     const size_t HW = (size_t)width * height;
@@ -126,8 +141,8 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
     GRAD_CHECK(grad_check_maps(maps, n_bands));
     for (int k = 0; k < n; ++k) {
         if (!h_test_ptrs[k] || !h_grad_ptrs[k]) return grad_fail(FVVDP_EINVAL, "null image pointer at pair %d", k);
-        if ((reinterpret_cast<uintptr_t>(h_test_ptrs[k]) | reinterpret_cast<uintptr_t>(h_grad_ptrs[k])) % 4 != 0)
-            return grad_fail(FVVDP_EINVAL, "image pointers must be aligned to 4 bytes (pair %d)", k);
+        if ((reinterpret_cast<uintptr_t>(h_test_ptrs[k]) | reinterpret_cast<uintptr_t>(h_grad_ptrs[k])) % es != 0)
+            return grad_fail(FVVDP_EINVAL, "image pointers must be aligned to %zu bytes (pair %d)", es, k);
     }
     GradLayout L;
     grad_layout(width, height, n_bands, n, 1, L);
@@ -139,6 +154,6 @@ extern "C" int fvvdp_images_grad(int width, int height, int n_bands, int n, cons
     GRAD_CHECK(grad_images_sweep(n_bands, n, prm, pool, d_Q, q_stride, q_col0, d_gamma, maps, ws, L, st));
 
     // 4. level 0 and the display model, 128 pairs per launch (pointer tables in the kernel arguments)
-    GRAD_HIP_TRY(grad_input_launch(ws, L, n, h_test_ptrs, h_grad_ptrs, C, chan_stride, eotf, h_rgb2y, st));
+    GRAD_HIP_TRY(grad_input_launch(ws, L, n, h_test_ptrs, h_grad_ptrs, dtype, C, chan_stride, eotf, h_rgb2y, st));
     return FVVDP_OK;
 }

@@ -11,6 +11,7 @@
 
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_ref_grad.h"
+#include "fvvdp_hip_half.h"
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"
 #include "grad_common.hpp"
@@ -98,9 +99,21 @@ extern "C" int fvvdp_images_ref_grad(int width, int height, int n_bands, int n, 
                                      const void* const* h_ref_ptrs, int C, size_t chan_stride, const fvvdp_eotf* eotf,
                                      const float* h_rgb2y, void* const* h_grad_ptrs, void* d_work, size_t work_bytes,
                                      void* stream) {
+    return fvvdp_images_ref_grad_st(width, height, n_bands, n, prm, pool, d_Q, q_stride, q_col0, d_gamma, maps, h_slope_ptrs,
+                                    h_ref_ptrs, FVVDP_F32, C, chan_stride, eotf, h_rgb2y, h_grad_ptrs, d_work, work_bytes, stream);
+}
+
+extern "C" int fvvdp_images_ref_grad_st(int width, int height, int n_bands, int n, const fvvdp_params* prm,
+                                        const fvvdp_pool_params* pool, const float* d_Q, int q_stride, int q_col0,
+                                        const float* d_gamma, const fvvdp_band_maps* maps, const float* const* h_slope_ptrs,
+                                        const void* const* h_ref_ptrs, int dtype, int C, size_t chan_stride,
+                                        const fvvdp_eotf* eotf, const float* h_rgb2y, void* const* h_grad_ptrs, void* d_work,
+                                        size_t work_bytes, void* stream) {
     if (!prm || !pool || !d_Q || !d_gamma || !maps || !h_ref_ptrs || !eotf || !h_grad_ptrs || !d_work)
         return grad_fail(FVVDP_EINVAL, "null argument");
     GRAD_CHECK(grad_check_dims(width, height, n_bands, n, INT_MAX, INT_MAX, "pairs"));
+    size_t es = 4;
+    GRAD_CHECK(grad_check_sample_type(dtype, &es));
     if (q_col0 < 0 || q_stride < 1 || q_col0 + n > q_stride) return grad_fail(FVVDP_EINVAL, "Q columns out of range");
     GRAD_CHECK(grad_check_channels(C, h_rgb2y));
     const size_t HW = (size_t)width * height;
@@ -111,8 +124,8 @@ extern "C" int fvvdp_images_ref_grad(int width, int height, int n_bands, int n, 
     GRAD_CHECK(check_slopes(h_slope_ptrs, n_bands));
     for (int k = 0; k < n; ++k) {
         if (!h_ref_ptrs[k] || !h_grad_ptrs[k]) return grad_fail(FVVDP_EINVAL, "null image pointer at pair %d", k);
-        if ((reinterpret_cast<uintptr_t>(h_ref_ptrs[k]) | reinterpret_cast<uintptr_t>(h_grad_ptrs[k])) % 4 != 0)
-            return grad_fail(FVVDP_EINVAL, "image pointers must be aligned to 4 bytes (pair %d)", k);
+        if ((reinterpret_cast<uintptr_t>(h_ref_ptrs[k]) | reinterpret_cast<uintptr_t>(h_grad_ptrs[k])) % es != 0)
+            return grad_fail(FVVDP_EINVAL, "image pointers must be aligned to %zu bytes (pair %d)", es, k);
     }
     RefGradLayout R;
     ref_grad_layout(width, height, n_bands, n, 1, R);
@@ -123,7 +136,7 @@ extern "C" int fvvdp_images_ref_grad(int width, int height, int n_bands, int n, 
     GRAD_HIP_TRY(grad_coef_launch(d_Q, q_stride, q_col0, d_gamma, ws + R.L.coef, n, n_bands, prm, pool, R.L, st));
     GRAD_CHECK(ref_layers_and_sweep<1>(maps, h_slope_ptrs, ws, R, n_bands, n, prm, st));
     // level 0 (GLR_0 + Reduce^T(GG_1)) and the display model's derivative at the reference's samples
-    GRAD_HIP_TRY(grad_input_launch(ws, R.L, n, h_ref_ptrs, h_grad_ptrs, C, chan_stride, eotf, h_rgb2y, st));
+    GRAD_HIP_TRY(grad_input_launch(ws, R.L, n, h_ref_ptrs, h_grad_ptrs, dtype, C, chan_stride, eotf, h_rgb2y, st));
     return FVVDP_OK;
 }
 

@@ -29,12 +29,7 @@ struct StillArgs {
 };
 
 template <int SRC, int PX>
-__global__ __launch_bounds__(256) void still_ingest_kernel(const StillArgs a) {
-    __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
-    if constexpr (SRC == SRC_U8) {
-        build_lutw(lutw, a.e, a.C, a.w, threadIdx.x, 256);
-        __syncthreads();
-    }
+__device__ __forceinline__ void still_ingest_body(const StillArgs& a, const float* lutw) {
     const int k = blockIdx.y;
     Sampler<SRC, PX> S[2];
 #pragma unroll
@@ -71,6 +66,22 @@ __global__ __launch_bounds__(256) void still_ingest_kernel(const StillArgs a) {
     }
     // one atomic per wave that saw an out-of-range sample
     if (a.oob && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(a.oob + k, 1);
+}
+
+template <int SRC, int PX>
+__global__ __launch_bounds__(256) void still_ingest_kernel(const StillArgs a) {
+    __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
+    if constexpr (SRC == SRC_U8) {
+        build_lutw(lutw, a.e, a.C, a.w, threadIdx.x, 256);
+        __syncthreads();
+    }
+    still_ingest_body<SRC, PX>(a, lutw);
+}
+// float16 / bfloat16 samples (widened exactly, then the float path): an entry point of its own on the same body
+template <int SRC, int PX>
+__global__ __launch_bounds__(256) void still_ingest_half_kernel(const StillArgs a) {
+    static_assert(src_is_half(SRC), "float16 / bfloat16");
+    still_ingest_body<SRC, PX>(a, nullptr);
 }
 
 // still_launch.hip: the instantiations, in a translation unit of their own (see there); px = 4 or 1

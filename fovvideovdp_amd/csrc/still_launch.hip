@@ -17,7 +17,8 @@ template <int SRC, int PX>
 static void launch(const StillArgs& a, int n, hipStream_t st) {
     const long long per_block = (long long)STILL_ITER * 256 * PX;
     const dim3 grid((unsigned int)((a.HW + per_block - 1) / per_block), (unsigned int)n), block(256);
-    hipLaunchKernelGGL((still_ingest_kernel<SRC, PX>), grid, block, 0, st, a);
+    if constexpr (src_is_half(SRC)) hipLaunchKernelGGL((still_ingest_half_kernel<SRC, PX>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((still_ingest_kernel<SRC, PX>), grid, block, 0, st, a);
 }
 
 // uint16 always runs one pixel per lane: with four, the closed-form display models of RGB input still contract differently from
@@ -29,6 +30,12 @@ void still_launch(int dtype, int px, const StillArgs& a, int n, hipStream_t st) 
         else launch<SRC_U8, 1>(a, n, st);
     } else if (dtype == FVVDP_U16) {
         launch<SRC_U16, 1>(a, n, st);
+    } else if (dtype == FVVDP_F16) {
+        if (px == 4) launch<SRC_F16, 4>(a, n, st);
+        else launch<SRC_F16, 1>(a, n, st);
+    } else if (dtype == FVVDP_BF16) {
+        if (px == 4) launch<SRC_BF16, 4>(a, n, st);
+        else launch<SRC_BF16, 1>(a, n, st);
     } else {
         if (px == 4) launch<SRC_F32, 4>(a, n, st);
         else launch<SRC_F32, 1>(a, n, st);

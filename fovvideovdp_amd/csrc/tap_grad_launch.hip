@@ -42,6 +42,7 @@ extern "C" int fvvdp_luminance_frames(const void* d_test, const void* d_ref, int
                                       size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf, const float* h_rgb2y,
                                       const int32_t* h_frames, int n, float* d_out, int32_t* d_oob_flag, void* stream) {
     if (!d_test || !d_ref || !eotf || !h_frames || !d_out) return tap_fail(FVVDP_EINVAL, "null argument");
+    // (FVVDP_F16 / FVVDP_BF16 are the ingest's and the *_st gradients'; this pass takes such a clip upcast: the caller's side is exact)
     if (dtype < FVVDP_U8 || dtype > FVVDP_F32) return tap_fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 is currently supported");
     if (C != 1 && C != 3) return tap_fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (C == 3 && !h_rgb2y) return tap_fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");

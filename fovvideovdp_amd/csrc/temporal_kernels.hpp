@@ -4,7 +4,28 @@
 // ------------------------------------------------------------------------------------------------------------
 // stage 1: unpack + display photometry + luminance + temporal FIR  ->  pyramid level 0 (interleaved planes)
 // ------------------------------------------------------------------------------------------------------------
-enum { SRC_U8 = 0, SRC_U16 = 1, SRC_F32 = 2 };
+enum { SRC_U8 = 0, SRC_U16 = 1, SRC_F32 = 2, SRC_F16 = 3, SRC_BF16 = 4 };      // = FVVDP_U8 ... FVVDP_BF16
+// float16 / bfloat16 samples: loaded as 16 bits, widened to fp32 exactly, then the code path of SRC_F32 (same display model, same
+// roundings, same out-of-range flag) -- every result equals the float32 path on the upcast input, bit for bit
+constexpr bool src_is_half(int SRC) { return SRC == SRC_F16 || SRC == SRC_BF16; }
+constexpr bool src_is_float(int SRC) { return SRC == SRC_F32 || src_is_half(SRC); }
+template <int SRC>
+__device__ __forceinline__ float half_widen(unsigned int bits16) {      // the low 16 bits hold the sample
+    static_assert(src_is_half(SRC), "float16 / bfloat16");
+    if constexpr (SRC == SRC_BF16) return __uint_as_float(bits16 << 16);                           // a shift
+    else return (float)__builtin_bit_cast(_Float16, (unsigned short)bits16);                       // v_cvt_f32_f16 (subnormals included)
+}
+// fp32 -> the sample type, one rounding to nearest even; float16 subnormals are kept (the fp16 denormal mode of a kernel is IEEE)
+template <int SRC>
+__device__ __forceinline__ unsigned short half_narrow(float v) {
+    static_assert(src_is_half(SRC), "float16 / bfloat16");
+    // The fp32 value is pinned in a register first.  Left alone, the compiler folds the multiply that produced it into the
+    // conversion (v_fma_mixlo_f16: round(a * b + 0) straight to float16): the exact product rounded once, which differs from the
+    // fp32 result rounded to float16 wherever that fp32 result is a tie, and turns -0 into +0.
+    asm volatile("" : "+v"(v));
+    if constexpr (SRC == SRC_BF16) return __builtin_bit_cast(unsigned short, (__bf16)v);
+    else return __builtin_bit_cast(unsigned short, (_Float16)v);
+}
 
 struct EotfDev {
     int kind;
@@ -154,6 +175,21 @@ struct Sampler {
 #pragma unroll
                 for (int i = 0; i < PX; ++i) o[i] = __fmul_rn(lut_entry(lut16, code[i], e), wc);
             }
+        } else if constexpr (src_is_half(SRC)) {
+            const unsigned short* q = reinterpret_cast<const unsigned short*>(p) + off;
+            float V[PX];
+            if constexpr (PX == 4) {
+                const ushort4 t = *reinterpret_cast<const ushort4*>(q);
+                V[0] = half_widen<SRC>(t.x); V[1] = half_widen<SRC>(t.y); V[2] = half_widen<SRC>(t.z); V[3] = half_widen<SRC>(t.w);
+            } else if constexpr (PX == 2) {
+                const ushort2 t = *reinterpret_cast<const ushort2*>(q);
+                V[0] = half_widen<SRC>(t.x); V[1] = half_widen<SRC>(t.y);
+            } else {
+                V[0] = half_widen<SRC>(*q);
+            }
+            const float wc = (c == 0) ? w0 : ((c == 1) ? w1 : w2);
+#pragma unroll
+            for (int i = 0; i < PX; ++i) o[i] = __fmul_rn(eotf_f32(V[i], e, bad), wc);
         } else {
             const float* q = reinterpret_cast<const float*>(p) + off;
             float V[PX];
@@ -238,7 +274,10 @@ template <int SRC, int PX>
 struct RawPx {
     unsigned int wd[PX];
     __device__ __forceinline__ unsigned int code(int i) const { return wd[i]; }              // integer sources
-    __device__ __forceinline__ float value(int i) const { return __uint_as_float(wd[i]); }   // float source
+    __device__ __forceinline__ float value(int i) const {                                    // float sources
+        if constexpr (src_is_half(SRC)) return half_widen<SRC>(wd[i]);
+        else return __uint_as_float(wd[i]);
+    }
 };
 
 template <int SRC, int PX>
@@ -247,7 +286,7 @@ __device__ __forceinline__ RawPx<SRC, PX> load_raw(const void* base, size_t off,
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
         if constexpr (SRC == SRC_U8) r.wd[i] = reinterpret_cast<const unsigned char*>(base)[off + px[i]];
-        else if constexpr (SRC == SRC_U16) r.wd[i] = reinterpret_cast<const unsigned short*>(base)[off + px[i]];
+        else if constexpr (SRC == SRC_U16 || src_is_half(SRC)) r.wd[i] = reinterpret_cast<const unsigned short*>(base)[off + px[i]];
         else r.wd[i] = reinterpret_cast<const unsigned int*>(base)[off + px[i]];
     }
     return r;
@@ -278,7 +317,7 @@ template <int SRC, int PX, typename FRAME, int KIND = -1, typename B = bool>
 __device__ __forceinline__ void frame_lum(const FRAME& f, int C, const float* lutw, const float* lut16,
                                           const float (&w)[3], const EotfDev& e, float (&L)[PX], B& bad) {
     float v[3][PX];
-    if constexpr (SRC == SRC_F32) {
+    if constexpr (src_is_float(SRC)) {
         if (C == 3) {
             float t[3 * PX];
 #pragma unroll
@@ -400,13 +439,13 @@ __device__ __forceinline__ void eotf_pairs_exact(v2f (&V)[N], const EotfDev& e, 
 template <int SRC, int PX, int CC, int KIND, typename FRAME, typename B>
 __device__ __forceinline__ void frame_lum_pairs(const FRAME& f0, const FRAME& f1, const float (&w)[3], const EotfDev& e, v2f (&L)[PX], B& bad) {
 #pragma clang fp contract(off)       // (Lr*w0 + Lg*w1) + Lb*w2 with every product and sum rounded, as frame_lum and video_source.py:206
-    static_assert(SRC == SRC_F32 || SRC == SRC_U16, "closed-form sources");
+    static_assert(src_is_float(SRC) || SRC == SRC_U16, "closed-form sources");
     v2f V[CC * PX];
 #pragma unroll
     for (int c = 0; c < CC; ++c)
 #pragma unroll
         for (int i = 0; i < PX; ++i) {
-            if constexpr (SRC == SRC_F32) {
+            if constexpr (src_is_float(SRC)) {
                 // (the two samples are pinned as scalars: left to itself the compiler interleaves the two loaded register quads into
                 // pairs with vector shuffles that it lowers THROUGH SCRATCH MEMORY -- 112 bytes of stack, 40 scratch accesses per frame)
                 float t0 = f0.ch[c].value(i), t1 = f1.ch[c].value(i);
@@ -415,7 +454,7 @@ __device__ __forceinline__ void frame_lum_pairs(const FRAME& f0, const FRAME& f1
             }
             else V[c * PX + i] = v2f{(float)f0.ch[c].code(i), (float)f1.ch[c].code(i)} * splat(1.0f / 65535.0f);
         }
-    eotf_pairs_exact<CC * PX, KIND, SRC == SRC_F32>(V, e, bad);
+    eotf_pairs_exact<CC * PX, KIND, src_is_float(SRC)>(V, e, bad);
 #pragma unroll
     for (int i = 0; i < PX; ++i) {
         if constexpr (CC == 3) L[i] = (V[i] * splat(w[0]) + V[PX + i] * splat(w[1])) + V[2 * PX + i] * splat(w[2]);
@@ -453,7 +492,7 @@ typedef const vtapf_a4 __attribute__((address_space(4)))* karg_taps_p;
 // Reference: fvvdp.py:294-300 (R[:,2cc+s] = sum_k window[s][k] * F[cc].flip(0)[k]).
 constexpr int TDIST = 1;        // frames of raw samples in flight per thread; 2 and 4 measured slower (VGPRs -> occupancy)
 template <int FL, int PX, int SRC>
-__global__ __launch_bounds__(256) void temporal_ring_kernel(const TemporalArgs a) {
+__device__ __forceinline__ void temporal_ring_body(const TemporalArgs a) {
     __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
     if constexpr (SRC == SRC_U8) {
         build_lutw(lutw, a.e, a.C, a.w, threadIdx.x, 256);
@@ -547,6 +586,17 @@ __global__ __launch_bounds__(256) void temporal_ring_kernel(const TemporalArgs a
     if (is_oob(bad) && a.oob) atomicOr(a.oob, 1);
 }
 
+template <int FL, int PX, int SRC>
+__global__ __launch_bounds__(256) void temporal_ring_kernel(const TemporalArgs a) {
+    temporal_ring_body<FL, PX, SRC>(a);
+}
+// float16 / bfloat16 samples: an entry point of its own on the same body
+template <int FL, int PX, int SRC>
+__global__ __launch_bounds__(256) void temporal_ring_half_kernel(const TemporalArgs a) {
+    static_assert(src_is_half(SRC), "float16 / bfloat16");
+    temporal_ring_body<FL, PX, SRC>(a);
+}
+
 // ---- vector variant of the temporally tiled FIR (the fast path) -------------------------------------------------
 // Single-wave workgroups; a lane owns PX CONSECUTIVE pixels, so one load per channel fetches all of them
 // (4 uint8 = one dword, 4 uint16 = 8 B, 4 fp32 = 16 B: 4x fewer memory instructions than the per-pixel loads of
@@ -555,14 +605,17 @@ __global__ __launch_bounds__(256) void temporal_ring_kernel(const TemporalArgs a
 // aligned strides; other sizes take temporal_ring_kernel.
 template <int SRC, int PX>
 struct RawVec {
-    static constexpr int ES = (SRC == SRC_U8 ? 1 : (SRC == SRC_U16 ? 2 : 4));
+    static constexpr int ES = (SRC == SRC_U8 ? 1 : ((SRC == SRC_U16 || src_is_half(SRC)) ? 2 : 4));
     static constexpr int WORDS = (ES * PX + 3) / 4;
     unsigned int wd[WORDS];
     __device__ __forceinline__ unsigned int code(int i) const {
         if constexpr (SRC == SRC_U8) return (wd[i / 4] >> (8 * (i % 4))) & 0xFFu;
         else return (wd[i / 2] >> (16 * (i % 2))) & 0xFFFFu;
     }
-    __device__ __forceinline__ float value(int i) const { return __uint_as_float(wd[i]); }
+    __device__ __forceinline__ float value(int i) const {
+        if constexpr (src_is_half(SRC)) return half_widen<SRC>(wd[i / 2] >> (16 * (i % 2)));
+        else return __uint_as_float(wd[i]);
+    }
 };
 template <int SRC, int PX>
 struct RawVecFrame {
@@ -661,7 +714,7 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
     // newest frame -> ring slot u.  The pair is pinned where it is produced: the compiler otherwise sinks the channel sums
     // to their first use (many steps later), keeping three table values per pixel alive instead of one luminance.
     // closed-form display models run on (test, reference) pairs (packed instructions; the reference's roundings)
-    constexpr bool PAIRS = (SRC == SRC_F32 || SRC == SRC_U16) && KIND >= 0 && KIND != FVVDP_EOTF_LUT;
+    constexpr bool PAIRS = (src_is_float(SRC) || SRC == SRC_U16) && KIND >= 0 && KIND != FVVDP_EOTF_LUT;
     auto push = [&](const RawVecFrame<SRC, PX>& c0, const RawVecFrame<SRC, PX>& c1, v2f (&slot)[PX]) {
         if constexpr (PAIRS) {
             frame_lum_pairs<SRC, PX, CC, KIND>(c0, c1, w, a.e, slot, bad);
@@ -861,6 +914,40 @@ void temporal_vec_kernel(const TemporalArgs a_byval) {
             case FVVDP_EOTF_LUT:
                 if constexpr (SRC == SRC_U16) temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_LUT>(a, lutw, s_t, block0);
                 break;                               // (a table for a float source is refused by the host side)
+            default: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_NONE>(a, lutw, s_t, block0); break;   // luminances already
+        }
+    }
+}
+
+// float16 / bfloat16 samples: an entry point of its own on the same bodies.  Pixels per lane as for float (k1_px: 8 / 4 / 2 bytes per
+// lane and load), no code-value table, the closed-form display models only; the 64-slot ring for RGB behind sRGB or PQ (k1_ring64_ok).
+template <int FL, int PX, int SRC, int TD = 1>
+__global__ __launch_bounds__(64 * k1_wpb(FL), k1_waves(FL, SRC))
+void temporal_vec_half_kernel(const TemporalArgs a_byval) {
+    static_assert(src_is_half(SRC), "float16 / bfloat16");
+    const TemporalArgs& a = *(const TemporalArgs*)__builtin_amdgcn_kernarg_segment_ptr();      // see temporal_vec_kernel
+    (void)a_byval;
+    static_assert(TD == 1, "one frame of raw samples in flight (temporal_launch.hpp)");
+    constexpr int WPB = k1_wpb(FL);
+    __shared__ float4 s_t_all[WPB][64 * (PX + 1)];  // per wave: one padded row of PX float4 per lane
+    const int wave = WPB > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    float4* const s_t = s_t_all[wave];
+    const int block0 = (int)blockIdx.x * WPB + wave;          // this wave's pixel block
+    if constexpr (WPB > 1) {
+        if (block0 * (64 * PX) >= a.HW) return;
+    }
+    const float* const lutw = nullptr;
+    if constexpr (FL == 64) {
+        if (a.C == 3 && a.e.kind == FVVDP_EOTF_SRGB) temporal_vec_body<FL, PX, SRC, TD, 3, FVVDP_EOTF_SRGB>(a, lutw, s_t, block0);
+        else if (a.C == 3 && a.e.kind == FVVDP_EOTF_PQ) temporal_vec_body<FL, PX, SRC, TD, 3, FVVDP_EOTF_PQ>(a, lutw, s_t, block0);
+    } else {
+        switch (a.e.kind) {
+            case FVVDP_EOTF_SRGB: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_SRGB>(a, lutw, s_t, block0); break;
+            case FVVDP_EOTF_GAMMA: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_GAMMA>(a, lutw, s_t, block0); break;
+            case FVVDP_EOTF_PQ: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_PQ>(a, lutw, s_t, block0); break;
+            case FVVDP_EOTF_LINEAR: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_LINEAR>(a, lutw, s_t, block0); break;
+            case FVVDP_EOTF_ABSOLUTE: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_ABSOLUTE>(a, lutw, s_t, block0); break;
+            case FVVDP_EOTF_LUT: break;              // (a table for a float source is refused by the host side)
             default: temporal_vec_cc<FL, PX, SRC, TD, FVVDP_EOTF_NONE>(a, lutw, s_t, block0); break;   // luminances already
         }
     }

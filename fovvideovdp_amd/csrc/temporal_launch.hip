@@ -10,12 +10,14 @@
 #include "temporal_launch.hpp"
 
 #ifndef K1_PART
-#error "compile with -DK1_PART=0..3"
+#error "compile with -DK1_PART=0..5"
 #endif
 
-#if K1_PART <= 2
-static constexpr int DT = K1_PART;                     // FVVDP_U8 / FVVDP_U16 / FVVDP_F32
-static constexpr int SRC = DT == FVVDP_U8 ? SRC_U8 : (DT == FVVDP_U16 ? SRC_U16 : SRC_F32);
+// parts 0..2: uint8 / uint16 / float32; part 3: planar YUV and the dispatcher; parts 4, 5: float16 / bfloat16
+#if K1_PART != 3
+static constexpr int DT = K1_PART <= 2 ? K1_PART : K1_PART - 1;      // FVVDP_U8 / U16 / F32, FVVDP_F16 / BF16
+static constexpr int SRC = DT == FVVDP_U8 ? SRC_U8 : (DT == FVVDP_U16 ? SRC_U16 : (DT == FVVDP_F32 ? SRC_F32 : (DT == FVVDP_F16 ? SRC_F16 : SRC_BF16)));
+static_assert(SRC == DT, "the kernels' sample types are numbered as the ABI's");
 
 template <int FL>
 static void launch_vec(const TemporalArgs& a, hipStream_t st) {
@@ -24,6 +26,10 @@ static void launch_vec(const TemporalArgs& a, hipStream_t st) {
     constexpr int WPB = k1_wpb(FL);                       // waves per workgroup, one pixel block each
     const int n_blocks = (a.HW + 64 * PX - 1) / (64 * PX);
     dim3 grid((n_blocks + WPB - 1) / WPB), block(64 * WPB);
+    if constexpr (src_is_half(SRC)) {
+        hipLaunchKernelGGL((temporal_vec_half_kernel<FL, PX, SRC, TD>), grid, block, 0, st, a);
+        return;
+    } else {
     if (a.ticket) {          // resident workgroups that take their pixel blocks from a.ticket (uint8, FL <= 16; the caller zeroed it)
         static int resident = 0;
         if (!resident) {
@@ -38,11 +44,13 @@ static void launch_vec(const TemporalArgs& a, hipStream_t st) {
         else { TemporalArgs b = a; b.ticket = nullptr; hipLaunchKernelGGL((temporal_vec_kernel<FL, PX, SRC, TD>), grid, block, 0, st, b); return; }
     }
     hipLaunchKernelGGL((temporal_vec_kernel<FL, PX, SRC, TD>), grid, block, 0, st, a);
+    }
 }
 template <int FL, int PX>
 static void launch_ring(const TemporalArgs& a, hipStream_t st) {
     dim3 grid((a.HW + 256 * PX - 1) / (256 * PX)), block(256);
-    hipLaunchKernelGGL((temporal_ring_kernel<FL, PX, SRC>), grid, block, 0, st, a);
+    if constexpr (src_is_half(SRC)) hipLaunchKernelGGL((temporal_ring_half_kernel<FL, PX, SRC>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((temporal_ring_kernel<FL, PX, SRC>), grid, block, 0, st, a);
 }
 template <int P>
 static void launch_generic(const GenericArgs& a, hipStream_t st) {
@@ -54,8 +62,12 @@ static void launch_generic(const GenericArgs& a, hipStream_t st) {
 #define K1_NAME(f) f##_u8
 #elif K1_PART == 1
 #define K1_NAME(f) f##_u16
-#else
+#elif K1_PART == 2
 #define K1_NAME(f) f##_f32
+#elif K1_PART == 4
+#define K1_NAME(f) f##_f16
+#else
+#define K1_NAME(f) f##_bf16
 #endif
 void K1_NAME(k1_vec)(int FL, const TemporalArgs& a, hipStream_t st) {
     if (FL == 8) launch_vec<8>(a, st);
@@ -92,25 +104,41 @@ void k1_generic_f32(int, const GenericArgs&, hipStream_t);
 void k1_luminance_u8(const LumArgs&, hipStream_t);
 void k1_luminance_u16(const LumArgs&, hipStream_t);
 void k1_luminance_f32(const LumArgs&, hipStream_t);
+void k1_vec_f16(int, const TemporalArgs&, hipStream_t);
+void k1_ring_f16(int, const TemporalArgs&, hipStream_t);
+void k1_generic_f16(int, const GenericArgs&, hipStream_t);
+void k1_luminance_f16(const LumArgs&, hipStream_t);
+void k1_vec_bf16(int, const TemporalArgs&, hipStream_t);
+void k1_ring_bf16(int, const TemporalArgs&, hipStream_t);
+void k1_generic_bf16(int, const GenericArgs&, hipStream_t);
+void k1_luminance_bf16(const LumArgs&, hipStream_t);
 
 void k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st) {
     if (dtype == FVVDP_U8) k1_vec_u8(FL, a, st);
     else if (dtype == FVVDP_U16) k1_vec_u16(FL, a, st);
+    else if (dtype == FVVDP_F16) k1_vec_f16(FL, a, st);
+    else if (dtype == FVVDP_BF16) k1_vec_bf16(FL, a, st);
     else k1_vec_f32(FL, a, st);
 }
 void k1_launch_ring(int FL, int dtype, const TemporalArgs& a, hipStream_t st) {
     if (dtype == FVVDP_U8) k1_ring_u8(FL, a, st);
     else if (dtype == FVVDP_U16) k1_ring_u16(FL, a, st);
+    else if (dtype == FVVDP_F16) k1_ring_f16(FL, a, st);
+    else if (dtype == FVVDP_BF16) k1_ring_bf16(FL, a, st);
     else k1_ring_f32(FL, a, st);
 }
 void k1_launch_luminance(int dtype, const LumArgs& a, hipStream_t st) {
     if (dtype == FVVDP_U8) k1_luminance_u8(a, st);
     else if (dtype == FVVDP_U16) k1_luminance_u16(a, st);
+    else if (dtype == FVVDP_F16) k1_luminance_f16(a, st);
+    else if (dtype == FVVDP_BF16) k1_luminance_bf16(a, st);
     else k1_luminance_f32(a, st);
 }
 void k1_launch_generic(int planes, int dtype, const GenericArgs& a, hipStream_t st) {
     if (dtype == FVVDP_U8) k1_generic_u8(planes, a, st);
     else if (dtype == FVVDP_U16) k1_generic_u16(planes, a, st);
+    else if (dtype == FVVDP_F16) k1_generic_f16(planes, a, st);
+    else if (dtype == FVVDP_BF16) k1_generic_bf16(planes, a, st);
     else k1_generic_f32(planes, a, st);
 }
 

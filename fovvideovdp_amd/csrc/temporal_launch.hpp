@@ -1,5 +1,5 @@
 // Launchers of the stage-1 (temporal) kernels.  The kernels are instantiated in temporal_launch.hip, which is compiled once
-// per sample type (-DK1_PART=0 uint8, 1 uint16, 2 float, 3 planar YUV): the register-ring kernels are fully unrolled per ring
+// per sample type (-DK1_PART=0 uint8, 1 uint16, 2 float, 3 planar YUV and the dispatcher, 4 float16, 5 bfloat16): the register-ring kernels are fully unrolled per ring
 // length, channel count and display model, and one translation unit holding all of them took 4 minutes to compile.
 #pragma once
 #include "temporal_kernels.hpp"
@@ -11,11 +11,11 @@ static constexpr int k1_px(int FL) { return FL == 8 ? 4 : (FL == 64 ? 1 : 2); }
 // what the 64-slot ring (temporal filters of 33-64 taps, 129-256 fps) is instantiated for
 static inline bool k1_ring64_ok(int dtype, int C, int eotf_kind) {
     if (dtype == FVVDP_U8) return true;
-    if (C == 3 && (eotf_kind == FVVDP_EOTF_SRGB || eotf_kind == FVVDP_EOTF_PQ)) return true;      // uint16 (closed form) / float RGB
+    if (C == 3 && (eotf_kind == FVVDP_EOTF_SRGB || eotf_kind == FVVDP_EOTF_PQ)) return true;      // uint16 (closed form) / float, float16, bfloat16 RGB
     return dtype == FVVDP_F32 && C == 1 && eotf_kind == FVVDP_EOTF_NONE;                          // luminance frames
 }
 
-// FL in {8, 16, 32}; dtype FVVDP_U8 / U16 / F32.  FL = 64: see k1_ring64_ok().
+// FL in {8, 16, 32}; dtype FVVDP_U8 / U16 / F32 / F16 / BF16.  FL = 64: see k1_ring64_ok().
 void k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st);     // aligned sizes (see the call site)
 void k1_launch_ring(int FL, int dtype, const TemporalArgs& a, hipStream_t st);    // any size
 void k1_launch_generic(int planes, int dtype, const GenericArgs& a, hipStream_t st);

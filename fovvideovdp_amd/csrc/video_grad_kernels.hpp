@@ -215,10 +215,39 @@ __device__ __forceinline__ void vg_store(float* p, const VgVec<PX>& r) {
     else __builtin_nontemporal_store(r.v[0], p);
 }
 
+// 16-bit forms for float16 / bfloat16 samples (ST = SRC_F16 / SRC_BF16): PX samples are 8 / 4 / 2 bytes, widened exactly on the
+// way in and rounded once (to nearest even, float16 subnormals kept) on the way out; the same non-temporal hints
+template <int PX, int ST>
+__device__ __forceinline__ VgVec<PX> vg_load16(const unsigned short* p) {
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    VgVec<PX> r;
+    if constexpr (PX == 4) {
+        const u2v t = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(p));
+        r.v[0] = half_widen<ST>(t.x); r.v[1] = half_widen<ST>(t.x >> 16); r.v[2] = half_widen<ST>(t.y); r.v[3] = half_widen<ST>(t.y >> 16);
+    } else if constexpr (PX == 2) {
+        const unsigned int t = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(p));
+        r.v[0] = half_widen<ST>(t); r.v[1] = half_widen<ST>(t >> 16);
+    } else {
+        r.v[0] = half_widen<ST>(__builtin_nontemporal_load(p));
+    }
+    return r;
+}
+template <int PX, int ST>
+__device__ __forceinline__ void vg_store16(unsigned short* p, const VgVec<PX>& r) {
+    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+    unsigned int h[PX];
+#pragma unroll
+    for (int i = 0; i < PX; ++i) h[i] = half_narrow<ST>(r.v[i]);
+    if constexpr (PX == 4) __builtin_nontemporal_store(u2v{h[0] | (h[1] << 16), h[2] | (h[3] << 16)}, reinterpret_cast<u2v*>(p));
+    else if constexpr (PX == 2) __builtin_nontemporal_store(h[0] | (h[1] << 16), reinterpret_cast<unsigned int*>(p));
+    else __builtin_nontemporal_store((unsigned short)h[0], p);
+}
+
 // FL: ring slots (fl rounded up to 8 / 16 / 32 / 64).  PX: pixels per lane (4 or 2: HW and the strides are multiples of PX and
-// the pointers PX-float aligned; 1: any size).
-template <int FL, int PX>
-__global__ __launch_bounds__(256) void video_input_kernel(const VideoInputArgs a) {
+// the pointers PX-float aligned; 1: any size).  ST: the type of the caller's samples and gradient (SRC_F32; SRC_F16 / SRC_BF16:
+// `test` and `grad` point at 16-bit samples, PX-sample aligned); g0, head and all arithmetic are fp32 whatever ST.
+template <int FL, int PX, int ST>
+__device__ __forceinline__ void video_input_body(const VideoInputArgs a) {
     const size_t px = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
     if (px >= (size_t)a.HW) return;
     // fold list and (long rings) taps straight from the kernel-argument segment: scalar loads, no copy of the block to scratch
@@ -247,10 +276,13 @@ __global__ __launch_bounds__(256) void video_input_kernel(const VideoInputArgs a
         }
         VgVec<PX> V[3];                         // the test samples of frame j, requested before the arithmetic
         if (j >= 0) {
-            const float* t = a.test + (size_t)j * a.frame_stride + px;
+            const size_t t = (size_t)j * a.frame_stride + px;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                if (c < a.C) V[c] = vg_load<PX>(t + (size_t)c * a.chan_stride);
+                if (c < a.C) {
+                    if constexpr (ST == SRC_F32) V[c] = vg_load<PX>(a.test + t + (size_t)c * a.chan_stride);
+                    else V[c] = vg_load16<PX, ST>(reinterpret_cast<const unsigned short*>(a.test) + t + (size_t)c * a.chan_stride);
+                }
         }
         // taps: long rings re-read them in every step, TAPC at a time through a laundered pointer -- hoisted out of the loop,
         // 2 FL scalar values would stay alive and spill (see temporal_ring_kernel)
@@ -293,16 +325,28 @@ __global__ __launch_bounds__(256) void video_input_kernel(const VideoInputArgs a
 #pragma unroll
                 for (int i = 0; i < PX; ++i) s.v[i] += done.v[i];
             }
-            float* o = a.grad + (size_t)j * a.frame_stride + px;
+            const size_t o = (size_t)j * a.frame_stride + px;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 if (c < a.C) {
                     VgVec<PX> r;
 #pragma unroll
                     for (int i = 0; i < PX; ++i) r.v[i] = a.wgt[c] * eotf_grad(V[c].v[i], a.e) * s.v[i];
-                    vg_store<PX>(o + (size_t)c * a.chan_stride, r);
+                    if constexpr (ST == SRC_F32) vg_store<PX>(a.grad + o + (size_t)c * a.chan_stride, r);
+                    else vg_store16<PX, ST>(reinterpret_cast<unsigned short*>(a.grad) + o + (size_t)c * a.chan_stride, r);
                 }
             }
         }
     }
+}
+
+template <int FL, int PX>
+__global__ __launch_bounds__(256) void video_input_kernel(const VideoInputArgs a) {
+    video_input_body<FL, PX, SRC_F32>(a);
+}
+// float16 / bfloat16 samples and gradient: an entry point of its own on the same body
+template <int FL, int PX, int ST>
+__global__ __launch_bounds__(256) void video_input_half_kernel(const VideoInputArgs a) {
+    static_assert(src_is_half(ST), "float16 / bfloat16");
+    video_input_body<FL, PX, ST>(a);
 }

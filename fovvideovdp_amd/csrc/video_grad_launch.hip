@@ -9,6 +9,7 @@
 
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_video_grad.h"
+#include "fvvdp_hip_half.h"
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"
 #include "grad_common.hpp"
@@ -117,14 +118,45 @@ static void launch_input(const VideoInputArgs& ia, bool vec, hipStream_t st) {
         hipLaunchKernelGGL((video_input_kernel<FL, 1>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
     }
 }
+// float16 / bfloat16 samples and gradient: the same grids, the same pixels per lane
+template <int FL, int ST>
+static void launch_input_half(const VideoInputArgs& ia, bool vec, hipStream_t st) {
+    constexpr int PXV = FL <= 16 ? 4 : 2;
+    const size_t HW = (size_t)ia.HW;
+    if (vec) {
+        const unsigned int blocks = (unsigned int)((HW / PXV + 255) / 256);
+        hipLaunchKernelGGL((video_input_half_kernel<FL, PXV, ST>), dim3(blocks), dim3(256), 0, st, ia);
+    } else {
+        hipLaunchKernelGGL((video_input_half_kernel<FL, 1, ST>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
+    }
+}
+template <int ST>
+static void launch_input_half(int FL, const VideoInputArgs& ia, bool vec, hipStream_t st) {
+    switch (FL) {
+        case 8: launch_input_half<8, ST>(ia, vec, st); break;
+        case 16: launch_input_half<16, ST>(ia, vec, st); break;
+        case 32: launch_input_half<32, ST>(ia, vec, st); break;
+        default: launch_input_half<64, ST>(ia, vec, st); break;
+    }
+}
 
 extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const float* d_g0, const int32_t* h_fold_frame,
                                       const int32_t* h_fold_pos, const float* h_taps, int fl, const float* d_test, float* d_grad,
                                       int C, size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf,
                                       const float* h_rgb2y, float* d_head, size_t head_bytes, void* stream) {
+    return fvvdp_video_grad_input_st(width, height, n_frames, d_g0, h_fold_frame, h_fold_pos, h_taps, fl, d_test, d_grad, FVVDP_F32,
+                                     C, chan_stride, frame_stride, eotf, h_rgb2y, d_head, head_bytes, stream);
+}
+
+extern "C" int fvvdp_video_grad_input_st(int width, int height, int n_frames, const float* d_g0, const int32_t* h_fold_frame,
+                                         const int32_t* h_fold_pos, const float* h_taps, int fl, const void* d_test, void* d_grad,
+                                         int dtype, int C, size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf,
+                                         const float* h_rgb2y, float* d_head, size_t head_bytes, void* stream) {
     if (!d_g0 || !h_fold_frame || !h_fold_pos || !h_taps || !d_test || !d_grad || !eotf || !d_head)
         return grad_fail(FVVDP_EINVAL, "null argument");
     if (width < 1 || height < 1 || n_frames < 1) return grad_fail(FVVDP_EINVAL, "bad shape %dx%d, %d frames", width, height, n_frames);
+    size_t es = 4;
+    GRAD_CHECK(grad_check_sample_type(dtype, &es));
     const size_t HW = (size_t)width * height;
     if (HW > 0x7FFFFFFFu) return grad_fail(FVVDP_EINVAL, "frame of %zu pixels is too large", HW);
     if (fl < 1 || fl > FVVDP_MAX_TAPS) return grad_fail(FVVDP_EINVAL, "filter length %d outside [1, %d]", fl, FVVDP_MAX_TAPS);
@@ -147,16 +179,19 @@ extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const
     }
     if (head_bytes < (size_t)fl * HW * sizeof(float))
         return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
-    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_test) |
-                           reinterpret_cast<uintptr_t>(d_grad) | reinterpret_cast<uintptr_t>(d_head);
-    if (ptrs % 4 != 0) return grad_fail(FVVDP_EINVAL, "device pointers must be aligned to 4 bytes");
+    // fp32 buffers of the backward, and the caller's samples and gradient (es bytes per sample)
+    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_head);
+    const uintptr_t sptrs = reinterpret_cast<uintptr_t>(d_test) | reinterpret_cast<uintptr_t>(d_grad);
+    if (ptrs % 4 != 0 || sptrs % es != 0)
+        return grad_fail(FVVDP_EINVAL, es == 4 ? "device pointers must be aligned to 4 bytes"
+                                               : "device pointers must be aligned to 4 bytes (16-bit samples and gradient: 2 bytes)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     VideoInputArgs ia;
     memset(&ia, 0, sizeof(ia));
     ia.g0 = d_g0;
-    ia.test = d_test;
-    ia.grad = d_grad;
+    ia.test = static_cast<const float*>(d_test);       // (16-bit samples: the kernel reads and writes them as such)
+    ia.grad = static_cast<float*>(d_grad);
     ia.head = d_head;
     ia.chan_stride = C == 3 ? chan_stride : 0;
     ia.frame_stride = frame_stride;
@@ -175,8 +210,11 @@ extern "C" int fvvdp_video_grad_input(int width, int height, int n_frames, const
     }
     const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : (fl <= 32 ? 32 : 64));
     const size_t pxv = FL <= 16 ? 4 : 2;
-    const bool vec = HW % pxv == 0 && frame_stride % pxv == 0 && ia.chan_stride % pxv == 0 && ptrs % (4 * pxv) == 0;
-    switch (FL) {
+    const bool vec = HW % pxv == 0 && frame_stride % pxv == 0 && ia.chan_stride % pxv == 0 && ptrs % (4 * pxv) == 0 &&
+                     sptrs % (es * pxv) == 0;
+    if (dtype == FVVDP_F16) launch_input_half<SRC_F16>(FL, ia, vec, st);
+    else if (dtype == FVVDP_BF16) launch_input_half<SRC_BF16>(FL, ia, vec, st);
+    else switch (FL) {
         case 8: launch_input<8>(ia, vec, st); break;
         case 16: launch_input<16>(ia, vec, st); break;
         case 32: launch_input<32>(ia, vec, st); break;

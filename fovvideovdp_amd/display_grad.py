@@ -268,7 +268,8 @@ def _need_float(name, test, reference):
     t, r = fvvdp_video_source_array._as_tensor(test), fvvdp_video_source_array._as_tensor(reference)
     if t.dtype != torch.float32 or r.dtype != torch.float32:
         raise RuntimeError("%s needs float32 test and reference (got %s and %s): convert integer sources to float32 in [0, 1] -- "
-                           "the integer path is a table of code values, not a closed form in the display's parameters"
+                           "the integer path is a table of code values, not a closed form in the display's parameters -- and "
+                           "float16 / bfloat16 sources with .float(): the reductions over the samples read float32"
                            % (name, t.dtype, r.dtype))
     return t, r
 

@@ -108,6 +108,27 @@ def _refuse_grad(a):
                            "fvvdp.jod_images; differentiable clips: fvvdp.jod_video)")
 
 
+def _sample_type(dt):
+    """torch dtype of the source samples -> (sample type code of the native ingest, bits of an integer code or 0).  float16 and
+    bfloat16 samples are read as they are (2 bytes each) and widened exactly in the kernels: every result equals the float32
+    path on the upcast input, bit for bit."""
+    if dt is torch.uint8:
+        return nat.FVVDP_U8, 8
+    if dt is torch.int16:
+        return nat.FVVDP_U16, 16
+    if dt is torch.float32:
+        return nat.FVVDP_F32, 0
+    if dt is torch.float16:
+        return nat.FVVDP_F16, 0
+    if dt is torch.bfloat16:
+        return nat.FVVDP_BF16, 0
+    raise RuntimeError("Only uint8, uint16 and float32 is currently supported")
+
+
+def _is_float_type(dtype):
+    return dtype in (nat.FVVDP_F32, nat.FVVDP_F16, nat.FVVDP_BF16)
+
+
 def _image_stack(test, reference, dim_order):
     """Stacked image pairs in `dim_order` (a B axis; F absent or of size 1) -> (test, reference) tensors [B, C, H, W] (views
     where possible; numpy uint16 carried as int16 like fvvdp_video_source_array)."""
@@ -321,8 +342,8 @@ class fvvdp:
         """Extension: the JOD of B still-image pairs as a differentiable [B] fp32 tensor on the metric's device, for losses
         such as `10 - metric.jod_images(x, ref)`.  Values are bit-identical to predict_images(test.detach(), reference, ...)[0].
         When `test` requires grad (and grad mode is on), backward() puts dJOD_k/dtest_k into `test`, whatever its layout or
-        device; the reference is a constant (a reference that requires grad is refused).  float32 samples only, behind a
-        display model with a closed form (sRGB, gamma, PQ, linear, absolute); samples the display model clamps (outside
+        device; the reference is a constant (a reference that requires grad is refused).  float32, float16 or bfloat16 samples
+        (see below), behind a display model with a closed form (sRGB, gamma, PQ, linear, absolute); samples the display model clamps (outside
         [0, 1], or beyond a luminance clip) get a zero gradient.  Foveated metrics take `fixation_point` as predict_images.
         Nothing is synchronised with the host (a user geometry model's gaze conversion aside): the out-of-range warning of predict_images is not issued and no heat maps are
         made, whatever `heatmap` the metric was built with.  Double backward is not supported.  The backward re-runs the
@@ -332,7 +353,17 @@ class fvvdp:
         grad is refused.  "both": one backward delivers both gradients to whichever of the two inputs require grad, from one
         re-ingest and one map-writing pass; the test gradient is bit-identical to wrt="test".  Anything else: ValueError.  The
         reference gradient covers its own band contrast, its role as the adaptation luminance L_bkg and, through L_bkg, the
-        CSF look-up (the slope of the LUT's interpolation); reference samples the display model clamps get zeros."""
+        CSF look-up (the slope of the LUT's interpolation); reference samples the display model clamps get zeros.
+        Half precision: `test` and `reference` may both be float16 or both bfloat16 (what a network under torch.autocast
+        emits).  The kernels read the 2-byte samples as they are and widen them exactly, so the JOD (fp32) equals the float32
+        path on the upcast input bit for bit; the half tensors are what is saved for backward; and the gradient comes back in
+        the dtype of the input -- the float32 gradient rounded once, to nearest even -- so it reaches a half-precision leaf or an
+        autocast graph without a cast.  A mixed pair (a half test with a float32 reference, or the reverse): the narrower side
+        is upcast with torch's .float() inside autograd's view, the float32 kernels run, and the gradient arrives in the
+        caller's dtype through torch's own cast node.  float16 gradients of a JOD are small (most of them below the smallest
+        normal float16, 6.1e-5, for a large image): scale the loss as torch.amp.GradScaler does -- the incoming grad_output
+        multiplies in fp32 before the one rounding, so the scale is not lost.  bfloat16 has float32's exponent range and needs
+        no scaling.  float64 is refused."""
         from .image_grad import jod_images
         return jod_images(self, test, reference, dim_order, fixation_point, wrt)
 
@@ -341,8 +372,8 @@ class fvvdp:
         `10 - metric.jod_video(x, ref, frames_per_second=30)`.  The value is bit-identical to
         predict(test.detach(), reference, dim_order, frames_per_second, fixation_point)[0].  When `test` requires grad (and grad
         mode is on), backward() puts dJOD/dtest into `test`, whatever its layout or device; the reference is a constant (a
-        reference that requires grad is refused).  float32 samples behind a display model with a closed form (sRGB, gamma, PQ,
-        linear, absolute), C = 1 or 3, one clip (B = 1) of at least 2 frames (a single frame: jod_images), every temporal
+        reference that requires grad is refused).  float32, float16 or bfloat16 samples (half precision and mixed pairs: as
+        jod_images describes them) behind a display model with a closed form (sRGB, gamma, PQ, linear, absolute), C = 1 or 3, one clip (B = 1) of at least 2 frames (a single frame: jod_images), every temporal
         padding, frame rates of up to 256 per second (a temporal filter of up to 64 taps), foveated or not (`fixation_point`
         as predict takes it).  Samples the display model clamps get a zero gradient, and so does a frame that no temporal
         window shows (`circular` padding of a clip more than one frame longer than the filter: frame 0).  Nothing is
@@ -365,7 +396,7 @@ class fvvdp:
         predict(test, reference, dim_order, frames_per_second, fixation_point=fixation_points[g]) on this metric, whatever
         the other gazes are: the temporal channels are made once per batch of frames and the pyramid pass evaluates what
         does not depend on the gaze once per group of up to 8 gazes (include/fvvdp_hip_gaze.h).  Every source predict
-        accepts (uint8 / uint16 / float32, C = 1 or 3, a single frame, batch_frames shorter than the clip).  Refused: a metric
+        accepts (uint8 / uint16 / float32 / float16 / bfloat16, C = 1 or 3, a single frame, batch_frames shorter than the clip).  Refused: a metric
         that is not foveated or makes heat maps, a user display_geometry class, inputs that require grad.  A band whose slice
         of the CSF table does not fit the LDS (every band of standard_hmd or htc_vive_pro, band 0 of a 2160-row frame on
         sdr_4k_30) runs the single-gaze kernel once per gaze: same results, only the temporal channels are shared."""
@@ -382,7 +413,8 @@ class fvvdp:
         depend on the gaze -- the ingest, the map-writing pyramid pass, the coarse-to-fine sweep, level 0 and the temporal
         transpose run once per backward batch or clip, only the pooling coefficients and the pointwise layer gradient once
         per gaze (include/fvvdp_hip_gaze_grad.h) -- and its memory does not grow with G.  Accepted: what jod_video accepts
-        (float32 samples, C = 1 or 3, one clip of at least 2 frames, closed-form display models, every temporal padding,
+        (float32, float16 or bfloat16 samples -- half precision and mixed pairs as jod_images describes them, the gradient in
+        the dtype of `test` --, C = 1 or 3, one clip of at least 2 frames, closed-form display models, every temporal padding,
         filters of up to 64 taps).  Refused: what predict_gazes refuses (a metric that is not foveated or makes heat maps,
         a user display_geometry class).  Nothing is synchronised with the host: no out-of-range warning.  Double backward
         is not supported.  The gradient does not depend on `self.grad_batch` nor on the grouping of the gazes, bit for bit."""
@@ -545,19 +577,12 @@ class fvvdp:
     def _image_eotf(self, dt):
         """(sample type code, fvvdp_eotf) of the display model for samples of torch dtype `dt` (the choice _make_feeder makes
         for a still image)."""
-        if dt is torch.uint8:
-            dtype, nbits = nat.FVVDP_U8, 8
-        elif dt is torch.int16:
-            dtype, nbits = nat.FVVDP_U16, 16
-        elif dt is torch.float32:
-            dtype, nbits = nat.FVVDP_F32, 0
-        else:
-            raise RuntimeError("Only uint8, uint16 and float32 is currently supported")
-        use_closed = dtype == nat.FVVDP_F32 or (dtype == nat.FVVDP_U16 and not getattr(self, "exact_uint16", False))
+        dtype, nbits = _sample_type(dt)
+        use_closed = _is_float_type(dtype) or (dtype == nat.FVVDP_U16 and not getattr(self, "exact_uint16", False))
         desc = native_eotf(self.display_photometry) if use_closed else None
         e = nat.Eotf()
         if desc is None:
-            if dtype == nat.FVVDP_F32:
+            if _is_float_type(dtype):
                 raise RuntimeError("predict_images needs a display model with a closed form for float input "
                                    "(a user photometry class works with predict())")
             lut = self._code_lut(self.display_photometry, nbits)
@@ -595,7 +620,7 @@ class fvvdp:
             placed.append(a.contiguous())
         td, rd = placed[:B], placed[B:]
         dtype, e = self._image_eotf(td[0].dtype)
-        if e.kind == nat.EOTF_ABSOLUTE and dtype == nat.FVVDP_F32:
+        if e.kind == nat.EOTF_ABSOLUTE and _is_float_type(dtype):
             lo = torch.stack([torch.maximum(a.max(), b.max()) for a, b in zip(td, rd)]).max()
             if float(lo) < 1:
                 logging.warning('Pixel values are very low. Perhaps images are not scaled in the absolute units of cd/m^2.')
@@ -1138,6 +1163,8 @@ class fvvdp:
         a = a.to(self.device)
         if a.dtype is torch.float32:
             return a
+        if a.dtype is torch.float16 or a.dtype is torch.bfloat16:
+            return a.to(torch.float32)          # exact
         if a.dtype is torch.uint8:
             return a.to(torch.float32) / 255
         if a.dtype is torch.int16:
@@ -1184,15 +1211,7 @@ class fvvdp:
                 # the reference unpacks each array by its own dtype (video_source.py:186-200): bring both to
                 # normalised fp32 code values on the device, then the common float path applies
                 test, ref = self._to_unit_float(test), self._to_unit_float(ref)
-            dt = test.dtype
-            if dt is torch.uint8:
-                dtype, nbits = nat.FVVDP_U8, 8
-            elif dt is torch.int16:
-                dtype, nbits = nat.FVVDP_U16, 16
-            elif dt is torch.float32:
-                dtype, nbits = nat.FVVDP_F32, 0
-            else:
-                raise RuntimeError("Only uint8, uint16 and float32 is currently supported")
+            dtype, nbits = _sample_type(test.dtype)
             C_ch = test.shape[1]
             if need is None:
                 need = np.arange(test.shape[2])
@@ -1200,9 +1219,9 @@ class fvvdp:
             # table sits in global memory (6 gathers per pixel: K1 98 vs 37 us/frame at 4K), so stock display models are
             # evaluated in closed form on code/65535 like float input (<= 1e-6 relative); `exact_uint16 = True` on the
             # metric, or a user photometry class, keeps the table.
-            use_closed = dtype == nat.FVVDP_F32 or (dtype == nat.FVVDP_U16 and not getattr(self, "exact_uint16", False))
+            use_closed = _is_float_type(dtype) or (dtype == nat.FVVDP_U16 and not getattr(self, "exact_uint16", False))
             desc = native_eotf(vs.dm_photometry) if use_closed else None
-            if dtype != nat.FVVDP_F32 or desc is not None:
+            if not _is_float_type(dtype) or desc is not None:
                 test_d, ref_d, remap = self._place_sources(test, ref, need)
                 N = test_d.shape[2]
                 e = nat.Eotf()
@@ -1218,7 +1237,7 @@ class fvvdp:
                     e.L_min = desc[1].get("L_min", 0.0)
                     e.L_max = desc[1].get("L_max", 0.0)
                     # (on the source arrays, not the uploaded subset: a frame-sharded call warns like the unsharded one)
-                    if e.kind == nat.EOTF_ABSOLUTE and dtype == nat.FVVDP_F32 and float(torch.maximum(test.max(), ref.max())) < 1:
+                    if e.kind == nat.EOTF_ABSOLUTE and _is_float_type(dtype) and float(torch.maximum(test.max(), ref.max())) < 1:
                         logging.warning('Pixel values are very low. Perhaps images are not scaled in the absolute units of cd/m^2.')
                 w = np.asarray(vs.color_to_luminance, dtype=np.float32)
 
@@ -1230,14 +1249,22 @@ class fvvdp:
                         N * HW, HW, C.byref(e), nat.fptr(w), idx.ctypes.data_as(C.POINTER(C.c_int32)),
                         nat.fptr(taps), fl, n_out, slot0, C.c_void_p(oob.data_ptr()), stream))
 
+                upcast = []          # float16 / bfloat16 clips as float32, made on the first luminance() call
+
                 def luminance(frames, out, oob, stream):
                     """fp32 luminance of the source frames `frames` (int32 array) of both clips into out [2, len, H, W]: the
-                    values feed's temporal kernel filters (fvvdp_luminance_frames)."""
+                    values feed's temporal kernel filters (fvvdp_luminance_frames).  That entry point takes uint8, uint16 and
+                    float32: a half-precision clip goes in upcast (exact, so the values are still the ones feed filters)."""
                     if remap is not None:
                         frames = remap[frames]
                     frames = np.ascontiguousarray(frames, dtype=np.int32)
+                    lt, lr, ldtype = test_d, ref_d, dtype
+                    if dtype in (nat.FVVDP_F16, nat.FVVDP_BF16):
+                        if not upcast:
+                            upcast.extend([test_d.float(), ref_d.float()])
+                        lt, lr, ldtype = upcast[0], upcast[1], nat.FVVDP_F32
                     nat.check(lib.fvvdp_luminance_frames(
-                        C.c_void_p(test_d.data_ptr()), C.c_void_p(ref_d.data_ptr()), dtype, C_ch, width, height, N * HW, HW,
+                        C.c_void_p(lt.data_ptr()), C.c_void_p(lr.data_ptr()), ldtype, C_ch, width, height, N * HW, HW,
                         C.byref(e), nat.fptr(w), frames.ctypes.data_as(C.POINTER(C.c_int32)), len(frames),
                         C.c_void_p(out.data_ptr()), C.c_void_p(oob.data_ptr()), stream))
                 feed.luminance = luminance

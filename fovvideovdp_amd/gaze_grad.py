@@ -102,7 +102,7 @@ def _backward(metric, t, r, fps, gaze, fix0, Q, gamma):
 
 
 class JodGazesFunction(torch.autograd.Function):
-    """test [1, C, N, H, W] (contiguous fp32 on the metric's device), reference (the same, constant), gaze [G, N, 2] (device)
+    """test [1, C, N, H, W] (contiguous float32, float16 or bfloat16 on the metric's device), reference (the same, constant), gaze [G, N, 2] (device)
     -> JOD [G]."""
 
     @staticmethod

@@ -56,7 +56,7 @@ class _Setup:
     def __init__(self, metric, t):
         self.B, self.C, self.H, self.W = t.shape
         self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, self.e = metric._image_eotf(torch.float32)
+        self.dtype, self.e = metric._image_eotf(t.dtype)          # float32, float16 or bfloat16 (float_pair)
         self.w = metric._rgb2y()
         self.batch = metric._batch_size(self.W, self.H, 2, self.B)
         self.ctx = metric._context(self.W, self.H, self.n_bands, 2, self.batch, self.rho_band)
@@ -135,21 +135,23 @@ def _backward(metric, t, r, fix, Q, gamma, need_t=True, need_r=False):
                 nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, None))
         if need_t:
             gp = (C.c_void_p * nb)(*[grad_t[k].data_ptr() for k in range(b0, b0 + nb)])
-            nat.check(lib.fvvdp_images_grad(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B, b0,
-                                            C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, tp, s.C, s.H * s.W, C.byref(s.e),
-                                            nat.fptr(s.w), gp, C.c_void_p(work.data_ptr()), nbytes.value, s.stream))
+            nat.check(lib.fvvdp_images_grad_st(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B, b0,
+                                               C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, tp, s.dtype, s.C, s.H * s.W,
+                                               C.byref(s.e), nat.fptr(s.w), gp, C.c_void_p(work.data_ptr()), nbytes.value,
+                                               s.stream))
         if need_r:
             rp = (C.c_void_p * nb)(*[r[k].data_ptr() for k in range(b0, b0 + nb)])
             gp = (C.c_void_p * nb)(*[grad_r[k].data_ptr() for k in range(b0, b0 + nb)])
-            nat.check(lib.fvvdp_images_ref_grad(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), B,
-                                                b0, C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, slopes, rp, s.C, s.H * s.W,
-                                                C.byref(s.e), nat.fptr(s.w), gp, C.c_void_p(rwork.data_ptr()), rbytes.value,
-                                                s.stream))
+            nat.check(lib.fvvdp_images_ref_grad_st(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()),
+                                                   B, b0, C.c_void_p(gamma.data_ptr() + 4 * b0), maps_arr, slopes, rp, s.dtype,
+                                                   s.C, s.H * s.W, C.byref(s.e), nat.fptr(s.w), gp,
+                                                   C.c_void_p(rwork.data_ptr()), rbytes.value, s.stream))
     return grad_t, grad_r
 
 
 class JodImagesFunction(torch.autograd.Function):
-    """test, reference [B, C, H, W] (contiguous fp32 on the metric's device) -> JOD [B].  place() detaches the input that
+    """test, reference [B, C, H, W] (contiguous, of one dtype -- float32, float16 or bfloat16 -- on the metric's device) -> JOD [B]
+    (fp32).  The tensors saved for backward are the inputs as they came, and each gradient has its input's dtype.  place() detaches the input that
     `wrt` treats as a constant, so needs_input_grad names the gradients to make."""
 
     @staticmethod
@@ -187,9 +189,21 @@ def refuse_unsupported(name, metric, test, reference, wrt="test"):
                            "absolute); a user photometry class has none" % name)
 
 
-def need_float32(name, what, t, r):
-    if t.dtype != torch.float32 or r.dtype != torch.float32:
-        raise RuntimeError("%s needs float32 test and reference %s (got %s and %s)" % (name, what, t.dtype, r.dtype))
+FLOAT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def float_pair(name, what, t, r):
+    """Test and reference of jod_images / jod_video / jod_gazes (`name`) with one dtype the kernels read: float32, float16 or
+    bfloat16.  A pair of two equal dtypes passes as it is: the half-precision kernels ingest it, and the gradient is written in
+    that dtype.  A mixed pair (say a float16 test from a network under autocast with a float32 reference from a dataset): the
+    narrower side is upcast with torch's .float(), inside autograd's view -- the float32 kernels run and the gradient reaches the
+    caller's tensor in its own dtype through torch's cast node."""
+    if t.dtype not in FLOAT_DTYPES or r.dtype not in FLOAT_DTYPES:
+        raise RuntimeError("%s needs float32, float16 or bfloat16 test and reference %s (got %s and %s)"
+                           % (name, what, t.dtype, r.dtype))
+    if t.dtype != r.dtype:
+        t, r = t.float(), r.float()
+    return t, r
 
 
 def place(metric, t, r, wrt="test"):
@@ -208,7 +222,7 @@ def jod_images(metric, test, reference, dim_order="BCHW", fixation_point=None, w
     check_wrt(wrt)
     refuse_unsupported("jod_images", metric, test, reference, wrt)
     t, r = _image_stack(test, reference, dim_order)
-    need_float32("jod_images", "images", t, r)
+    t, r = float_pair("jod_images", "images", t, r)
     t, r = place(metric, t, r, wrt)
     fix = None
     if metric.foveated:

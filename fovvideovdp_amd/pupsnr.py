@@ -67,6 +67,11 @@ class pu_psnr:
 
     def predict_video_source(self, vid_source, fixation_point=None, frame_padding="replicate"):
         """Returns (PU21-PSNR in dB as a 0-d tensor, None) like the reference (pupsnr.py:52-76)."""
+        if isinstance(vid_source, fvvdp_video_source_array):
+            for a in (vid_source.test_video, vid_source.reference_video):
+                if a.dtype in (torch.float16, torch.bfloat16):       # (the half-precision ingest is the metric's: fvvdp.predict)
+                    raise RuntimeError("pu_psnr takes uint8, uint16 and float32 sources, not %s: convert with .float() first"
+                                       % a.dtype)
         height, width, N = vid_source.get_video_size()
         HW = height * width
         sse = torch.empty(N, dtype=torch.float64, device=self.device)

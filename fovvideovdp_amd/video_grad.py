@@ -16,7 +16,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .fvvdp import filter_length, window_frame_indices      # filter_length: imported from here by tools
-from .image_grad import check_wrt, grad_batch_size, grad_planes, need_float32, place, refuse_unsupported, slope_planes
+from .image_grad import check_wrt, float_pair, grad_batch_size, grad_planes, place, refuse_unsupported, slope_planes
 from .video_source import fvvdp_video_source_array, reshuffle_dims
 
 # fp32 planes per pyramid pixel and frame: maps (D 2 + contrast 4 + L_bkg 1 + S 2) and workspace (layer + sweep gradients of
@@ -61,7 +61,7 @@ class _Setup:
     def __init__(self, metric, t, fps):
         _, self.C, self.N, self.H, self.W = t.shape
         self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, self.e = metric._image_eotf(torch.float32)
+        self.dtype, self.e = metric._image_eotf(t.dtype)          # float32, float16 or bfloat16 (float_pair)
         self.w = metric._rgb2y()
         self.fl, self.taps = metric._temporal_taps(fps)
         self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
@@ -155,11 +155,11 @@ class _Buffers:
         grad = self.grad if grad is None else grad
         N, HW = s.N, s.H * s.W
         ff, fp = _fold_arrays(fold_list(s.widx, s.fl, N))
-        nat.check(lib.fvvdp_video_grad_input(s.W, s.H, N, C.c_void_p(g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
-                                             C.c_void_p(t.data_ptr()), C.c_void_p(grad.data_ptr()), s.C, N * HW, HW,
-                                             C.byref(s.e), nat.fptr(s.w), C.c_void_p(self.head.data_ptr()), self.head.numel() * 4,
-                                             s.stream))
+        nat.check(lib.fvvdp_video_grad_input_st(s.W, s.H, N, C.c_void_p(g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
+                                                C.c_void_p(t.data_ptr()), C.c_void_p(grad.data_ptr()), s.dtype, s.C, N * HW, HW,
+                                                C.byref(s.e), nat.fptr(s.w), C.c_void_p(self.head.data_ptr()),
+                                                self.head.numel() * 4, s.stream))
         return grad
 
 
@@ -198,7 +198,8 @@ def _backward(metric, t, r, fps, fix, Q, gamma, need_t=True, need_r=False):
 
 
 class JodVideoFunction(torch.autograd.Function):
-    """test, reference [1, C, N, H, W] (contiguous fp32 on the metric's device) -> JOD (0-d).  place() detaches the input that
+    """test, reference [1, C, N, H, W] (contiguous, of one dtype -- float32, float16 or bfloat16 -- on the metric's device) -> JOD
+    (0-d, fp32).  The tensors saved for backward are the clips as they came, and each gradient has its clip's dtype.  place() detaches the input that
     `wrt` treats as a constant, so needs_input_grad names the gradients to make."""
 
     @staticmethod
@@ -222,7 +223,7 @@ class JodVideoFunction(torch.autograd.Function):
 
 
 def clip_arguments(name, metric, test, reference, dim_order, frames_per_second, wrt=None):
-    """What jod_video and jod_gazes (`name`) accept: one float32 clip pair of at least 2 frames, C = 1 or 3, a closed-form display
+    """What jod_video and jod_gazes (`name`) accept: one float32 / float16 / bfloat16 clip pair (float_pair) of at least 2 frames, C = 1 or 3, a closed-form display
     model, a temporal filter of at most VIDEO_GRAD_MAX_TAPS taps.  Returns test and reference as [1, C, N, H, W] tensors, not yet
     placed on the device.  wrt: which input the gradient is taken for (None: `name` has no wrt=, the test)."""
     refuse_unsupported(name, metric, test, reference, wrt)
@@ -240,7 +241,7 @@ def clip_arguments(name, metric, test, reference, dim_order, frames_per_second, 
                            "image: use jod_images)" % name)
     if "B" in d and t.shape[d.index("B")] != 1:
         raise RuntimeError("%s takes one clip per call (B must be 1)" % name)
-    need_float32(name, "clips", t, r)
+    t, r = float_pair(name, "clips", t, r)
     if not frames_per_second > 0:
         raise RuntimeError("When passing video sequences, you must set frames_per_second parameter")
     fl = filter_length(frames_per_second)

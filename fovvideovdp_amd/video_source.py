@@ -62,7 +62,9 @@ class fvvdp_video_source_dm(fvvdp_video_source):
 
 
 class fvvdp_video_source_array(fvvdp_video_source_dm):
-    """Test/reference content held in torch tensors or numpy arrays (uint8, uint16, float32), any dimension order."""
+    """Test/reference content held in torch tensors or numpy arrays (uint8, uint16, float32; float16 and, for tensors,
+    bfloat16: read as they are and widened exactly, so the result is the float32 source's on the upcast array), any dimension
+    order."""
 
     def __init__(self, test_video, reference_video, fps, dim_order='BCFHW', display_photometry='sdr_4k_30',
                  color_space_name='sRGB'):
@@ -111,6 +113,8 @@ class fvvdp_video_source_array(fvvdp_video_source_dm):
         fr = from_array[:, :, frame:(frame + 1), :, :].to(device)
         if from_array.dtype is torch.float32:
             V = fr
+        elif from_array.dtype is torch.float16 or from_array.dtype is torch.bfloat16:
+            V = fr.to(torch.float32)        # exact
         elif from_array.dtype is torch.int16:
             V = (fr.to(torch.int32) & 0xFFFF).to(torch.float32) / 65535
         elif from_array.dtype is torch.uint8:

@@ -59,8 +59,12 @@ typedef struct fvvdp_params {
     float d_max;         /* 1e4                                   fvvdp.py:595 */
 } fvvdp_params;
 
-/* Source sample types accepted by fvvdp_temporal_channels (pyfvvdp/video_source.py:184-200). */
-enum { FVVDP_U8 = 0, FVVDP_U16 = 1, FVVDP_F32 = 2 };
+/* Source sample types accepted by fvvdp_temporal_channels (pyfvvdp/video_source.py:184-200).  FVVDP_F16 (IEEE binary16) and
+ * FVVDP_BF16 (bfloat16) samples are widened to fp32 exactly and then take the path of FVVDP_F32: every result equals the one
+ * for the upcast input, bit for bit.  They are accepted by fvvdp_temporal_channels, fvvdp_temporal_channels_frames and
+ * fvvdp_images_channels, and by the *_st gradients of fvvdp_hip_half.h; not by fvvdp_pu21_sse nor by fvvdp_luminance_frames
+ * (fvvdp_hip_taps.h), which take such a source upcast to float32. */
+enum { FVVDP_U8 = 0, FVVDP_U16 = 1, FVVDP_F32 = 2, FVVDP_F16 = 3, FVVDP_BF16 = 4 };
 
 /* Display photometry applied per colour channel (pyfvvdp/fvvdp_display_model.py:147-165, :203-212). */
 enum {
@@ -152,7 +156,7 @@ int fvvdp_ctx_set_view_maps(fvvdp_ctx* ctx, int band, const float* d_view_x, con
  * (fvvdp_display_model.py:147-165) and the sliding-window temporal filter (fvvdp.py:258-300) for `n_out`
  * consecutive output frames; the result is written into pyramid level 0 of slots [slot0, slot0+n_out).
  *   d_test, d_ref   source videos, element (c, f, y, x) at  c*chan_stride + f*frame_stride + y*width + x
- *   dtype, C        FVVDP_U8/U16/F32; C in {1,3}
+ *   dtype, C        FVVDP_U8/U16/F32/F16/BF16; C in {1,3}
  *   h_rgb2y[3]      luminance weights (color_spaces.json RGB2Y), ignored when C == 1
  *   h_frame_idx     [fl-1+n_out] source frame of every virtual time step: the first fl-1 entries are the
  *                   history before the first output (temporal padding, or real frames when continuing a

@@ -727,6 +727,7 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                                     (chan_stride % PXv == 0) && (frame_stride % PXv == 0) &&
                                     (reinterpret_cast<uintptr_t>(d_test) % (size_t)(es * PXv) == 0) &&
                                     (reinterpret_cast<uintptr_t>(d_ref) % (size_t)(es * PXv) == 0);
+                bool ticketed = false;
                 if (vec_ok) {
                     // uint8, 9..16 taps (33-64 fps): resident workgroups that take their pixel blocks from a counter
                     // (temporal_vec_kernel; FVVDP_K1_TICKET=0: one workgroup per block).  Same blocks, same arithmetic.
@@ -735,13 +736,16 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                         if (hipMemsetAsync(c->d_ticket, 0, sizeof(int), st) == hipSuccess) a.ticket = c->d_ticket;
                         else (void)hipGetLastError();
                     }
-                    k1_launch_vec(FL, dtype, a, st);
+                    ticketed = k1_launch_vec(FL, dtype, a, st);
                 } else if (FL == 64) {
                     // the 64-slot ring exists as the 1-pixel-per-lane vector kernel only; it needs nothing but element alignment
                     return fail(FVVDP_EINVAL, "source pointers must be aligned to their element size");
                 } else {
                     k1_launch_ring(FL, dtype, a, st);
                 }
+                if (c->env.debug_variant)                // tests: which kernel this launch ran (one line per launch of a split call)
+                    fprintf(stderr, "fvvdp: array ingest: %s, FL %d, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 %d, tickets %d\n",
+                            vec_ok ? "vector" : "per-pixel", FL, fl, dtype, C, eotf->kind, nn, t0, ticketed ? 1 : 0);
             }
             return FVVDP_OK;
         };
@@ -778,6 +782,9 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
         la.oob = d_oob_flag;
         for (int k = 0; k < nu; ++k) la.fr[k] = uniq[k];
         k1_launch_luminance(dtype, la, st);
+        if (c->env.debug_variant)                        // (n_out: the frames converted; the inner call prints its own line)
+            fprintf(stderr, "fvvdp: array ingest: luminance, FL 0, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 0, tickets 0\n",
+                    fl, dtype, C, eotf->kind, nu);
         std::vector<int32_t> pos(total);
         for (int u = 0; u < total; ++u) pos[u] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), h_frame_idx[u]) - uniq.begin());
         fvvdp_eotf none;
@@ -824,6 +831,9 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
         a.taps = c->d_taps;
         a.idx = c->d_idx;
         k1_launch_generic(c->P, dtype, a, st);
+        if (c->env.debug_variant)
+            fprintf(stderr, "fvvdp: array ingest: generic, FL 0, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 0, tickets 0\n",
+                    fl, dtype, C, eotf->kind, n_out);
     }
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;

@@ -19,8 +19,9 @@ static constexpr int DT = K1_PART <= 2 ? K1_PART : K1_PART - 1;      // FVVDP_U8
 static constexpr int SRC = DT == FVVDP_U8 ? SRC_U8 : (DT == FVVDP_U16 ? SRC_U16 : (DT == FVVDP_F32 ? SRC_F32 : (DT == FVVDP_F16 ? SRC_F16 : SRC_BF16)));
 static_assert(SRC == DT, "the kernels' sample types are numbered as the ABI's");
 
+// returns whether the launch takes its pixel blocks from the ticket counter (FVVDP_DEBUG_VARIANT reports it)
 template <int FL>
-static void launch_vec(const TemporalArgs& a, hipStream_t st) {
+static bool launch_vec(const TemporalArgs& a, hipStream_t st) {
     constexpr int PX = k1_px(FL);
     constexpr int TD = 1;
     constexpr int WPB = k1_wpb(FL);                       // waves per workgroup, one pixel block each
@@ -28,7 +29,7 @@ static void launch_vec(const TemporalArgs& a, hipStream_t st) {
     dim3 grid((n_blocks + WPB - 1) / WPB), block(64 * WPB);
     if constexpr (src_is_half(SRC)) {
         hipLaunchKernelGGL((temporal_vec_half_kernel<FL, PX, SRC, TD>), grid, block, 0, st, a);
-        return;
+        return false;
     } else {
     if (a.ticket) {          // resident workgroups that take their pixel blocks from a.ticket (uint8, FL <= 16; the caller zeroed it)
         static int resident = 0;
@@ -41,9 +42,10 @@ static void launch_vec(const TemporalArgs& a, hipStream_t st) {
             else { (void)hipGetLastError(); resident = -1; }
         }
         if (resident > 0 && (int)grid.x > 2 * resident) grid.x = (unsigned int)resident;
-        else { TemporalArgs b = a; b.ticket = nullptr; hipLaunchKernelGGL((temporal_vec_kernel<FL, PX, SRC, TD>), grid, block, 0, st, b); return; }
+        else { TemporalArgs b = a; b.ticket = nullptr; hipLaunchKernelGGL((temporal_vec_kernel<FL, PX, SRC, TD>), grid, block, 0, st, b); return false; }
     }
     hipLaunchKernelGGL((temporal_vec_kernel<FL, PX, SRC, TD>), grid, block, 0, st, a);
+    return a.ticket != nullptr;
     }
 }
 template <int FL, int PX>
@@ -69,11 +71,11 @@ static void launch_generic(const GenericArgs& a, hipStream_t st) {
 #else
 #define K1_NAME(f) f##_bf16
 #endif
-void K1_NAME(k1_vec)(int FL, const TemporalArgs& a, hipStream_t st) {
-    if (FL == 8) launch_vec<8>(a, st);
-    else if (FL == 16) launch_vec<16>(a, st);
-    else if (FL == 64) launch_vec<64>(a, st);     // the cases of k1_ring64_ok() only (compile time: the loop is unrolled FL times per case)
-    else launch_vec<32>(a, st);
+bool K1_NAME(k1_vec)(int FL, const TemporalArgs& a, hipStream_t st) {
+    if (FL == 8) return launch_vec<8>(a, st);
+    if (FL == 16) return launch_vec<16>(a, st);
+    if (FL == 64) return launch_vec<64>(a, st);   // the cases of k1_ring64_ok() only (compile time: the loop is unrolled FL times per case)
+    return launch_vec<32>(a, st);
 }
 void K1_NAME(k1_ring)(int FL, const TemporalArgs& a, hipStream_t st) {
     if (FL == 8) launch_ring<8, 4>(a, st);
@@ -92,9 +94,9 @@ void K1_NAME(k1_luminance)(const LumArgs& a, hipStream_t st) {
 #endif
 
 #if K1_PART == 3
-void k1_vec_u8(int, const TemporalArgs&, hipStream_t);
-void k1_vec_u16(int, const TemporalArgs&, hipStream_t);
-void k1_vec_f32(int, const TemporalArgs&, hipStream_t);
+bool k1_vec_u8(int, const TemporalArgs&, hipStream_t);
+bool k1_vec_u16(int, const TemporalArgs&, hipStream_t);
+bool k1_vec_f32(int, const TemporalArgs&, hipStream_t);
 void k1_ring_u8(int, const TemporalArgs&, hipStream_t);
 void k1_ring_u16(int, const TemporalArgs&, hipStream_t);
 void k1_ring_f32(int, const TemporalArgs&, hipStream_t);
@@ -104,21 +106,21 @@ void k1_generic_f32(int, const GenericArgs&, hipStream_t);
 void k1_luminance_u8(const LumArgs&, hipStream_t);
 void k1_luminance_u16(const LumArgs&, hipStream_t);
 void k1_luminance_f32(const LumArgs&, hipStream_t);
-void k1_vec_f16(int, const TemporalArgs&, hipStream_t);
+bool k1_vec_f16(int, const TemporalArgs&, hipStream_t);
 void k1_ring_f16(int, const TemporalArgs&, hipStream_t);
 void k1_generic_f16(int, const GenericArgs&, hipStream_t);
 void k1_luminance_f16(const LumArgs&, hipStream_t);
-void k1_vec_bf16(int, const TemporalArgs&, hipStream_t);
+bool k1_vec_bf16(int, const TemporalArgs&, hipStream_t);
 void k1_ring_bf16(int, const TemporalArgs&, hipStream_t);
 void k1_generic_bf16(int, const GenericArgs&, hipStream_t);
 void k1_luminance_bf16(const LumArgs&, hipStream_t);
 
-void k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st) {
-    if (dtype == FVVDP_U8) k1_vec_u8(FL, a, st);
-    else if (dtype == FVVDP_U16) k1_vec_u16(FL, a, st);
-    else if (dtype == FVVDP_F16) k1_vec_f16(FL, a, st);
-    else if (dtype == FVVDP_BF16) k1_vec_bf16(FL, a, st);
-    else k1_vec_f32(FL, a, st);
+bool k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st) {
+    if (dtype == FVVDP_U8) return k1_vec_u8(FL, a, st);
+    if (dtype == FVVDP_U16) return k1_vec_u16(FL, a, st);
+    if (dtype == FVVDP_F16) return k1_vec_f16(FL, a, st);
+    if (dtype == FVVDP_BF16) return k1_vec_bf16(FL, a, st);
+    return k1_vec_f32(FL, a, st);
 }
 void k1_launch_ring(int FL, int dtype, const TemporalArgs& a, hipStream_t st) {
     if (dtype == FVVDP_U8) k1_ring_u8(FL, a, st);

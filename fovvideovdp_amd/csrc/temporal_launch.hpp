@@ -16,7 +16,7 @@ static inline bool k1_ring64_ok(int dtype, int C, int eotf_kind) {
 }
 
 // FL in {8, 16, 32}; dtype FVVDP_U8 / U16 / F32 / F16 / BF16.  FL = 64: see k1_ring64_ok().
-void k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st);     // aligned sizes (see the call site)
+bool k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st);     // aligned sizes (see the call site); true: blocks handed out by the ticket counter
 void k1_launch_ring(int FL, int dtype, const TemporalArgs& a, hipStream_t st);    // any size
 void k1_launch_generic(int planes, int dtype, const GenericArgs& a, hipStream_t st);
 void k1_launch_luminance(int dtype, const LumArgs& a, hipStream_t st);     // source frames -> fp32 luminance frames (two-pass path)

@@ -12,7 +12,9 @@ When psi needs a gradient the forward also makes, per backward batch, one ingest
 the slope planes on and the two level-0 backward passes of jod_images / jod_video(wrt="both") with gamma = 1; what their last
 kernel would multiply by dL/dV and store is multiplied by dL/dpsi and summed instead (fvvdp_images_display_sums per batch,
 fvvdp_video_display_sums once per stream after the last batch).  Only three sums per stream are kept -- [2, 3] doubles for a
-clip, [B, 2, 3] for a stack -- and backward() is `chain`: float64 arithmetic on them, times the upstream gradient."""
+clip, [B, 2, 3] for a stack -- and backward() is `chain`: float64 arithmetic on them, times the upstream gradient.
+The setups (with psi's display block), both forward loops, the map-writing passes, the buffers and the level-0 backward are
+grad_passes.py's, shared with the other differentiable entry points."""
 import ctypes as C
 import math
 
@@ -22,7 +24,13 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .display_model import fvvdp_display_photo_eotf, native_eotf
-from .fvvdp import fvvdp as _fvvdp
+from .fvvdp import _image_stack, fvvdp as _fvvdp
+from .grad_passes import (ClipSetup, ImageSetup, Maps, _apply, _fold_arrays, _ptr, _refuse, batches, fold_list, forward_clip,
+                          forward_images, grad_batch_size, level0_backward, level0_buffers, vector_values, work_tensor,
+                          workspace_bytes)
+from .image_grad import grad_planes
+from .video_grad import clip_arguments, video_grad_planes
+from .video_source import fvvdp_video_source_array
 
 DISPLAY_PARAMETER_NAMES = _fvvdp.DISPLAY_PARAMETER_NAMES
 _IDX = {name: i for i, name in enumerate(DISPLAY_PARAMETER_NAMES)}
@@ -52,16 +60,7 @@ def display_parameter_tensor(metric):
 def psi_values(psi):
     """psi (a 1-D tensor or sequence of the 5 values of DISPLAY_PARAMETER_NAMES) -> list of Python floats; refuses what no
     display can have.  A host tensor is read without touching the GPU."""
-    t = psi.detach() if isinstance(psi, torch.Tensor) else torch.as_tensor(np.asarray(psi, dtype=np.float64))
-    if t.dim() != 1 or t.shape[0] != len(DISPLAY_PARAMETER_NAMES):
-        raise RuntimeError("psi must be a 1-D vector of the %d parameters of DISPLAY_PARAMETER_NAMES, got shape %s"
-                           % (len(DISPLAY_PARAMETER_NAMES), tuple(t.shape)))
-    if not t.is_floating_point():
-        raise RuntimeError("psi must be a float32 or float64 tensor, got %s" % t.dtype)
-    vals = [float(v) for v in t.to(device="cpu", dtype=torch.float64).tolist()]
-    bad = [DISPLAY_PARAMETER_NAMES[i] for i, v in enumerate(vals) if not math.isfinite(v)]
-    if bad:
-        raise RuntimeError("psi has non-finite entries: %s" % ", ".join(bad))
+    vals = vector_values("psi", "DISPLAY_PARAMETER_NAMES", psi)
     for name in _POSITIVE:
         if not vals[_IDX[name]] > 0:
             raise RuntimeError("psi: %s must be positive, got %g" % (name, vals[_IDX[name]]))
@@ -124,50 +123,28 @@ def _images_forward(metric, t, r, fix, e, want_sums):
     """The launches of predict_images under the display block e -> (JOD [B], Q_per_ch [bands, 2, B], sums [B, 2, 3] float64 or
     None).  t, r: contiguous
     fp32 [B, C, H, W] on the metric's device."""
-    from .image_grad import _Setup, grad_batch_size, grad_planes, slope_planes
-    s = _Setup(metric, t)
-    s.e = e
+    s = ImageSetup(metric, t, r, eotf=e)
     B, dev, HW = s.B, metric.device, s.H * s.W
-    Q = torch.zeros((s.n_bands, 2, B), dtype=torch.float32, device=dev)
-    jod = torch.empty(B, dtype=torch.float32, device=dev)
-    lib = nat.lib()
-    for b0 in range(0, B, s.batch):
-        nb = min(s.batch, B - b0)
-        s.ingest(lib, t, r, b0, nb)
-        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        nat.check(lib.fvvdp_images_forward_pool(s.ctx.handle, nb, C.c_void_p(Q.data_ptr()), B, b0, fx, g, None, C.byref(s.pp),
-                                                C.c_void_p(jod.data_ptr() + 4 * b0), s.stream))
+    jod, Q = forward_images(s, fix)
     if not want_sums:
         return jod, Q, None
     gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, grad_planes("both"))
-    maps_arr, _maps = metric._band_maps(gb, s.W, s.H, s.n_bands, contrast_planes=2)
-    slopes, _slopes = slope_planes(metric, gb, s.W, s.H, s.n_bands)
-    tb, rb = C.c_size_t(), C.c_size_t()
-    nat.check(lib.fvvdp_images_display_sums_workspace(s.W, s.H, s.n_bands, gb, 0, C.byref(tb)))
-    nat.check(lib.fvvdp_images_display_sums_workspace(s.W, s.H, s.n_bands, gb, 1, C.byref(rb)))
-    work = torch.empty((max(tb.value, rb.value) + 7) // 8, dtype=torch.float64, device=dev)
-    q_scratch = torch.empty((s.n_bands, 2, gb), dtype=torch.float32, device=dev)
-    jod_scratch = torch.empty(gb, dtype=torch.float32, device=dev)
+    maps = Maps(metric, s.W, s.H, s.n_bands, 2, gb).add_slopes()
+    lib = nat.lib()
+    tb = workspace_bytes(lib.fvvdp_images_display_sums_workspace, s.W, s.H, s.n_bands, gb, 0)
+    rb = workspace_bytes(lib.fvvdp_images_display_sums_workspace, s.W, s.H, s.n_bands, gb, 1)
+    work = work_tensor(max(tb, rb), torch.float64)
     ones = torch.ones(gb, dtype=torch.float32, device=dev)
     part = torch.empty((2, gb, nat.DISPLAY_SUMS), dtype=torch.float64, device=dev)
     sums = torch.empty((B, 2, nat.DISPLAY_SUMS), dtype=torch.float64, device=dev)
-    prm = metric.native_params()
-    for b0 in range(0, B, gb):
-        nb = min(gb, B - b0)
-        tp = s.ingest(lib, t, r, b0, nb)
+    prm = s.params()
+    for b0, nb in batches(B, gb):
+        tp = s.write_maps(maps, fix, b0, nb)
         rp = (C.c_void_p * nb)(*[r[k].data_ptr() for k in range(b0, b0 + nb)])
-        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, slopes))
-        try:
-            nat.check(lib.fvvdp_images_forward_pool(s.ctx.handle, nb, C.c_void_p(q_scratch.data_ptr()), nb, 0, fx, g, maps_arr,
-                                                    C.byref(s.pp), C.c_void_p(jod_scratch.data_ptr()), s.stream))
-        finally:
-            nat.check(lib.fvvdp_ctx_set_slope_maps(s.ctx.handle, None))
-        for side, (sl, ptrs, nbytes) in enumerate(((None, tp, tb.value), (slopes, rp, rb.value))):
-            nat.check(lib.fvvdp_images_display_sums(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()),
-                                                    B, b0, C.c_void_p(ones.data_ptr()), maps_arr, sl, ptrs, s.C, HW, C.byref(s.e),
-                                                    nat.fptr(s.w), C.c_void_p(part[side].data_ptr()),
-                                                    C.c_void_p(work.data_ptr()), nbytes, s.stream))
+        for side, (sl, ptrs, nbytes) in enumerate(((None, tp, tb), (maps.slopes, rp, rb))):
+            nat.check(lib.fvvdp_images_display_sums(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), _ptr(Q), B, b0,
+                                                    _ptr(ones), maps.maps_arr, sl, ptrs, s.C, HW, C.byref(s.e), nat.fptr(s.w),
+                                                    _ptr(part[side]), _ptr(work), nbytes, s.stream))
         sums[b0:b0 + nb] = part[:, :nb].transpose(0, 1)
     return jod, Q, sums
 
@@ -176,55 +153,29 @@ def _video_forward(metric, t, r, fps, fix, e, want_sums):
     """The launches of predict (sync=False) under the display block e -> (JOD 0-d, Q_per_ch [bands, 2, N], sums [2, 3]
     float64 or None).  t, r: contiguous
     fp32 [1, C, N, H, W] on the metric's device."""
-    from .image_grad import grad_batch_size
-    from .video_grad import _Buffers, _Setup, _fold_arrays, fold_list, video_grad_planes
-    s = _Setup(metric, t, fps)
-    s.e = e
+    s = ClipSetup(metric, t, fps, r, eotf=e)
     N, dev, HW = s.N, metric.device, s.H * s.W
-    nq = s.n_bands * 2 * N
-    res = torch.zeros(nq + 2, dtype=torch.float32, device=dev)          # Q_per_ch | range flag | JOD, as predict lays it out
-    Q = res[:nq].view(s.n_bands, 2, N)
-    oob = res[nq:nq + 1].view(torch.int32)
-    lib = nat.lib()
-    for b0 in range(0, N, s.batch):
-        nb = min(s.batch, N - b0)
-        s.ingest(lib, t, r, b0, nb, oob)
-        fx, g, _keep = metric._fov_args(s.ctx, fix, b0, nb, s.n_bands, s.W, s.H)
-        if b0 + nb == N:
-            nat.check(lib.fvvdp_bands_forward_pool(s.ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None,
-                                                   C.byref(s.pp), C.c_void_p(res[nq + 1:].data_ptr()), s.stream))
-        else:
-            nat.check(lib.fvvdp_bands_forward(s.ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None, s.stream))
+    jod, Q = forward_clip(s, fix)
     if not want_sums:
-        return res[nq + 1], Q, None
+        return jod, Q, None
     gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, video_grad_planes("both"))
-    vb, rb, sb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-    nat.check(lib.fvvdp_video_grad_workspace(s.W, s.H, s.n_bands, gb, C.byref(vb)))
-    nat.check(lib.fvvdp_ref_grad_workspace(s.W, s.H, s.n_bands, gb, 2, C.byref(rb)))
-    nat.check(lib.fvvdp_video_display_sums_workspace(s.W, s.H, C.byref(sb)))
-    buf = _Buffers("display_jod_video", metric, s, t, gb, vb.value, True, rb.value, results=False)
-    prm = metric.native_params()
+    lib = nat.lib()
+    buf = level0_buffers("display_jod_video", metric, s, t, gb, True, True, results=False)
+    sb = workspace_bytes(lib.fvvdp_video_display_sums_workspace, s.W, s.H)
+    prm = s.params()
     gamma = torch.ones(1, dtype=torch.float32, device=dev)
-    for b0 in range(0, N, gb):
-        nb = min(gb, N - b0)
+    for b0, nb in batches(N, gb):
         buf.maps_pass(lib, metric, s, t, r, fix, b0, nb)
-        nat.check(lib.fvvdp_video_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), N, b0,
-                                              C.c_void_p(gamma.data_ptr()), buf.maps_arr, C.c_void_p(buf.g0.data_ptr()),
-                                              C.c_void_p(buf.work.data_ptr()), buf.work_bytes, s.stream))
-        nat.check(lib.fvvdp_video_ref_grad_frames(s.W, s.H, s.n_bands, nb, C.byref(prm), C.byref(s.pp), C.c_void_p(Q.data_ptr()), N,
-                                                  b0, C.c_void_p(gamma.data_ptr()), buf.maps_arr, buf.slopes,
-                                                  C.c_void_p(buf.g0_r.data_ptr()), C.c_void_p(buf.work_r.data_ptr()),
-                                                  buf.ref_bytes, s.stream))
+        level0_backward(buf, s, prm, Q, N, b0, nb, gamma)
     ff, fp = _fold_arrays(fold_list(s.widx, s.fl, N))
-    work = torch.empty((sb.value + 7) // 8, dtype=torch.float64, device=dev)
+    work = work_tensor(sb, torch.float64)
     sums = torch.empty((2, nat.DISPLAY_SUMS), dtype=torch.float64, device=dev)
     for side, (g0, clip) in enumerate(((buf.g0, t), (buf.g0_r, r))):
-        nat.check(lib.fvvdp_video_display_sums(s.W, s.H, N, C.c_void_p(g0.data_ptr()), ff.ctypes.data_as(C.POINTER(C.c_int32)),
-                                               fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl,
-                                               C.c_void_p(clip.data_ptr()), s.C, N * HW, HW, C.byref(s.e), nat.fptr(s.w),
-                                               C.c_void_p(buf.head.data_ptr()), buf.head.numel() * 4,
-                                               C.c_void_p(sums[side].data_ptr()), C.c_void_p(work.data_ptr()), sb.value, s.stream))
-    return res[nq + 1], Q, sums
+        nat.check(lib.fvvdp_video_display_sums(s.W, s.H, N, _ptr(g0), ff.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               fp.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(s.taps), s.fl, _ptr(clip), s.C,
+                                               N * HW, HW, C.byref(s.e), nat.fptr(s.w), _ptr(buf.head), buf.head.numel() * 4,
+                                               _ptr(sums[side]), _ptr(work), sb, s.stream))
+    return jod, Q, sums
 
 
 class _DisplayFunction(torch.autograd.Function):
@@ -232,7 +183,7 @@ class _DisplayFunction(torch.autograd.Function):
     depend on the upstream gradient, so the forward forms them and keeps [..., 2, 3] doubles."""
 
     @staticmethod
-    def forward(ctx, psi, metric, vals, eotf, run):
+    def forward(ctx, psi, metric, run, vals, eotf):
         want = bool(ctx.needs_input_grad[0])
         with torch.cuda.device(metric.device):
             jod, _, sums = run(want)
@@ -254,17 +205,7 @@ class _DisplayFunction(torch.autograd.Function):
         return chain(U, ctx.vals, ctx.eotf).to(device=ctx.psi_device, dtype=ctx.psi_dtype), None, None, None, None
 
 
-def _refuse(name, metric, test, reference, other):
-    for a in (test, reference):
-        if isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("%s differentiates the JOD with respect to the display's parameters only and this test or "
-                               "reference requires grad; detach it (gradients for the images or frames: %s)" % (name, other))
-    if metric.do_heatmap:
-        raise RuntimeError("%s makes no heat maps: build the metric with heatmap=None (heat maps: predict)" % name)
-
-
 def _need_float(name, test, reference):
-    from .video_source import fvvdp_video_source_array
     t, r = fvvdp_video_source_array._as_tensor(test), fvvdp_video_source_array._as_tensor(reference)
     if t.dtype != torch.float32 or r.dtype != torch.float32:
         raise RuntimeError("%s needs float32 test and reference (got %s and %s): convert integer sources to float32 in [0, 1] -- "
@@ -274,20 +215,12 @@ def _need_float(name, test, reference):
     return t, r
 
 
-def _apply(metric, psi, vals, eotf, run):
-    if isinstance(psi, torch.Tensor) and psi.requires_grad and torch.is_grad_enabled():
-        return _DisplayFunction.apply(psi, metric, vals, eotf, run)
-    with torch.cuda.device(metric.device):
-        return run(False)[0]
-
-
 def display_jod_images(metric, test, reference, psi, dim_order="BCHW", fixation_point=None):
     """fvvdp.display_jod_images (see there)."""
-    from .fvvdp import _image_stack
     name = "display_jod_images"
     vals = psi_values(psi)
     ph = photometry_of(metric, vals, name)
-    _refuse(name, metric, test, reference, "jod_images")
+    _refuse(name, "the display's parameters", metric, test, reference, "jod_images", " (heat maps: predict)")
     t, r = _need_float(name, test, reference)
     t, r = _image_stack(t, r, dim_order)
     if t.shape[1] != 1 and t.shape[1] != 3:
@@ -296,16 +229,16 @@ def display_jod_images(metric, test, reference, psi, dim_order="BCHW", fixation_
     t, r = t.detach().to(metric.device).contiguous(), r.detach().to(metric.device).contiguous()
     fix = metric._fixation(fixation_point, t.shape[3], t.shape[2], t.shape[0]) if metric.foveated else None
     e = eotf_of(ph)
-    return _apply(metric, psi, vals, ph.EOTF, lambda want: _images_forward(metric, t, r, fix, e, want))
+    run = lambda want: _images_forward(metric, t, r, fix, e, want)          # noqa: E731
+    return _apply(_DisplayFunction, metric, psi, run, vals, ph.EOTF)
 
 
 def display_jod_video(metric, test, reference, psi, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
     """fvvdp.display_jod_video (see there)."""
-    from .video_grad import clip_arguments
     name = "display_jod_video"
     vals = psi_values(psi)
     ph = photometry_of(metric, vals, name)
-    _refuse(name, metric, test, reference, "jod_video")
+    _refuse(name, "the display's parameters", metric, test, reference, "jod_video", " (heat maps: predict)")
     t, r = _need_float(name, test, reference)
     t, r = clip_arguments(name, metric, t, r, dim_order, frames_per_second)
     metric._check_device()
@@ -313,4 +246,5 @@ def display_jod_video(metric, test, reference, psi, dim_order="BCFHW", frames_pe
     fix = metric._fixation(fixation_point, t.shape[4], t.shape[3], t.shape[2]) if metric.foveated else None
     e = eotf_of(ph)
     fps = float(frames_per_second)
-    return _apply(metric, psi, vals, ph.EOTF, lambda want: _video_forward(metric, t, r, fps, fix, e, want))
+    run = lambda want: _video_forward(metric, t, r, fps, fix, e, want)          # noqa: E731
+    return _apply(_DisplayFunction, metric, psi, run, vals, ph.EOTF)

@@ -1035,7 +1035,7 @@ class fvvdp:
             per_frame += W * H * 8.0                   # ... and of every frame of the batch
         return max(1, min(n_out, cap, int(max(budget, per_frame) // per_frame)))
 
-    # ---- launch arguments shared by predict, predict_images and the gradient passes (image_grad.py, video_grad.py) ----------
+    # ---- launch arguments shared by predict, predict_images and the launch layer of the gradients (grad_passes.py) ----------
     def _band_count(self, width, height):
         """(number of band-pass levels, their centre frequencies) of a frame on this display; refuses a frame with none."""
         n_bands, rho_band = band_frequencies(width, height, self.pix_per_deg)

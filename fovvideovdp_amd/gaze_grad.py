@@ -7,7 +7,7 @@ everything that does not depend on the gaze: per backward batch one ingest and o
 gaze 0; only its contrast and L_bkg maps are read), then fvvdp_gaze_grad_frames sums the layer gradients of all gazes and runs
 the coarse-to-fine sweep and level 0 once, and after the last batch one fvvdp_video_grad_input applies the transpose of the
 temporal filter and the display model's derivative.  Neither pass reads context scratch left by the other, and neither
-synchronises with the host."""
+synchronises with the host.  Setup, buffers and the map-writing pass are grad_passes.py's, as jod_video's."""
 import ctypes as C
 
 import numpy as np
@@ -17,8 +17,9 @@ from torch.autograd.function import once_differentiable
 from . import _native as nat
 from .display_model import native_geometry
 from .gazes import _gaze_array
-from .image_grad import grad_batch_size, place
-from .video_grad import GRAD_PLANES, _Buffers, _Setup, clip_arguments
+from .grad_passes import ClipBuffers, ClipSetup, _ptr, batches, grad_batch_size, workspace_bytes
+from .image_grad import place
+from .video_grad import GRAD_PLANES, clip_arguments
 
 # Largest group of gazes one gaze_layer_kernel launch takes: 0 = the library's default (FVVDP_GAZE_GROUP_MAX = 8), or 1, 2, 4, 8.
 # The gradient does not depend on it, bit for bit; smaller groups only make more launches (tests, A/B runs).
@@ -49,7 +50,7 @@ def _csf_tables(metric):
 
 def _forward(metric, t, r, fps, gaze):
     """JOD [G] and Q_per_ch [G, n_bands, 2, N] on the device: the launches of predict_gazes, no flag read back."""
-    s = _Setup(metric, t, fps)
+    s = ClipSetup(metric, t, fps, r)
     N, dev, G = s.N, metric.device, gaze.shape[0]
     nq = s.n_bands * 2 * N
     res = torch.zeros(G * nq + 1 + G, dtype=torch.float32, device=dev)      # Q_per_ch | range flag | JOD, as predict_gazes lays it out
@@ -57,47 +58,36 @@ def _forward(metric, t, r, fps, gaze):
     oob = res[G * nq:G * nq + 1].view(torch.int32)
     jod = res[G * nq + 1:]
     lib = nat.lib()
-    nbytes = C.c_size_t()
-    nat.check(lib.fvvdp_gaze_workspace(s.W, s.H, s.n_bands, G, min(s.batch, N), C.byref(nbytes)))
-    work = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+    nbytes = workspace_bytes(lib.fvvdp_gaze_workspace, s.W, s.H, s.n_bands, G, min(s.batch, N))
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     geom = metric._geom_struct()
-    for b0 in range(0, N, s.batch):
-        nb = min(s.batch, N - b0)
+    for b0, nb in batches(N, s.batch):
         s.ingest(lib, t, r, b0, nb, oob)
-        gp = C.c_void_p(gaze.data_ptr() + 8 * b0)
+        common = (s.ctx.handle, nb, G, _ptr(gaze, 8 * b0), 2 * N, _ptr(Q), N, b0, C.byref(geom), _ptr(work), nbytes)
         if b0 + nb == N:
-            nat.check(lib.fvvdp_bands_forward_gazes_pool(s.ctx.handle, nb, G, gp, 2 * N, C.c_void_p(Q.data_ptr()), N, b0,
-                                                         C.byref(geom), C.c_void_p(work.data_ptr()), nbytes.value, C.byref(s.pp),
-                                                         C.c_void_p(jod.data_ptr()), s.stream))
+            nat.check(lib.fvvdp_bands_forward_gazes_pool(*common, C.byref(s.pp), _ptr(jod), s.stream))
         else:
-            nat.check(lib.fvvdp_bands_forward_gazes(s.ctx.handle, nb, G, gp, 2 * N, C.c_void_p(Q.data_ptr()), N, b0,
-                                                    C.byref(geom), C.c_void_p(work.data_ptr()), nbytes.value, s.stream))
+            nat.check(lib.fvvdp_bands_forward_gazes(*common, s.stream))
     return jod, Q
 
 
 def _backward(metric, t, r, fps, gaze, fix0, Q, gamma):
     """sum_g gamma[g] * dJOD_g/dt for the contiguous device clip t [1, C, N, H, W]."""
-    s = _Setup(metric, t, fps)
+    s = ClipSetup(metric, t, fps, r)
     N, dev, G = s.N, metric.device, gaze.shape[0]
     gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, GRAD_PLANES)
     lib = nat.lib()
-    nbytes = C.c_size_t()
-    nat.check(lib.fvvdp_gaze_grad_workspace(s.W, s.H, s.n_bands, gb, G, C.byref(nbytes)))
-    buf = _Buffers("jod_gazes", metric, s, t, gb, nbytes.value)
+    buf = ClipBuffers("jod_gazes", metric, s, t, gb, workspace_bytes(lib.fvvdp_gaze_grad_workspace, s.W, s.H, s.n_bands, gb, G))
     lut0, lut1, d_axes, h_axes = _csf_tables(metric)
-    prm, geom = metric.native_params(), metric._geom_struct()
+    prm, geom = s.params(), metric._geom_struct()
     rho = np.ascontiguousarray(s.rho_band, dtype=np.float64)
     gamma = gamma.to(device=dev, dtype=torch.float32).reshape(G).contiguous()
-    for b0 in range(0, N, gb):
-        nb = min(gb, N - b0)
-        buf.maps_pass(lib, metric, s, t, r, fix0, b0, nb)          # on the trace of gaze 0: only gaze-invariant maps are read
+    for b0, nb in batches(N, gb):
+        buf.maps_pass(lib, metric, s, t, r, fix0, b0, nb)                      # on the trace of gaze 0: only gaze-invariant maps are read
         nat.check(lib.fvvdp_gaze_grad_frames(s.W, s.H, s.n_bands, nb, G, int(GROUP_MAX), C.byref(prm), C.byref(s.pp),
-                                             C.byref(geom), rho.ctypes.data_as(C.POINTER(C.c_double)),
-                                             C.c_void_p(lut0.data_ptr()), C.c_void_p(lut1.data_ptr()),
-                                             C.c_void_p(d_axes.data_ptr()), nat.fptr(h_axes),
-                                             C.c_void_p(gaze.data_ptr() + 8 * b0), 2 * N, C.c_void_p(Q.data_ptr()), N, b0,
-                                             C.c_void_p(gamma.data_ptr()), buf.maps_arr, C.c_void_p(buf.g0.data_ptr()),
-                                             C.c_void_p(buf.work.data_ptr()), buf.work_bytes, s.stream))
+                                             C.byref(geom), rho.ctypes.data_as(C.POINTER(C.c_double)), _ptr(lut0), _ptr(lut1),
+                                             _ptr(d_axes), nat.fptr(h_axes), _ptr(gaze, 8 * b0), 2 * N, _ptr(Q), N, b0,
+                                             _ptr(gamma), buf.maps.maps_arr, _ptr(buf.g0), _ptr(buf.work), buf.work_bytes, s.stream))
     return buf.input_grad(lib, s, t)
 
 

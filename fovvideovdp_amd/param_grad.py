@@ -7,7 +7,7 @@ whose model constants are replaced for the duration of the call (fvvdp_ctx_set_p
 attributes are never touched, no context is created.  The forward makes the launches of predict_images / predict with constants
 converted from theta exactly as native_params() and _pool_params() convert the attributes, so the JOD is bit-identical to that
 of a metric whose attributes hold theta.  When theta needs a gradient the forward also re-runs the pyramid pass with every
-band's maps written, per backward batch of frames (image_grad.grad_batch_size), and fvvdp_param_sums reduces the maps to five
+band's maps written, per backward batch of frames (grad_passes.grad_batch_size), and fvvdp_param_sums reduces the maps to five
 sums per (band, temporal channel, frame); only Q_per_ch and the sums are kept.  backward() is `chain` alone: float64 tensor
 operations on [bands, 2, frames] arrays.
 
@@ -20,7 +20,10 @@ clip is evaluated under taps made from phi (fvvdp.temporal_filters, the expressi
 gradient, every backward batch also makes the two level-0 backward passes of jod_video(wrt="both") with gamma = 1 from the same
 maps (slope planes on), the luminance of the source frames under the batch's windows (fvvdp_luminance_frames) and the
 tap-gradient kernel (fvvdp_tap_grad, include/fvvdp_hip_taps.h); the batches' dJOD/dtaps [2, fl] are added in frame order in
-float64 and are all that is kept.  backward() is `tap_chain`: the float64 Jacobian of the taps with respect to phi."""
+float64 and are all that is kept.  backward() is `tap_chain`: the float64 Jacobian of the taps with respect to phi.
+The setups (with theta's constants and phi's taps), both forward loops, the map-writing passes, the buffers with their memory
+check and the level-0 backward are grad_passes.py's, shared with the other differentiable entry points; what is here is the
+vectors, the two chains, the sums (_Sums) and the tap gradient's own buffers and kernel (_TapGrad)."""
 import ctypes as C
 import math
 
@@ -29,8 +32,12 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _native as nat
-from .fvvdp import fvvdp as _fvvdp
-from .image_grad import grad_batch_size
+from .fvvdp import _image_stack, filter_length, fvvdp as _fvvdp, temporal_filters
+from .grad_passes import (ClipBuffers, ImageSetup, Maps, PlanClipSetup, _apply, _ptr, _refuse, batches, forward_clip,
+                          forward_images, grad_batch_size, level0_backward, vector_values, work_tensor, workspace,
+                          workspace_bytes)
+from .video_grad import video_grad_planes
+from .video_source import fvvdp_video_source_array
 
 PARAMETER_NAMES = _fvvdp.PARAMETER_NAMES
 TEMPORAL_PARAMETER_NAMES = _fvvdp.TEMPORAL_PARAMETER_NAMES
@@ -57,16 +64,7 @@ def set_parameters(metric, theta):
 def theta_values(theta):
     """theta (a 1-D tensor or sequence of len(PARAMETER_NAMES) values) -> list of Python floats; refuses what the metric cannot
     be evaluated under.  A host tensor is read without touching the GPU."""
-    t = theta.detach() if isinstance(theta, torch.Tensor) else torch.as_tensor(np.asarray(theta, dtype=np.float64))
-    if t.dim() != 1 or t.shape[0] != len(PARAMETER_NAMES):
-        raise RuntimeError("theta must be a 1-D vector of the %d parameters of PARAMETER_NAMES, got shape %s"
-                           % (len(PARAMETER_NAMES), tuple(t.shape)))
-    if not t.is_floating_point():
-        raise RuntimeError("theta must be a float32 or float64 tensor, got %s" % t.dtype)
-    vals = [float(v) for v in t.to(device="cpu", dtype=torch.float64).tolist()]
-    bad = [PARAMETER_NAMES[i] for i, v in enumerate(vals) if not math.isfinite(v)]
-    if bad:
-        raise RuntimeError("theta has non-finite entries: %s" % ", ".join(bad))
+    vals = vector_values("theta", "PARAMETER_NAMES", theta)
     for name in _POSITIVE:
         if not vals[_IDX[name]] > 0:
             raise RuntimeError("theta: %s must be positive (an exponent of the model), got %g" % (name, vals[_IDX[name]]))
@@ -90,16 +88,7 @@ def set_temporal_parameters(metric, phi):
 def phi_values(phi):
     """phi (a 1-D tensor or sequence of the 2 values of TEMPORAL_PARAMETER_NAMES) -> list of Python floats; refuses what no
     temporal filter can be made from.  A host tensor is read without touching the GPU."""
-    t = phi.detach() if isinstance(phi, torch.Tensor) else torch.as_tensor(np.asarray(phi, dtype=np.float64))
-    if t.dim() != 1 or t.shape[0] != len(TEMPORAL_PARAMETER_NAMES):
-        raise RuntimeError("temporal must be a 1-D vector of the %d parameters of TEMPORAL_PARAMETER_NAMES, got shape %s"
-                           % (len(TEMPORAL_PARAMETER_NAMES), tuple(t.shape)))
-    if not t.is_floating_point():
-        raise RuntimeError("temporal must be a float32 or float64 tensor, got %s" % t.dtype)
-    vals = [float(v) for v in t.to(device="cpu", dtype=torch.float64).tolist()]
-    bad = [TEMPORAL_PARAMETER_NAMES[i] for i, v in enumerate(vals) if not math.isfinite(v)]
-    if bad:
-        raise RuntimeError("temporal has non-finite entries: %s" % ", ".join(bad))
+    vals = vector_values("temporal", "TEMPORAL_PARAMETER_NAMES", phi)
     for name, v in zip(TEMPORAL_PARAMETER_NAMES, vals):
         if not v > 0:
             raise RuntimeError("temporal: %s must be positive (a width and a time of the log-Gaussian filter), got %g" % (name, v))
@@ -275,141 +264,91 @@ class _Sums:
     def __init__(self, metric, W, H, n_bands, planes, gb, total):
         dev = metric.device
         self.W, self.H, self.n_bands, self.planes, self.gb = W, H, n_bands, planes, gb
-        self.maps_arr, self._maps = metric._band_maps(gb, W, H, n_bands, contrast_planes=planes)
-        nbytes = C.c_size_t(0)
-        nat.check(nat.lib().fvvdp_param_sums_workspace(W, H, n_bands, gb, C.byref(nbytes)))
-        self.work_bytes = nbytes.value
-        self.work = torch.empty((nbytes.value + 7) // 8, dtype=torch.float64, device=dev)
+        self.maps = Maps(metric, W, H, n_bands, planes, gb)
+        self.maps_arr, self.q_scratch = self.maps.maps_arr, self.maps.q_scratch              # (tools read them here)
+        self.work_bytes, self.work = workspace(nat.lib().fvvdp_param_sums_workspace, W, H, n_bands, gb, dtype=torch.float64)
         self.batch_sums = torch.empty((n_bands, 2, gb, nat.PARAM_SUMS), dtype=torch.float64, device=dev)
         self.sums = torch.empty((n_bands, 2, total, nat.PARAM_SUMS), dtype=torch.float64, device=dev)
-        self.q_scratch = torch.empty((n_bands, 2, gb), dtype=torch.float32, device=dev)
-        self.jod_scratch = torch.empty(gb, dtype=torch.float32, device=dev)
         self.npx = torch.tensor([float(w * h) for w, h in metric._level_sizes(W, H, n_bands)[:n_bands]], dtype=torch.float64)
 
     def reduce(self, prm, b0, nb, stream):
         """The maps of the nb slots just written -> columns [b0, b0 + nb) of self.sums."""
         out = self.batch_sums.view(-1)[:self.n_bands * 2 * nb * nat.PARAM_SUMS].view(self.n_bands, 2, nb, nat.PARAM_SUMS)
         nat.check(nat.lib().fvvdp_param_sums(self.W, self.H, self.n_bands, nb, self.planes, C.byref(prm), self.maps_arr,
-                                             C.c_void_p(out.data_ptr()), C.c_void_p(self.work.data_ptr()), self.work_bytes, stream))
+                                             _ptr(out), _ptr(self.work), self.work_bytes, stream))
         self.sums[:, :, b0:b0 + nb] = out
+
+    def drop_maps(self):
+        """The maps are transient: only Q and the sums outlive the forward."""
+        self.maps = self.maps_arr = self.q_scratch = None
 
 
 def _images_forward(metric, t, r, fix, vals, want_sums):
     """The launches of fvvdp._predict_image_group (no heat maps, no flags read back) under theta -> (JOD [B], Q [bands, 2, B],
     _Sums or None).  t, r: [B, C, H, W] on any device."""
-    B, C_ch, height, width = t.shape
-    dev = metric.device
-    n_bands, rho_band = metric._band_count(width, height)
     if t.dtype != r.dtype:
         t, r = metric._to_unit_float(t), metric._to_unit_float(r)
-    td, rd = t.to(dev).contiguous(), r.to(dev).contiguous()
-    dtype, e = metric._image_eotf(td.dtype)
-    w = metric._rgb2y()
-    batch = metric._batch_size(width, height, 2, B)
-    ctx = metric._context(width, height, n_bands, 2, batch, rho_band)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    Q = torch.zeros((n_bands, 2, B), dtype=torch.float32, device=dev)
-    jod = torch.empty(B, dtype=torch.float32, device=dev)
-    prm, pp = native_params_of(vals), pool_params_of(vals)
-    lib = nat.lib()
+    s = ImageSetup(metric, t.to(metric.device).contiguous(), r.to(metric.device).contiguous(),
+                   prm=native_params_of(vals), pp=pool_params_of(vals))
     sums = None
-
-    def ingest(b0, nb):
-        tp = (C.c_void_p * nb)(*[td[k].data_ptr() for k in range(b0, b0 + nb)])
-        rp = (C.c_void_p * nb)(*[rd[k].data_ptr() for k in range(b0, b0 + nb)])
-        nat.check(lib.fvvdp_images_channels(ctx.handle, tp, rp, nb, dtype, C_ch, height * width, C.byref(e), nat.fptr(w), 0,
-                                            None, stream))
-
-    with _UnderTheta(metric, ctx, prm):
-        for b0 in range(0, B, batch):
-            nb = min(batch, B - b0)
-            ingest(b0, nb)
-            fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
-            nat.check(lib.fvvdp_images_forward_pool(ctx.handle, nb, C.c_void_p(Q.data_ptr()), B, b0, fx, g, None, C.byref(pp),
-                                                    C.c_void_p(jod.data_ptr() + 4 * b0), stream))
+    with _UnderTheta(metric, s.ctx, s.prm):
+        jod, Q = forward_images(s, fix)
         if want_sums:
-            gb = grad_batch_size(metric, width, height, n_bands, batch, 7)
-            sums = _Sums(metric, width, height, n_bands, 2, gb, B)
-            for b0 in range(0, B, gb):
-                nb = min(gb, B - b0)
-                ingest(b0, nb)
-                fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
-                nat.check(lib.fvvdp_images_forward_pool(ctx.handle, nb, C.c_void_p(sums.q_scratch.data_ptr()), nb, 0, fx, g,
-                                                        sums.maps_arr, C.byref(pp), C.c_void_p(sums.jod_scratch.data_ptr()), stream))
-                sums.reduce(prm, b0, nb, stream)
-            sums._maps = sums.maps_arr = None            # the maps are transient: only Q and the sums outlive the forward
+            gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch, 7)
+            sums = _Sums(metric, s.W, s.H, s.n_bands, 2, gb, s.B)
+            for b0, nb in batches(s.B, gb):
+                s.write_maps(sums.maps, fix, b0, nb)
+                sums.reduce(s.prm, b0, nb, s.stream)
+            sums.drop_maps()
     return jod, Q, sums
 
 
 class _TapGrad:
-    """Buffers of the tap gradient for a clip of N frames in backward batches of up to gb: the clip-long level-0 gradients of
-    both sides, the workspaces of the two level-0 backward passes, the slope planes, the luminance frames under a batch's
-    windows, workspace and result of fvvdp_tap_grad, and the running dJOD/dtaps [2, fl] (float64, added in frame order).
-    Checked against the free device memory first: a sentence instead of an out-of-memory error."""
+    """What the tap gradient of the clip of the setup s holds beside a backward's buffers, in backward batches of up to gb: the
+    luminance frames under a batch's windows, workspace and result of fvvdp_tap_grad, and the running dJOD/dtaps [2, fl]
+    (float64, added in frame order).  self.buf: the grad_passes.ClipBuffers of the two level-0 backward passes (clip-long
+    gradients of both sides, their workspaces, maps and slope planes), whose memory check covers all of this."""
 
-    def __init__(self, metric, W, H, n_bands, gb, N, fl, with_scale=False):
-        from .image_grad import slope_planes
-        dev, HW = metric.device, H * W
-        lib = nat.lib()
-        vb, rb, tb = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        nat.check(lib.fvvdp_video_grad_workspace(W, H, n_bands, gb, C.byref(vb)))
-        nat.check(lib.fvvdp_ref_grad_workspace(W, H, n_bands, gb, 2, C.byref(rb)))
-        nat.check(lib.fvvdp_tap_grad_workspace(W, H, fl, C.byref(tb)))
-        n_lum = min(N, fl - 1 + gb)
-        px = sum(w * h for w, h in metric._level_sizes(W, H, n_bands)[:n_bands])
+    def __init__(self, metric, s, gb, with_scale=False):
+        dev, HW, lib = metric.device, s.H * s.W, nat.lib()
+        vb = workspace_bytes(lib.fvvdp_video_grad_workspace, s.W, s.H, s.n_bands, gb)
+        rb = workspace_bytes(lib.fvvdp_ref_grad_workspace, s.W, s.H, s.n_bands, gb, 2)
+        self.tap_bytes = workspace_bytes(lib.fvvdp_tap_grad_workspace, s.W, s.H, s.fl)
+        n_lum = min(s.N, s.fl - 1 + gb)
         lum_bytes = 2 * n_lum * HW * 4
-        need = gb * px * 4 * (9 + 2) + vb.value + rb.value + tb.value + 2 * N * HW * 8 + lum_bytes
-        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-        if need > free:
-            raise RuntimeError("calibration_jod_video: the gradient for the temporal parameters of this clip needs %.1f GB of "
-                               "device memory (maps and workspace of %d frames, the clip-long level-0 gradients of both sides "
-                               "and %.2f GB of luminance frames under a batch's windows) and %.1f GB are free; set a smaller "
-                               "metric.grad_batch or a shorter clip" % (need / 1e9, gb, lum_bytes / 1e9, free / 1e9))
-        self.W, self.H, self.n_bands, self.N, self.fl, self.n_lum = W, H, n_bands, N, fl, n_lum
-        self.g0 = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
-        self.g0_r = torch.empty((N, 2, H, W), dtype=torch.float32, device=dev)
-        self.work = torch.empty((vb.value + 3) // 4, dtype=torch.float32, device=dev)
-        self.work_r = torch.empty((rb.value + 3) // 4, dtype=torch.float32, device=dev)
-        self.work_bytes, self.ref_bytes, self.tap_bytes = vb.value, rb.value, tb.value
-        self.slopes, self._slopes = slope_planes(metric, gb, W, H, n_bands)
-        self.lum = torch.empty((2, n_lum, H, W), dtype=torch.float32, device=dev)
-        self.tap_work = torch.empty((tb.value + 7) // 8, dtype=torch.float64, device=dev)
-        self.out = torch.empty((2, fl), dtype=torch.float64, device=dev)
-        self.dtaps = torch.zeros((2, fl), dtype=torch.float64, device=dev)
+        self.s = s
+        self.buf = ClipBuffers("calibration_jod_video", metric, s, None, gb, vb, True, rb, results=False, head=False, maps=False,
+                               extra_bytes=self.tap_bytes + lum_bytes, lum_bytes=lum_bytes)
+        self.lum = torch.empty((2, n_lum, s.H, s.W), dtype=torch.float32, device=dev)
+        self.tap_work = work_tensor(self.tap_bytes, torch.float64)
+        self.out = torch.empty((2, s.fl), dtype=torch.float64, device=dev)
+        self.dtaps = torch.zeros((2, s.fl), dtype=torch.float64, device=dev)
         self.gamma = torch.ones(1, dtype=torch.float32, device=dev)
-        self.flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.scale = torch.zeros((2, fl), dtype=torch.float64, device=dev) if with_scale else None
+        self.scale = torch.zeros((2, s.fl), dtype=torch.float64, device=dev) if with_scale else None
 
-    def batch(self, feeder, prm, pp, Q, maps_arr, idx, b0, nb, stream):
-        """The maps of output frames [b0, b0 + nb) (slope planes included) -> their share of dJOD/dtaps, added to self.dtaps.
-        idx: the batch's slice of the window index list (fl - 1 + nb source frames, oldest first)."""
-        lib = nat.lib()
-        W, H, HW = self.W, self.H, self.H * self.W
-        nat.check(lib.fvvdp_video_grad_frames(W, H, self.n_bands, nb, C.byref(prm), C.byref(pp), C.c_void_p(Q.data_ptr()), self.N, b0,
-                                              C.c_void_p(self.gamma.data_ptr()), maps_arr, C.c_void_p(self.g0.data_ptr()),
-                                              C.c_void_p(self.work.data_ptr()), self.work_bytes, stream))
-        nat.check(lib.fvvdp_video_ref_grad_frames(W, H, self.n_bands, nb, C.byref(prm), C.byref(pp), C.c_void_p(Q.data_ptr()), self.N,
-                                                  b0, C.c_void_p(self.gamma.data_ptr()), maps_arr, self.slopes,
-                                                  C.c_void_p(self.g0_r.data_ptr()), C.c_void_p(self.work_r.data_ptr()),
-                                                  self.ref_bytes, stream))
+    def batch(self, prm, Q, b0, nb):
+        """The maps of output frames [b0, b0 + nb) (slope planes included) -> their share of dJOD/dtaps, added to self.dtaps."""
+        s, buf = self.s, self.buf
+        W, H, HW, fl = s.W, s.H, s.H * s.W, s.fl
+        level0_backward(buf, s, prm, Q, s.N, b0, nb, self.gamma)
+        idx = s.widx[b0:b0 + fl - 1 + nb]                  # the batch's window list: fl - 1 + nb source frames, oldest first
         frames = np.unique(idx)
         nu = len(frames)
         pos = np.ascontiguousarray(np.searchsorted(frames, idx), dtype=np.int32)
         lum = self.lum.view(-1)[:2 * nu * HW]
-        feeder.luminance(frames, lum, self.flag, stream)
-        nat.check(lib.fvvdp_tap_grad(W, H, nb, self.fl, C.c_void_p(self.g0.data_ptr() + b0 * 2 * HW * 4),
-                                     C.c_void_p(self.g0_r.data_ptr() + b0 * 2 * HW * 4), C.c_void_p(lum.data_ptr()),
-                                     C.c_void_p(lum.data_ptr() + nu * HW * 4), pos.ctypes.data_as(C.POINTER(C.c_int32)), nu,
-                                     C.c_void_p(self.out.data_ptr()), C.c_void_p(self.tap_work.data_ptr()), self.tap_bytes, stream))
+        s.feeder.luminance(frames, lum, buf.oob, s.stream)
+        nat.check(nat.lib().fvvdp_tap_grad(W, H, nb, fl, _ptr(buf.g0, b0 * 2 * HW * 4), _ptr(buf.g0_r, b0 * 2 * HW * 4), _ptr(lum),
+                                           _ptr(lum, nu * HW * 4), pos.ctypes.data_as(C.POINTER(C.c_int32)), nu, _ptr(self.out),
+                                           _ptr(self.tap_work), self.tap_bytes, s.stream))
         self.dtaps += self.out
         if self.scale is not None:
             # the yardstick of the kernel's rounding: sum |g0 Y| per entry, with torch, in float64
             widx = torch.as_tensor(pos.astype(np.int64), device=self.out.device)
             t = torch.arange(nb, device=self.out.device)
-            for k in range(self.fl):
-                q = widx[t + self.fl - 1 - k]
-                for g, y in ((self.g0, self.lum.view(-1)[:nu * HW].view(nu, H, W)),
-                             (self.g0_r, self.lum.view(-1)[nu * HW:2 * nu * HW].view(nu, H, W))):
+            for k in range(fl):
+                q = widx[t + fl - 1 - k]
+                for g, y in ((buf.g0, self.lum.view(-1)[:nu * HW].view(nu, H, W)),
+                             (buf.g0_r, self.lum.view(-1)[nu * HW:2 * nu * HW].view(nu, H, W))):
                     self.scale[:, k] += (g[b0:b0 + nb].abs().double() * y[q].double()[:, None].abs()).sum(dim=(0, 2, 3))
 
 
@@ -417,82 +356,45 @@ def _video_pass(metric, vs, fixation_point, vals, want_sums, pvals=None, want_ta
     """The launches of fvvdp._predict_on_device (sync=False, no heat maps) under theta -> (JOD 0-d, Q [bands, 2, N], _Sums or
     None, number of temporal channels, dJOD/dtaps [2, fl] float64 or None).  pvals: the values of TEMPORAL_PARAMETER_NAMES the
     taps are made from (None: the metric's own taps); want_taps: also the gradient of the JOD with respect to the taps."""
-    from .fvvdp import _PipelinedSourceFeeder, temporal_filters
-    from .video_grad import video_grad_planes
     height, width, N = vs.get_video_size()
-    dev = metric.device
     fix = metric._fixation(fixation_point, width, height, N) if metric.foveated else None
     pl = metric._clip_plan(vs)
-    if isinstance(pl.feeder, _PipelinedSourceFeeder):
-        raise RuntimeError("calibration_jod_video needs a display model with a closed form for float input (sRGB, gamma, PQ, "
-                           "linear or absolute); a user photometry class has none")
-    n_bands, planes, fl, taps, widx = pl.n_bands, pl.planes, pl.fl, pl.taps, pl.widx
+    PlanClipSetup.refuse_user_photometry("calibration_jod_video", pl)
+    taps = None
     if pvals is not None:
-        if planes != 4:
+        if pl.planes != 4:
             raise RuntimeError("calibration_jod_video: temporal= needs a clip of at least 2 frames (a single frame has no "
                                "temporal filter)")
         # the taps under phi: never cached (an optimiser makes a new phi per step), never written to the metric
-        taps = np.ascontiguousarray(temporal_filters(vs.get_frames_per_second(), fl, pvals[0], pvals[1]).numpy(), dtype=np.float32)
-    ctx = metric._context(width, height, n_bands, planes, pl.batch, pl.rho_band)
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    nq = n_bands * 2 * N
-    res = torch.zeros(nq + 2, dtype=torch.float32, device=dev)          # Q_per_ch | range flag | JOD, as predict lays it out
-    Q = res[:nq].view(n_bands, 2, N)
-    oob = res[nq:nq + 1].view(torch.int32)
-    prm, pp = native_params_of(vals), pool_params_of(vals)
-    lib = nat.lib()
-    sums = None
-    with _UnderTheta(metric, ctx, prm):
-        b0 = 0
-        for nb in pl.schedule:
-            idx = np.ascontiguousarray(widx[b0:b0 + fl - 1 + nb])
-            pl.feeder(ctx, idx, taps, fl, nb, oob, stream)
-            fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
-            if b0 + nb == N:
-                nat.check(lib.fvvdp_bands_forward_pool(ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None, C.byref(pp),
-                                                       C.c_void_p(res[nq + 1:].data_ptr()), stream))
-            else:
-                nat.check(lib.fvvdp_bands_forward(ctx.handle, nb, C.c_void_p(Q.data_ptr()), N, b0, fx, g, None, stream))
-            b0 += nb
-        if want_taps:
-            # one ingest and one map-writing pass per backward batch (slope planes on, as jod_video(wrt="both")): theta's sums
-            # and the two level-0 backward passes read the same maps
-            gb = grad_batch_size(metric, width, height, n_bands, pl.batch, video_grad_planes("both"))
-            gb = max(1, min(gb, nat.TAPS_MAX_POSITIONS - (fl - 1)))
-            tg = _TapGrad(metric, width, height, n_bands, gb, N, fl, with_scale)
-            sums = _Sums(metric, width, height, n_bands, planes, gb, N)
-            for b0 in range(0, N, gb):
-                nb = min(gb, N - b0)
-                idx = np.ascontiguousarray(widx[b0:b0 + fl - 1 + nb])
-                pl.feeder(ctx, idx, taps, fl, nb, tg.flag, stream)
-                fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
-                nat.check(lib.fvvdp_ctx_set_slope_maps(ctx.handle, tg.slopes))
-                try:
-                    nat.check(lib.fvvdp_bands_forward(ctx.handle, nb, C.c_void_p(sums.q_scratch.data_ptr()), nb, 0, fx, g,
-                                                      sums.maps_arr, stream))
-                finally:
-                    nat.check(lib.fvvdp_ctx_set_slope_maps(ctx.handle, None))
+        taps = np.ascontiguousarray(temporal_filters(vs.get_frames_per_second(), pl.fl, pvals[0], pvals[1]).numpy(), dtype=np.float32)
+    s = PlanClipSetup("calibration_jod_video", metric, pl, native_params_of(vals), pool_params_of(vals), taps)
+    sums = dtaps = None
+    with _UnderTheta(metric, s.ctx, s.prm):
+        jod, Q = forward_clip(s, fix)
+        if want_taps or want_sums:
+            # one ingest and one map-writing pass per backward batch; for the taps with the slope planes on, as
+            # jod_video(wrt="both"): theta's sums and the two level-0 backward passes read the same maps
+            gb = grad_batch_size(metric, s.W, s.H, s.n_bands, s.batch,
+                                 video_grad_planes("both") if want_taps else (9 if s.planes == 4 else 7))
+            if want_taps:
+                gb = max(1, min(gb, nat.TAPS_MAX_POSITIONS - (s.fl - 1)))
+            tg = _TapGrad(metric, s, gb, with_scale) if want_taps else None
+            sums = _Sums(metric, s.W, s.H, s.n_bands, s.planes, gb, N)
+            if tg:
+                tg.buf.use_maps(sums.maps)                 # (made last, as the sums' maps always were: the allocator's order)
+            flag = tg.buf.oob if tg else torch.zeros(1, dtype=torch.int32, device=metric.device)
+            for b0, nb in batches(N, gb):
+                s.write_maps(sums.maps, fix, b0, nb, flag)
                 if want_sums:
-                    sums.reduce(prm, b0, nb, stream)
-                tg.batch(pl.feeder, prm, pp, Q, sums.maps_arr, idx, b0, nb, stream)
-            sums._maps = sums.maps_arr = None
+                    sums.reduce(s.prm, b0, nb, s.stream)
+                if tg:
+                    tg.batch(s.prm, Q, b0, nb)
+            sums.drop_maps()
             if not want_sums:
                 sums = None
-            return res[nq + 1], Q, sums, planes // 2, (tg.dtaps, tg.scale) if with_scale else tg.dtaps
-        if want_sums:
-            gb = grad_batch_size(metric, width, height, n_bands, pl.batch, 9 if planes == 4 else 7)
-            sums = _Sums(metric, width, height, n_bands, planes, gb, N)
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            for b0 in range(0, N, gb):
-                nb = min(gb, N - b0)
-                idx = np.ascontiguousarray(widx[b0:b0 + fl - 1 + nb])
-                pl.feeder(ctx, idx, taps, fl, nb, flag, stream)
-                fx, g, _keep = metric._fov_args(ctx, fix, b0, nb, n_bands, width, height)
-                nat.check(lib.fvvdp_bands_forward(ctx.handle, nb, C.c_void_p(sums.q_scratch.data_ptr()), nb, 0, fx, g,
-                                                  sums.maps_arr, stream))
-                sums.reduce(prm, b0, nb, stream)
-            sums._maps = sums.maps_arr = None
-    return res[nq + 1], Q, sums, planes // 2, None
+            if tg:
+                dtaps = (tg.dtaps, tg.scale) if with_scale else tg.dtaps
+    return jod, Q, sums, s.planes // 2, dtaps
 
 
 def _video_forward(metric, vs, fixation_point, vals, want_sums):
@@ -505,7 +407,6 @@ def tap_gradient(metric, test, reference, theta, temporal, dim_order="BCFHW", fr
     """dJOD/dtaps [2, fl] (float64, on the metric's device) of one clip under theta and phi: what the forward of
     calibration_jod_video keeps when phi requires grad.  For tests and tools.  with_scale: also sum |g0 Y| of every entry, the
     yardstick of the tap-gradient kernel's rounding (include/fvvdp_hip_taps.h), made with torch."""
-    from .video_source import fvvdp_video_source_array
     vals, pvals = theta_values(theta), phi_values(temporal)
     vs = fvvdp_video_source_array(test, reference, frames_per_second, dim_order=dim_order,
                                   display_photometry=metric.display_photometry, color_space_name=metric.color_space)
@@ -518,7 +419,7 @@ class _CalibrationFunction(torch.autograd.Function):
     """theta -> JOD ([B] for images, 0-d for a clip).  `run(want_sums)` makes the forward under theta's values."""
 
     @staticmethod
-    def forward(ctx, theta, metric, vals, run, per_column):
+    def forward(ctx, theta, metric, run, vals, per_column):
         want = bool(ctx.needs_input_grad[0])
         with torch.cuda.device(metric.device):
             jod, Q, sums, channels = run(want)
@@ -575,27 +476,10 @@ class _TemporalCalibrationFunction(torch.autograd.Function):
         return g_theta, g_phi, None, None, None, None
 
 
-def _refuse(name, metric, test, reference, other):
-    for a in (test, reference):
-        if isinstance(a, torch.Tensor) and a.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("%s differentiates the JOD with respect to the model parameters only and this test or reference "
-                               "requires grad; detach it (gradients for the images or frames: %s)" % (name, other))
-    if metric.do_heatmap:
-        raise RuntimeError("%s makes no heat maps: build the metric with heatmap=None" % name)
-
-
-def _apply(metric, theta, vals, run, per_column):
-    if isinstance(theta, torch.Tensor) and theta.requires_grad and torch.is_grad_enabled():
-        return _CalibrationFunction.apply(theta, metric, vals, run, per_column)
-    with torch.cuda.device(metric.device):
-        return run(False)[0]
-
-
 def calibration_jod_images(metric, test, reference, theta, dim_order="BCHW", fixation_point=None):
     """fvvdp.calibration_jod_images (see there)."""
-    from .fvvdp import _image_stack
     vals = theta_values(theta)
-    _refuse("calibration_jod_images", metric, test, reference, "jod_images")
+    _refuse("calibration_jod_images", "the model parameters", metric, test, reference, "jod_images")
     t, r = _image_stack(test, reference, dim_order)
     metric._check_device()
     fix = metric._fixation(fixation_point, t.shape[3], t.shape[2], t.shape[0]) if metric.foveated else None
@@ -604,14 +488,12 @@ def calibration_jod_images(metric, test, reference, theta, dim_order="BCHW", fix
         jod, Q, sums = _images_forward(metric, t, r, fix, vals, want_sums)
         return jod, Q, sums, 1
 
-    return _apply(metric, theta, vals, run, True)
+    return _apply(_CalibrationFunction, metric, theta, run, vals, True)
 
 
 def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", frames_per_second=0, fixation_point=None,
                           temporal=None):
     """fvvdp.calibration_jod_video (see there)."""
-    from .fvvdp import filter_length
-    from .video_source import fvvdp_video_source_array
     vals = theta_values(theta)
     pvals = None if temporal is None else phi_values(temporal)
     phi_grad = isinstance(temporal, torch.Tensor) and temporal.requires_grad and torch.is_grad_enabled()
@@ -620,7 +502,7 @@ def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", fra
                            "filter has %d taps, the tap-gradient kernel covers %d (256 frames per second); the forward runs "
                            "with a temporal= that does not require grad"
                            % (filter_length(frames_per_second), nat.VIDEO_GRAD_MAX_TAPS))
-    _refuse("calibration_jod_video", metric, test, reference, "jod_video")
+    _refuse("calibration_jod_video", "the model parameters", metric, test, reference, "jod_video")
     d = dim_order.upper()
     if "B" in d and len(d) == len(test.shape) and test.shape[d.index("B")] != 1:
         raise RuntimeError("calibration_jod_video takes one clip per call (B must be 1)")
@@ -632,13 +514,14 @@ def calibration_jod_video(metric, test, reference, theta, dim_order="BCFHW", fra
         def run(want_sums):
             return _video_forward(metric, vs, fixation_point, vals, want_sums)
 
-        return _apply(metric, theta, vals, run, False)
+        return _apply(_CalibrationFunction, metric, theta, run, vals, False)
 
     def run_phi(want_sums, want_taps=False):
         return _video_pass(metric, vs, fixation_point, vals, want_sums, pvals, want_taps)
 
     if not phi_grad:
-        return _apply(metric, theta, vals, lambda want_sums: run_phi(want_sums)[:4], False)
+        run = lambda want_sums: run_phi(want_sums)[:4]                                     # noqa: E731
+        return _apply(_CalibrationFunction, metric, theta, run, vals, False)
     fps = float(vs.get_frames_per_second())
     return _TemporalCalibrationFunction.apply(theta, temporal, metric, vals, run_phi,
                                               (fps, filter_length(fps), pvals[0], pvals[1]))

@@ -430,7 +430,10 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
             // (tan(a+d)-tan(a))/tan(d) == cos(d)/(cos(a)cos(a+d)): evaluated in this form it needs no slow tan and
             // does not lose digits to the reference's fp32 finite difference (whose noise, ~5e-4, bounds parity).
             const float dx = vx - gx, dy = vy - gy;
-            const float ecc = __builtin_amdgcn_sqrtf(dx * dx + dy * dy);
+            // the fused form spelled out: left to the compiler, which of the two products it folds into the add differed between
+            // the unrolled instances of `step` (the odd row of step<3> came out 1 ulp off in ecc^2, up to 4e-6 in S), so a pixel's
+            // S and D depended on the loop phase, i.e. on the chunk height, that computed it
+            const float ecc = __builtin_amdgcn_sqrtf(fmaf(dy, dy, dx * dx));
             const float eq = __builtin_amdgcn_sqrtf(fminf(fmaxf(ecc, a.ecc_lo), a.ecc_hi));
             // interval on each (uniform) axis from the grid, fraction from the stored knots incl. interp.py:16's +1e-6
             auto axis = [&](int ax, float q, int lo, int hi, int& k, float& f) {

@@ -81,6 +81,7 @@ struct CtxEnv {
     bool temporal_scalar = false; // FVVDP_TEMPORAL_SCALAR=1: the per-pixel temporal kernels (fallbacks for unaligned sizes)
     bool debug_variant = false;   // FVVDP_DEBUG_VARIANT=1: print which kernel variants are launched (tests)
     int gaze_group = 0;           // FVVDP_GAZE_GROUP=1 / 2 / 4 / 8: largest gaze group of one multigaze_kernel launch (tests, A/B runs)
+    int band_cr = 0;              // FVVDP_BAND_CR=n >= 2: chunk height (coarse rows) of every one-level launch instead of chunking()'s (tests, A/B runs)
     bool yuv_general = false;     // FVVDP_YUV_GENERAL_MATRIX=1: YUV ingest with the nine-term colour matrix also where it has the ITU shape (tests)
 };
 static CtxEnv read_env() {
@@ -103,6 +104,7 @@ static CtxEnv read_env() {
     e.debug_variant = getenv("FVVDP_DEBUG_VARIANT") != nullptr;
     e.yuv_general = getenv("FVVDP_YUV_GENERAL_MATRIX") != nullptr;
     e.gaze_group = num("FVVDP_GAZE_GROUP", 0);
+    e.band_cr = num("FVVDP_BAND_CR", 0);
     return e;
 }
 
@@ -1237,6 +1239,20 @@ static int build_sublut(fvvdp_ctx* c, const fvvdp_geom* g, hipStream_t st) {
     return FVVDP_OK;
 }
 
+// FOVM of the band_kernel<P, dbg, FOVM> that a one-level launch takes (see band_item)
+static int band_fovm(const BandArgs& a, bool dbg, bool fov) {
+    if (!fov) return 0;
+    if (dbg) return 2;
+    if (a.lut_lds && a.rmap && !a.mvx) return 1;
+    return a.lut_lds ? 3 : 2;
+}
+
+// FVVDP_DEBUG_VARIANT (tests): the instantiation and the plan of one one-level launch of level b over n frames
+static void debug_band_line(const fvvdp_ctx* c, int b, const BandArgs& a, int n, bool dbg, bool fov) {
+    fprintf(stderr, "fvvdp: level %d: band_kernel<%d, %s, %d>, n %d, n_strips %d, n_chunks %d, cr %d, rw %d, lut_lds %d\n",
+            b, c->P, dbg ? "true" : "false", band_fovm(a, dbg, fov), n, a.n_strips, a.n_chunks, a.cr, a.rw, a.lut_lds);
+}
+
 template <int P>
 static void launch_band(const BandArgs& a, int nblocks, bool dbg, bool fov, hipStream_t st, float* d_slope = nullptr) {
     dim3 grid(nblocks), block(64);
@@ -1252,9 +1268,10 @@ static void launch_band(const BandArgs& a, int nblocks, bool dbg, bool fov, hipS
         // dynamic LDS: [LUT slice of the band (mode 1)] + vertical view angle of every band row
         const size_t lds_vy = (size_t)a.h * sizeof(float);
         const size_t lds_lut = (size_t)FOV_PLANE * a.rw * sizeof(float4);
+        const int fovm = band_fovm(a, dbg, fov);
         if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 2>), gridf, blockf, lds_vy, st, with_slope());
-        else if (a.lut_lds && a.rmap && !a.mvx) hipLaunchKernelGGL((band_kernel<P, false, 1>), gridf, blockf, lds_lut + lds_vy, st, a);
-        else if (a.lut_lds) hipLaunchKernelGGL((band_kernel<P, false, 3>), gridf, blockf, lds_lut + lds_vy, st, a);
+        else if (fovm == 1) hipLaunchKernelGGL((band_kernel<P, false, 1>), gridf, blockf, lds_lut + lds_vy, st, a);
+        else if (fovm == 3) hipLaunchKernelGGL((band_kernel<P, false, 3>), gridf, blockf, lds_lut + lds_vy, st, a);
         else hipLaunchKernelGGL((band_kernel<P, false, 2>), gridf, blockf, lds_vy, st, a);
     } else {
         if (dbg) hipLaunchKernelGGL((band_kernel<P, true, 0>), grid, block, 0, st, with_slope());
@@ -1298,6 +1315,10 @@ static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, boo
     a.hc = c->lh[b + 1];
     a.n_strips = band_strips(a.wc);
     chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, a.n_chunks, a.cr);
+    if (c->env.band_cr >= 2) {                           // FVVDP_BAND_CR: taller chunks than chunking() picks (fewer, never more, than max_blk[] holds)
+        a.cr = c->env.band_cr > a.hc ? a.hc : c->env.band_cr;
+        a.n_chunks = (a.hc + a.cr - 1) / a.cr;
+    }
     a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
     a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
     a.csf_y = c->csf_y;
@@ -1517,6 +1538,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
         const int nblk = a.n_strips * a.n_chunks;
         if (nblk > c->max_blk[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
         a.n_items = nblk * n;
+        if (c->env.debug_variant) debug_band_line(c, b, a, n, dbg, fov);
         {
             Timed tm(c, 1 + b, st);
             if (c->P == 4) launch_band<4>(a, nblk * n, dbg, fov, st, c->slope[b]);
@@ -1651,6 +1673,7 @@ static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const floa
             for (int g = 0; g < n_gazes; ++g) {
                 a.fix = d_gaze + (size_t)g * gaze_stride;
                 a.partial = work + (size_t)g * row + off[b];
+                if (c->env.debug_variant) debug_band_line(c, b, a, n, false, true);
                 if (c->P == 4) launch_band<4>(a, a.n_items, false, true, st);
                 else launch_band<2>(a, a.n_items, false, true, st);
             }
@@ -1663,6 +1686,9 @@ static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const floa
             m[b].gaze = d_gaze + (size_t)g0 * gaze_stride;
             m[b].partial = work + (size_t)g0 * row + off[b];
             m[b].store_coarse = g0 == 0 ? 1 : 0;     // the later groups of a level read the same rows and leave the next level alone
+            if (c->env.debug_variant)
+                fprintf(stderr, "fvvdp: level %d: multigaze_kernel<%d, %d>, n %d, n_strips %d, n_chunks %d, cr %d, rw %d, lut_lds %d, store_coarse %d\n",
+                        b, c->P, ng, n, m[b].b.n_strips, m[b].b.n_chunks, m[b].b.cr, m[b].b.rw, m[b].b.lut_lds, m[b].store_coarse);
             if (c->P == 4) launch_multigaze<4>(m[b], ng, st);
             else launch_multigaze<2>(m[b], ng, st);
             g0 += ng;

@@ -31,6 +31,14 @@ class Pipeline:
                 y_log, tab = metric.csf_tables_1d(self.rho_band, self.n_bands)
                 nat.check(self.lib.fvvdp_ctx_set_csf_1d(self.handle, nat.fptr(y_log), nat.fptr(tab)))
         self.foveated = foveated
+        self.user_geometry = False
+
+    def set_view_maps(self):
+        """The metric's display geometry is a user subclass: hand its per-band view-direction / magnification maps to the context,
+        as predict() does (fvvdp._set_view_maps); bands_forward then passes the gazes as view directions and no geometry."""
+        with torch.cuda.device(self.dev):
+            self.m._set_view_maps(self, self.n_bands, self.W, self.H)
+        self.user_geometry = True
 
     def close(self):
         if self.handle:
@@ -93,8 +101,11 @@ class Pipeline:
         fx, g = None, None
         if fixation is not None:
             fxa = np.ascontiguousarray(fixation, dtype=np.float32).reshape(n, 2)
+            if self.user_geometry:
+                fxa = self.m._gaze_view_dirs(fxa, self.W, self.H)
+            else:
+                g = C.byref(self.m._geom_struct())
             fx = nat.fptr(fxa)
-            g = C.byref(self.m._geom_struct())
         nat.check(self.lib.fvvdp_bands_forward(self.handle, n, C.c_void_p(Q.data_ptr()), n, 0, fx, g, maps_arr, self.stream()))
         return (Q, maps) if want_maps else Q
 

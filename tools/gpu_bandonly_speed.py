@@ -29,5 +29,5 @@ for _ in range(reps):
 a = np.array(per_rep)
 tot = a.sum(axis=1)
 print("%s bands us/frame median [%s] | total median %.2f min %.2f max %.2f | Q00 %.6f" % (
-    " ".join("%s=%s" % (k, os.environ[k]) for k in ("FVVDP_BAND_FUSE", "FVVDP_BAND2_KR", "FVVDP_LIB") if k in os.environ),
+    " ".join("%s=%s" % (k, os.environ[k]) for k in ("FVVDP_BAND_FUSE", "FVVDP_BAND2_KR", "FVVDP_BAND_CR", "FVVDP_LIB") if k in os.environ),
     " ".join("%.2f" % x for x in np.median(a, axis=0)), np.median(tot), tot.min(), tot.max(), float(Q[0, 0, 0])), flush=True)

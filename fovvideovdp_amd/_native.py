@@ -210,22 +210,40 @@ HALF_SYMBOLS = {
     "fvvdp_video_grad_input_st": (C.c_int, _with_dtype(VIDEO_GRAD_SYMBOLS["fvvdp_video_grad_input"][1], 10)),
 }
 
+# include/fvvdp_hip_diffmap.h: the difference map before its power and the gradient of a per-pixel cotangent of the map (bound by
+# lib() as well)
+DIFFMAP_SYMBOLS = {
+    "fvvdp_heatmap_reconstruct_linear": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_void_p]),
+    "fvvdp_diffmap_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t),
+                                               C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fvvdp_diffmap_grad_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(PoolParams),
+                                            C.c_int, C.c_void_p, C.c_void_p, C.POINTER(BandMaps), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fvvdp_diffmap_images_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(PoolParams), C.c_int,
+                                            C.c_void_p, C.c_void_p, C.POINTER(BandMaps), C.POINTER(C.c_void_p), C.c_int, C.c_int,
+                                            C.c_size_t, C.POINTER(Eotf), C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.c_void_p,
+                                            C.c_size_t, C.c_void_p]),
+    "fvvdp_diffmap_video_grad_frames": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(PoolParams),
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(BandMaps), C.c_void_p,
+                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+DIFFMAP_JOD, DIFFMAP_LINEAR = 0, 1       # FVVDP_DIFFMAP_JOD, FVVDP_DIFFMAP_LINEAR
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Fifteen translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Sixteen translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
-    (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip) and the sums for the gradient with
-    respect to the display's photometry (display_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip), the sums for the gradient with
+    respect to the display's photometry (display_grad_launch.hip) and the gradients of the difference map (map_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
-                                                                                                                              "fvvdp_hip_display.h", "fvvdp_hip_half.h")]
+                                                                                                                              "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -256,6 +274,8 @@ def build(force=False, verbose=False):
     units += [(os.path.join(csrc, "tap_grad_launch.hip"), ["-fno-slp-vectorize"], os.path.join(objdir, "tap_grad_launch.o"))]
     # the sums behind the gradient with respect to the display's photometry (include/fvvdp_hip_display.h)
     units += [(os.path.join(csrc, "display_grad_launch.hip"), [], os.path.join(objdir, "display_grad_launch.o"))]
+    # the gradients of the difference map (include/fvvdp_hip_diffmap.h)
+    units += [(os.path.join(csrc, "map_grad_launch.hip"), [], os.path.join(objdir, "map_grad_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -283,7 +303,7 @@ def lib():
         for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()) + list(GRAD_SYMBOLS.items()) + \
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
-                list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()):
+                list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

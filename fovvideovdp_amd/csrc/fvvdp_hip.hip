@@ -25,6 +25,7 @@
 #include "fvvdp_hip_gaze.h"
 #include "fvvdp_hip_ref_grad.h"
 #include "fvvdp_hip_params.h"
+#include "fvvdp_hip_diffmap.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // errors
@@ -1979,8 +1980,9 @@ extern "C" int fvvdp_pool_jod(const float* d_Q, int n_bands, int n_channels, int
     return FVVDP_OK;
 }
 
-extern "C" int fvvdp_heatmap_reconstruct(fvvdp_ctx* c, int n, const float* const* h_dD, float w_transient, float beta_jod,
-                                         float jod_a_abs, float* d_out, void* stream) {
+// the levels of the heat-map reconstruction, coarse to fine; final_power: level 0 ends in ^beta_jod * jod_a_abs
+static int heatmap_levels(fvvdp_ctx* c, int n, const float* const* h_dD, float w_transient, float beta_jod, float jod_a_abs,
+                          bool final_power, float* d_out, void* stream) {
     if (!c || !h_dD || !d_out) return fail(FVVDP_EINVAL, "null argument");
     if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
     for (int b = 0; b < c->n_bands; ++b)
@@ -2006,12 +2008,23 @@ extern "C" int fvvdp_heatmap_reconstruct(fvvdp_ctx* c, int n, const float* const
         a.inv_m = (b == 0) ? 1.0f : 0.5f;                              // set_band divides by the band multiplier
         a.beta_jod = beta_jod;
         a.scale = jod_a_abs;
-        a.final_level = (b == 0);
+        a.final_level = (b == 0) && final_power;
         dim3 grid((a.w + 255) / 256, a.h, n), block(256);
         hipLaunchKernelGGL(heat_level_kernel, grid, block, 0, st, a);
     }
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
+}
+
+extern "C" int fvvdp_heatmap_reconstruct(fvvdp_ctx* c, int n, const float* const* h_dD, float w_transient, float beta_jod,
+                                         float jod_a_abs, float* d_out, void* stream) {
+    return heatmap_levels(c, n, h_dD, w_transient, beta_jod, jod_a_abs, true, d_out, stream);
+}
+
+// include/fvvdp_hip_diffmap.h: the same launches without the power and the scale of level 0
+extern "C" int fvvdp_heatmap_reconstruct_linear(fvvdp_ctx* c, int n, const float* const* h_dD, float w_transient, float* d_out,
+                                                void* stream) {
+    return heatmap_levels(c, n, h_dD, w_transient, 1.0f, 1.0f, false, d_out, stream);
 }
 
 extern "C" int fvvdp_heatmap_colorize(fvvdp_ctx* c, int n, const float* d_dmap, const float* h_knots, const float* h_rgb,

@@ -85,6 +85,41 @@ __device__ __forceinline__ float expand_t(const float* Y, int wf, int hf, int wc
     return s;
 }
 
+// ---- layer gradient of one band pixel and temporal channel ------------------------------------------------------------------
+// adj_layer_kernel's formula (grad_kernels.hpp), the powers in the forward's log2 / exp2 form (band_kernel.hpp): three
+// transcendental pairs per value instead of three powf.  s = S gain; s * m_lb = S gain m / L_bkg is d(T')/d(layer).  `a`: any
+// argument block with p, k_mask, beta, cmax_hi and dmax_hi (grad_fill_layer's members).
+//   PLANE_WEIGHT false: c is the band's pooling coefficient and the value is c D^(beta - 1) dD/dT' s m_lb (video_layer_one);
+//   PLANE_WEIGHT true:  c is a per-pixel weight that stands in the place of c D^(beta - 1) (map_level_kernel).
+template <bool PLANE_WEIGHT, class Args>
+__device__ __forceinline__ float layer_term(float c, float T, float R, float Dm, float s, float m_lb, float q, float m,
+                                            const Args& a) {
+    // zero: no weight, D == 0 (an identical pixel), the d_max clamp or the contrast clamp binds
+    if (!(c != 0.0f && Dm > 0.0f && Dm < a.dmax_hi && T < m * a.cmax_hi)) return 0.0f;
+    const float Tp = T * s, Rp = R * s;
+    const float u = Tp - Rp, au = fabsf(u);
+    const float aT = fabsf(Tp), aR = fabsf(Rp);
+    const float M = a.k_mask * fminf(aT, aR);
+    const float Mq = M > 0.0f ? fast_exp2(q * fast_log2(M)) : 0.0f;
+    const float den = 1.0f + Mq;
+    const float lnum = a.p * fast_log2(au);                 // au == 0 (with D > 0 it cannot be): -inf, num = 0
+    const float num = fast_exp2(lnum);
+    const float rden = fast_rcp(den);
+    const float D = num * rden;
+    // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
+    float dD = au > 0.0f ? copysignf(a.p * num * fast_rcp(au), u) * rden : 0.0f;
+    if (M > 0.0f && aT <= aR) {
+        const float share = aT < aR ? 1.0f : 0.5f;
+        dD -= share * copysignf(D * rden * q * Mq * fast_rcp(aT), Tp);
+    }
+    if constexpr (PLANE_WEIGHT) {
+        return c * dD * s * m_lb;
+    } else {
+        const float Db = fast_exp2((a.beta - 1.0f) * (lnum - fast_log2(den)));      // D^(beta - 1)
+        return c * Db * dD * s * m_lb;
+    }
+}
+
 // ---- coarse-to-fine sweep, one level L >= 1 (adj_sweep_kernel, grad_kernels.hpp) -------------------------------------------
 struct GradSweepArgs {
     const float* GL;        // [n][h][w] layer gradient of level L (nullptr: L is the base band, no layer of its own)

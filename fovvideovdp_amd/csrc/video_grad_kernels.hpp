@@ -101,30 +101,11 @@ struct VideoLayerArgs {
     float p, q[2], k_mask, beta, gain, cmax_hi, dmax_hi;
 };
 
-// adj_layer_kernel's formula for one temporal channel, the powers in the forward's log2 / exp2 form (band_kernel.hpp):
-// three transcendental pairs per value instead of three powf.  s = S gain; s * m_lb = S gain m / L_bkg is d(T')/d(layer).
+// adj_layer_kernel's formula for one temporal channel with the band's pooling coefficient c as the weight: layer_term
+// (grad_common.hpp), which the difference map's backward shares with a plane as the weight.
 __device__ __forceinline__ float video_layer_one(float c, float T, float R, float Dm, float s, float m_lb, float q, float m,
                                                  const VideoLayerArgs& a) {
-    // zero: no pooling weight, D == 0 (an identical pixel), the d_max clamp or the contrast clamp binds
-    if (!(c != 0.0f && Dm > 0.0f && Dm < a.dmax_hi && T < m * a.cmax_hi)) return 0.0f;
-    const float Tp = T * s, Rp = R * s;
-    const float u = Tp - Rp, au = fabsf(u);
-    const float aT = fabsf(Tp), aR = fabsf(Rp);
-    const float M = a.k_mask * fminf(aT, aR);
-    const float Mq = M > 0.0f ? fast_exp2(q * fast_log2(M)) : 0.0f;
-    const float den = 1.0f + Mq;
-    const float lnum = a.p * fast_log2(au);                 // au == 0 (with D > 0 it cannot be): -inf, num = 0
-    const float num = fast_exp2(lnum);
-    const float rden = fast_rcp(den);
-    const float D = num * rden;
-    // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
-    float dD = au > 0.0f ? copysignf(a.p * num * fast_rcp(au), u) * rden : 0.0f;
-    if (M > 0.0f && aT <= aR) {
-        const float share = aT < aR ? 1.0f : 0.5f;
-        dD -= share * copysignf(D * rden * q * Mq * fast_rcp(aT), Tp);
-    }
-    const float Db = fast_exp2((a.beta - 1.0f) * (lnum - fast_log2(den)));      // D^(beta - 1)
-    return c * Db * dD * s * m_lb;
+    return layer_term<false>(c, T, R, Dm, s, m_lb, q, m, a);
 }
 
 __global__ __launch_bounds__(256) void video_layer_kernel(const VideoLayerArgs a) {

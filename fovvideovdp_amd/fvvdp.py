@@ -388,6 +388,40 @@ class fvvdp:
         from .video_grad import jod_video
         return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point, wrt)
 
+    def diff_map_images(self, test, reference, dim_order="BCHW", fixation_point=None, units="jod"):
+        """Extension: the difference maps of B still-image pairs as a differentiable [B, H, W] fp32 tensor on the metric's
+        device, for per-pixel losses such as `(mask * metric.diff_map_images(x, ref)).sum()`, a worst-pixel or top-k loss, or a
+        saliency-weighted one.  units="jod": the reference's raw difference map before its float16 rounding,
+        v_0^beta_jod |jod_a| with v_0 the map the bands add up in; rounded with .to(torch.float16) it equals stats['heatmap'] of
+        predict_images on a metric built with heatmap="raw", bit for bit, whatever the batch.  units="linear": v_0 itself, with
+        no power and no |jod_a|.  beta_jod = 10^log_jod_exp is about 0.59 < 1, so the derivative of the JOD-unit map grows
+        without bound as the map goes to 0: a loss on nearly invisible regions wants the well-conditioned linear form.
+        Anything else: ValueError.
+        When `test` requires grad (and grad mode is on) the result has a grad_fn, and backward() with a cotangent G of the
+        result's shape -- whatever torch expression stands on the map -- puts sum_px G dmap/dtest into `test`, whatever its
+        layout or device.  The reference is a constant (one that requires grad is refused: detach it).  Sources, display models,
+        half precision and mixed pairs as jod_images takes them, the gradient in the dtype of `test`; `fixation_point` as
+        predict_images.  A gradient entry is 0 where jod_images' is (a band pixel with D == 0, the d_max clamp, the contrast
+        clamp, samples the display model clamps) and, for units="jod", where v_0 == 0 (an identical pair; the plain chain rule
+        gives inf * 0 there): the result is finite for finite inputs and a finite cotangent.  Works whatever `heatmap` the
+        metric was built with, makes no coloured maps and does not synchronise with the host.  Double backward is not
+        supported.  The backward re-runs the forward with per-band maps in batches of up to `self.grad_batch` pairs; a pair's
+        gradient does not depend on the batching, bit for bit."""
+        from .map_grad import diff_map_images
+        return diff_map_images(self, test, reference, dim_order, fixation_point, units)
+
+    def diff_map_video(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, units="jod"):
+        """Extension: the difference maps of one clip as a differentiable [N, H, W] fp32 tensor on the metric's device; as
+        diff_map_images, with predict in the place of predict_images (rounded to float16 the units="jod" map equals
+        stats['heatmap'][0, 0] of predict on a heatmap="raw" metric, bit for bit, whatever `batch_frames`) and what jod_video
+        accepts: one clip (B = 1) of at least 2 frames, C = 1 or 3, float32 / float16 / bfloat16, closed-form display models,
+        foveated or not, every temporal padding, temporal filters of up to 64 taps.  units="linear" is the map before the power
+        and |jod_a|; its gradient stays bounded where the JOD-unit map's does not (see diff_map_images).  backward() takes a
+        cotangent [N, H, W] and puts sum_px G dmap/dtest into `test`.  The backward batches like jod_video's
+        (`self.grad_batch`, the same check against the free device memory) and does not depend on the batching, bit for bit."""
+        from .map_grad import diff_map_video
+        return diff_map_video(self, test, reference, dim_order, frames_per_second, fixation_point, units)
+
     def predict_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
         """Extension: one (test, reference) clip or image scored under G gaze traces in one pass (foveated metric, stock
         display geometry).  `fixation_points`: [G, 2] (one fixed gaze per row) or [G, N_frames, 2] (one trace per gaze), in

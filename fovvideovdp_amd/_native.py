@@ -36,6 +36,12 @@ class YuvFormat(C.Structure):
     _fields_ = [("bit_depth", C.c_int32), ("chroma_420", C.c_int32), ("ycbcr2rgb", C.c_float * 9)]
 
 
+class YuvPlanes(C.Structure):
+    """fvvdp_yuv_planes (include/fvvdp_hip_yuv_grad.h): one stream of float32 planes, strides in elements."""
+    _fields_ = [("d_y", C.c_void_p), ("d_u", C.c_void_p), ("d_v", C.c_void_p), ("luma_stride", C.c_size_t),
+                ("chroma_stride", C.c_size_t)]
+
+
 class Geom(C.Structure):
     _fields_ = [("display_size_m", C.c_float * 2), ("distance_m", C.c_float), ("ppd_centre", C.c_float)]
 
@@ -228,22 +234,37 @@ DIFFMAP_SYMBOLS = {
 }
 DIFFMAP_JOD, DIFFMAP_LINEAR = 0, 1       # FVVDP_DIFFMAP_JOD, FVVDP_DIFFMAP_LINEAR
 
+# include/fvvdp_hip_yuv_grad.h: planar YUV clips of float32 code values -- their ingest, the temporal transpose down to the
+# luminance frames and the adjoint of the unpack (bound by lib() as well)
+YUV_GRAD_SYMBOLS = {
+    "fvvdp_temporal_channels_yuv_planes": (C.c_int, [C.c_void_p, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes), C.POINTER(YuvFormat),
+                                                     C.POINTER(Eotf), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                                     C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fvvdp_video_grad_luminance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_float), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fvvdp_yuv_grad_planes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(YuvPlanes), C.POINTER(YuvPlanes),
+                                        C.POINTER(YuvFormat), C.POINTER(Eotf), C.POINTER(C.c_float), C.c_void_p]),
+}
+YUV_GRAD_MAX_TAPS = 32                   # FVVDP_YUV_GRAD_MAX_TAPS
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Sixteen translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Seventeen translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
     (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip), the sums for the gradient with
-    respect to the display's photometry (display_grad_launch.hip) and the gradients of the difference map (map_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    respect to the display's photometry (display_grad_launch.hip), the gradients of the difference map (map_grad_launch.hip) and the
+    float YUV planes with their gradients (yuv_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
-                                                                                                                              "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h")]
+                                                                                                                              "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
+                                                                                                                              "fvvdp_hip_yuv_grad.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -276,6 +297,11 @@ def build(force=False, verbose=False):
     units += [(os.path.join(csrc, "display_grad_launch.hip"), [], os.path.join(objdir, "display_grad_launch.o"))]
     # the gradients of the difference map (include/fvvdp_hip_diffmap.h)
     units += [(os.path.join(csrc, "map_grad_launch.hip"), [], os.path.join(objdir, "map_grad_launch.o"))]
+    # planar YUV clips of float32 code values: ingest and gradients (include/fvvdp_hip_yuv_grad.h).  -ffp-contract=off: the ingest
+    # evaluates the unpack of the test and of the reference stream as two copies of scalar code, and left to itself the compiler
+    # fuses a multiply-add in one copy and not in the other -- an identical pair then has a level 0 that differs in the last bit
+    # and a gradient of 1e-8 where the reference has an exact zero.  Every fused multiply-add of this unit is written as one
+    units += [(os.path.join(csrc, "yuv_grad_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "yuv_grad_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -303,7 +329,8 @@ def lib():
         for name, (res, args) in list(SYMBOLS.items()) + list(IMAGE_SYMBOLS.items()) + list(GRAD_SYMBOLS.items()) + \
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
-                list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()):
+                list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
+                list(YUV_GRAD_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

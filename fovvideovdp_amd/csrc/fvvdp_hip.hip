@@ -1019,6 +1019,22 @@ extern "C" int fvvdp_temporal_channels_yuv(fvvdp_ctx* c, const void* d_test, con
     return FVVDP_OK;
 }
 
+// The context's side of fvvdp_temporal_channels_yuv_planes (yuv_grad_launch.hip, include/fvvdp_hip_yuv_grad.h): the checks the
+// function above makes on the context, the same bookkeeping of level 0's value range, the frame size and where slot0 lies.  Host
+// code only: the kernels and their launches live in that translation unit.
+int fvvdp_ctx_yuv_planes_begin(fvvdp_ctx* c, int chroma_420, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps,
+                               int fl, int n_out, int slot0, int* width, int* height, L0Addr* out) {
+    if (c->P != 4) return fail(FVVDP_EINVAL, "YUV ingest is for video contexts (planes == 4)");
+    if (chroma_420 && ((c->W | c->H) & 1)) return fail(FVVDP_EINVAL, "4:2:0 needs even frame dimensions");
+    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");
+    luminance_slots(c, slot0, n_out);
+    luminance_range(c, eotf, 3, h_rgb2y, h_taps, fl);
+    *width = c->W;
+    *height = c->H;
+    *out = level_addr(c, 0, slot0);
+    return FVVDP_OK;
+}
+
 extern "C" int fvvdp_load_channels_planar(fvvdp_ctx* c, const float* d_R, int n, int slot0, void* stream) {
     if (!c || !d_R) return fail(FVVDP_EINVAL, "null argument");
     if (n < 1 || slot0 < 0 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");

@@ -388,6 +388,31 @@ class fvvdp:
         from .video_grad import jod_video
         return jod_video(self, test, reference, dim_order, frames_per_second, fixation_point, wrt)
 
+    def jod_video_yuv(self, test, reference, frames_per_second=0, width=None, height=None, bit_depth=8, chroma_ss="420",
+                      color_space="bt709", fixation_point=None, full_screen_resize=None):
+        """Extension: jod_video for a clip of planar YUV, as a learned codec, in-loop filter or post-filter produces it, for
+        losses such as `10 - metric.jod_video_yuv((Y, U, V), ref, frames_per_second=30)`.  `test` and `reference`: a tuple
+        (Y, U, V) of float32 tensors -- Y [N, H, W]; U, V [N, H/2, W/2] for chroma_ss="420", [N, H, W] for "444" -- or one packed
+        float32 tensor [N, H*W + 2*uvh*uvw] with the layout of fvvdp_video_source_yuv_frames together with width= and height=
+        (read as three views of itself: no copy).  The samples are limited-range CODE VALUES on the scale of `bit_depth` (Y
+        nominally in [16, 235] * 2^(bit_depth - 8)), fractions allowed: the arithmetic is the integer source's with the sample in
+        the place of (float)code, so a normalised range is the caller's one multiply.  The reference may also be the integer
+        codes that source class takes (converted once, exactly); it is a constant, and one that requires grad is refused.
+        Returns the JOD as a 0-d fp32 tensor on the metric's device; when a test plane requires grad, backward() puts dJOD/dY,
+        dJOD/dU, dJOD/dV into the caller's tensors (or the packed one), on host or device.  The unpack -- the two clamps,
+        bilinear x2 chroma for 4:2:0, the `color_space` matrix ("bt709" or "bt2020nc", with the luminance weights of sRGB or
+        BT.2020), the clip to [0, 1] -- runs inside the ingest kernel and its adjoint in one gather kernel: no RGB clip exists
+        at any point.  A sample gets an exact zero gradient where a clamp binds (Y or chroma outside its range, an RGB value
+        clipped), and so does a frame no temporal window shows.  Accepted: the metric's display model when it has a closed form
+        (sRGB, gamma, PQ, linear, absolute), every temporal padding, foveated or not (`fixation_point` as predict takes it),
+        N >= 2, temporal filters of up to 32 taps (120 frames per second have 30).  Refused, each with a sentence: longer
+        filters, half-precision or float64 planes, 4:2:0 with odd width or height, full_screen_resize, a look-up-table or user
+        photometry, shapes that do not match, 4:2:2.  Double backward is not supported.  The value does not depend on whether
+        grad is on, the gradient not on `self.grad_batch`, and both repeat bit for bit."""
+        from .yuv_grad import jod_video_yuv
+        return jod_video_yuv(self, test, reference, frames_per_second, width, height, bit_depth, chroma_ss, color_space,
+                             fixation_point, full_screen_resize)
+
     def diff_map_images(self, test, reference, dim_order="BCHW", fixation_point=None, units="jod"):
         """Extension: the difference maps of B still-image pairs as a differentiable [B, H, W] fp32 tensor on the metric's
         device, for per-pixel losses such as `(mask * metric.diff_map_images(x, ref)).sum()`, a worst-pixel or top-k loss, or a

@@ -236,6 +236,39 @@ class PlanClipSetup(ClipSetup):
         self.feeder(self.ctx, idx, self.taps, self.fl, nb, oob, self.stream)
 
 
+def yuv_planes(planes):
+    """fvvdp_yuv_planes of the device tensors (Y [N, H, W], U, V [N, uvh, uvw]; rows contiguous, U and V with one frame stride)."""
+    y, u, v = planes
+    return nat.YuvPlanes(y.data_ptr(), u.data_ptr(), v.data_ptr(), y.stride(0), u.stride(0))
+
+
+class YuvClipSetup(ClipSetup):
+    """ClipSetup for a clip of float32 YUV planes (yuv_grad.jod_video_yuv): t and r are (Y, U, V) tuples as yuv_planes takes them,
+    fmt the fvvdp_yuv_format, w the luminance weights of the YUV colour space; the ingest is fvvdp_temporal_channels_yuv_planes.
+    Taps, window list, schedule, launch and write_maps are ClipSetup's."""
+
+    def __init__(self, metric, t, fps, r, fmt, w, prm=None, pp=None):
+        self.t, self.r, self.fmt = t, r, fmt
+        self.C = 3
+        self.N, self.H, self.W = t[0].shape
+        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
+        self.dtype, self.e = metric._image_eotf(torch.float32)
+        self.w = w
+        self.fl, self.taps = metric._temporal_taps(fps)
+        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
+        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
+        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
+        self._finish(metric, 4, prm, pp)
+
+    def ingest(self, lib, t, r, b0, nb, oob):
+        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
+        tp, rp = yuv_planes(t), yuv_planes(r)
+        nat.check(lib.fvvdp_temporal_channels_yuv_planes(self.ctx.handle, C.byref(tp), C.byref(rp), C.byref(self.fmt),
+                                                         C.byref(self.e), nat.fptr(self.w),
+                                                         idx.ctypes.data_as(C.POINTER(C.c_int32)), nat.fptr(self.taps), self.fl, nb,
+                                                         0, _ptr(oob), self.stream))
+
+
 def forward_clip(s, fix):
     """JOD (0-d) and Q_per_ch [n_bands, 2, N] on the device: the launches of predict(..., sync=False), no flag read back."""
     nq = s.n_bands * 2 * s.N

@@ -146,6 +146,16 @@ GAZE_SYMBOLS = {
 }
 GAZE_GROUP_MAX = 8                       # FVVDP_GAZE_GROUP_MAX
 
+# include/fvvdp_hip_tests.h: many test clips against one reference (bound by lib() as well)
+MULTITEST_SYMBOLS = {
+    "fvvdp_tests_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fvvdp_bands_forward_tests": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
+    "fvvdp_bands_forward_tests_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                 C.c_size_t, C.POINTER(PoolParams), C.c_void_p, C.c_void_p]),
+}
+TESTS_GROUP_MAX = 3                      # FVVDP_TESTS_GROUP_MAX
+
 # include/fvvdp_hip_gaze_grad.h: gradients of the video JOD under many gaze traces (bound by lib() as well)
 GAZE_GRAD_SYMBOLS = {
     "fvvdp_gaze_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -252,7 +262,7 @@ _lib = None
 
 def build(force=False, verbose=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Seventeen translation units -- the band /
-    pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h among them), the temporal kernels once
+    pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
@@ -264,7 +274,7 @@ def build(force=False, verbose=False):
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
-                                                                                                                              "fvvdp_hip_yuv_grad.h")]
+                                                                                                                              "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -330,7 +340,7 @@ def lib():
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
-                list(YUV_GRAD_SYMBOLS.items()):
+                list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

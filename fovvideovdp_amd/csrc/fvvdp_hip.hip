@@ -23,6 +23,7 @@
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_images.h"
 #include "fvvdp_hip_gaze.h"
+#include "fvvdp_hip_tests.h"
 #include "fvvdp_hip_ref_grad.h"
 #include "fvvdp_hip_params.h"
 #include "fvvdp_hip_diffmap.h"
@@ -58,6 +59,7 @@ int fvvdp_fail_from(int code, const char* msg) { return fail(code, "%s", msg); }
 #include "band2_kernel.hpp"
 #include "aux_kernels.hpp"
 #include "multigaze_kernel.hpp"
+#include "multitest_kernel.hpp"
 #include "still_kernels.hpp"
 #include "psnr_kernel.hpp"
 #include "resize_kernels.hpp"
@@ -83,6 +85,7 @@ struct CtxEnv {
     bool debug_variant = false;   // FVVDP_DEBUG_VARIANT=1: print which kernel variants are launched (tests)
     int gaze_group = 0;           // FVVDP_GAZE_GROUP=1 / 2 / 4 / 8: largest gaze group of one multigaze_kernel launch (tests, A/B runs)
     int band_cr = 0;              // FVVDP_BAND_CR=n >= 2: chunk height (coarse rows) of every one-level launch instead of chunking()'s (tests, A/B runs)
+    int tests_group = 0;          // FVVDP_TESTS_GROUP=1 / 2 / 3: most quads of one multitest_kernel launch (tests, A/B runs)
     bool yuv_general = false;     // FVVDP_YUV_GENERAL_MATRIX=1: YUV ingest with the nine-term colour matrix also where it has the ITU shape (tests)
 };
 static CtxEnv read_env() {
@@ -106,6 +109,7 @@ static CtxEnv read_env() {
     e.yuv_general = getenv("FVVDP_YUV_GENERAL_MATRIX") != nullptr;
     e.gaze_group = num("FVVDP_GAZE_GROUP", 0);
     e.band_cr = num("FVVDP_BAND_CR", 0);
+    e.tests_group = num("FVVDP_TESTS_GROUP", 0);
     return e;
 }
 
@@ -369,6 +373,35 @@ static void chunking(int hc, int n_strips, int n, long long capacity, int& n_chu
 }
 
 static void choose_level0(fvvdp_ctx* c);
+
+// Does the plain pass walk levels b and b + 1 in one two-level launch (band2_kernel)?  Where it pays -- large levels, see
+// bands_forward_core -- and where the two-level border logic holds; FVVDP_BAND_FUSE=1 forces it wherever valid, =0 (the
+// caller's check) never.
+static bool band2_takes(const fvvdp_ctx* c, int b) {
+    const bool big = (long long)c->lw[b] * c->lh[b] >= 500000;      // (4K: levels 0+1 and 2+3; 2+3 in one launch: 3.06 -> 2.67 us per frame)
+    return (big || c->env.fuse_mode == 1) && b + 1 < c->n_bands && c->lw[b + 1] >= 4 && c->lh[b + 1] >= 4 &&
+           c->lw[b + 2] >= 2 && c->lh[b + 2] >= 2;
+}
+
+// Work decomposition of the two-level launch over levels b, b + 1 for plan_n frames: strips of level-B columns, chunks of level-C
+// rows -- the first n_big of kr rows, the others of kr2.
+static void band2_plan(const fvvdp_ctx* c, int b, int plan_n, int& n_strips, int& n_chunks, int& kr, int& n_big, int& kr2_out) {
+    const int hc = c->lh[b + 2];
+    n_strips = band2_strips(c->lw[b + 1]);
+    chunking2(hc, n_strips, plan_n, c->wave_capacity2, c->env.band2_kr, n_chunks, kr);
+    n_big = n_chunks;
+    kr2_out = kr;
+    // a launch of several rounds of tall chunks: the last chunk of every frame is cut into four and dispatched after
+    // all tall ones (band2_kernel's two phases)
+    const long long waves = (long long)plan_n * n_strips * n_chunks;
+    int kr2 = (waves >= 2 * c->wave_capacity2 && n_chunks >= 3 && kr >= 16) ? (kr + 3) / 4 : 0;
+    if (c->env.band2_kr2 >= 0) kr2 = c->env.band2_kr2;                  // tuning override (FVVDP_BAND2_KR2); 0 = uniform chunks
+    if (kr2 >= 1 && kr2 < kr && n_chunks >= 2) {
+        n_big = n_chunks - 1;
+        kr2_out = kr2;
+        n_chunks = n_big + (hc - n_big * kr + kr2 - 1) / kr2;
+    }
+}
 
 extern "C" int fvvdp_ctx_create(fvvdp_ctx** out, int width, int height, int n_bands, int planes, int max_frames,
                                 const double* h_rho_band, const fvvdp_params* prm) {
@@ -1443,9 +1476,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
     const int fuse_mode = c->env.fuse_mode;                      // 0 / 1, anything else: automatic
     const bool fuse_ok = !fov && !any_maps && fuse_mode != 0;
     for (int b = 0; b < c->n_bands; ++b) {
-        const bool big = (long long)c->lw[b] * c->lh[b] >= 500000;      // (4K: levels 0+1 and 2+3; 2+3 in one launch: 3.06 -> 2.67 us per frame)
-        if (fuse_ok && (big || fuse_mode == 1) && b + 1 < c->n_bands && c->lw[b + 1] >= 4 && c->lh[b + 1] >= 4 &&
-            c->lw[b + 2] >= 2 && c->lh[b + 2] >= 2) {
+        if (fuse_ok && band2_takes(c, b)) {
             Band2Args a;
             memset(&a, 0, sizeof(a));
             a.A = level_addr(c, b, b == 0 ? slot0 : 0);
@@ -1456,23 +1487,8 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             a.hb = c->lh[b + 1];
             a.wc = c->lw[b + 2];
             a.hc = c->lh[b + 2];
-            a.n_strips = band2_strips(a.wb);
-            chunking2(a.hc, a.n_strips, plan_n, c->wave_capacity2, c->env.band2_kr, a.n_chunks, a.kr);
-            a.n_big = a.n_chunks;
-            a.kr2 = a.kr;
+            band2_plan(c, b, plan_n, a.n_strips, a.n_chunks, a.kr, a.n_big, a.kr2);
             a.n_frames = n;
-            {
-                // a launch of several rounds of tall chunks: the last chunk of every frame is cut into four and dispatched after
-                // all tall ones (band2_kernel's two phases)
-                const long long waves = (long long)plan_n * a.n_strips * a.n_chunks;
-                int kr2 = (waves >= 2 * c->wave_capacity2 && a.n_chunks >= 3 && a.kr >= 16) ? (a.kr + 3) / 4 : 0;
-                if (c->env.band2_kr2 >= 0) kr2 = c->env.band2_kr2;                  // tuning override (FVVDP_BAND2_KR2); 0 = uniform chunks
-                if (kr2 >= 1 && kr2 < a.kr && a.n_chunks >= 2) {
-                    a.n_big = a.n_chunks - 1;
-                    a.kr2 = kr2;
-                    a.n_chunks = a.n_big + (a.hc - a.n_big * a.kr + kr2 - 1) / kr2;
-                }
-            }
             a.mulA = (b == 0) ? 1.0f : 2.0f;
             a.mulB = 2.0f;
             a.csfA = c->csf + (size_t)b * FVVDP_LUT_N;
@@ -1750,6 +1766,184 @@ extern "C" int fvvdp_bands_forward_gazes_pool(fvvdp_ctx* c, int n, int n_gazes, 
     if (!pool) return fail(FVVDP_EINVAL, "null argument");
     return bands_forward_gazes_core(c, n, n_gazes, d_gaze, gaze_stride, d_Q, q_stride, q_col0, geom, d_work, work_bytes, pool, d_jod,
                                     stream);
+}
+
+// ---- many tests per reference (include/fvvdp_hip_tests.h) ------------------------------------------------------------------
+// Floats of one test's row of the workspace (documented in the header) and, in off[], where every band starts in it: per band the
+// larger of the one-level and the two-level bound of work items per frame, as fvvdp_ctx_create sizes the context's own partials.
+static size_t tests_row_floats(int width, int height, int n_bands, int n, size_t* off) {
+    int lw[FVVDP_MAX_BANDS + 2], lh[FVVDP_MAX_BANDS + 2];
+    lw[0] = width;
+    lh[0] = height;
+    for (int i = 1; i <= n_bands + 1; ++i) {
+        lw[i] = (lw[i - 1] + 1) / 2;
+        lh[i] = (lh[i - 1] + 1) / 2;
+    }
+    size_t blk[FVVDP_MAX_BANDS];
+    for (int b = 0; b < n_bands; ++b) blk[b] = (size_t)band_strips(lw[b + 1]) * ((lh[b + 1] + 1) / 2);
+    for (int b = 0; b + 1 < n_bands; ++b) {
+        const size_t blk2 = (size_t)band2_strips(lw[b + 1]) * lh[b + 2];
+        if (blk2 > blk[b]) blk[b] = blk2;
+        if (blk2 > blk[b + 1]) blk[b + 1] = blk2;
+    }
+    size_t fl = 0;
+    for (int b = 0; b < n_bands; ++b) {
+        if (off) off[b] = fl;
+        fl += (size_t)n * blk[b] * 2;
+    }
+    return (fl + 63) / 64 * 64;
+}
+
+extern "C" int fvvdp_tests_workspace(int width, int height, int n_bands, int n_tests, int n, size_t* bytes) {
+    if (!bytes) return fail(FVVDP_EINVAL, "null argument");
+    if (width < 1 || height < 1 || n_tests < 1 || n < 1 || n_bands < 1 || n_bands > FVVDP_MAX_BANDS)
+        return fail(FVVDP_EINVAL, "bad shape: %dx%d, %d bands, %d tests, %d frames", width, height, n_bands, n_tests, n);
+    *bytes = (size_t)n_tests * tests_row_floats(width, height, n_bands, n, nullptr) * sizeof(float);
+    return FVVDP_OK;
+}
+
+template <bool SPLIT>
+static void launch_multitest(const MultiTestArgs& m, int nq, bool rx, hipStream_t st) {
+    const dim3 grid(m.b.n_items), block(64);
+    if (nq == 3 && rx) hipLaunchKernelGGL((multitest_kernel<3, true, SPLIT>), grid, block, 0, st, m);
+    else if (nq == 3) hipLaunchKernelGGL((multitest_kernel<3, false, SPLIT>), grid, block, 0, st, m);
+    else if (nq == 2 && rx) hipLaunchKernelGGL((multitest_kernel<2, true, SPLIT>), grid, block, 0, st, m);
+    else if (nq == 2) hipLaunchKernelGGL((multitest_kernel<2, false, SPLIT>), grid, block, 0, st, m);
+    else hipLaunchKernelGGL((multitest_kernel<1, true, SPLIT>), grid, block, 0, st, m);
+}
+
+static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, void* d_work,
+                                    size_t work_bytes, const fvvdp_pool_params* pool, float* d_jod, void* stream) {
+    if (!c || !d_Q || !d_work) return fail(FVVDP_EINVAL, "null argument");
+    if (pool) {
+        if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
+        int rc = check_pool_params(pool);
+        if (rc != FVVDP_OK) return rc;
+    }
+    if (n_tests < 1) return fail(FVVDP_EINVAL, "n_tests must be >= 1, got %d", n_tests);
+    if (n < 1) return fail(FVVDP_EINVAL, "n must be >= 1, got %d", n);
+    const int n_quads = n_tests / 2 + 1;                     // ceil((n_tests + 1) / 2): streams 0 .. n_tests, two per quad
+    if ((long long)n_quads * n > c->max_frames)
+        return fail(FVVDP_EINVAL, "%d tests x %d frames need %d x %d frame slots, the context has max_frames=%d", n_tests, n, n_quads, n,
+                    c->max_frames);
+    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    if (c->P != 4) return fail(FVVDP_EINVAL, "a still-image context (2 planes): the tests pass covers video contexts (4 planes)");
+    if (c->lut3_set[0] || c->lut3_set[1])
+        return fail(FVVDP_EINVAL, "the context is foveated (fvvdp_ctx_set_csf_3d called): the tests pass covers the non-foveated metric");
+    if (!c->csf_set) return fail(FVVDP_ESTATE, "fvvdp_ctx_set_csf_1d not called");
+    if (((uintptr_t)d_work & 255) != 0) return fail(FVVDP_EINVAL, "the workspace must be 256-byte aligned");
+    size_t off[FVVDP_MAX_BANDS];
+    const size_t row = tests_row_floats(c->W, c->H, c->n_bands, n, off);
+    if (work_bytes < (size_t)n_tests * row * sizeof(float))
+        return fail(FVVDP_EINVAL, "workspace of %zu bytes is too small: %d tests x %d frames need %zu", work_bytes, n_tests, n,
+                    (size_t)n_tests * row * sizeof(float));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float* work = reinterpret_cast<float*>(d_work);
+    int group_max = FVVDP_TESTS_GROUP_MAX;
+    if (c->env.tests_group >= 1 && c->env.tests_group < group_max) group_max = c->env.tests_group;
+    if (group_max < 2 && n_quads > 1) group_max = 2;         // a group is the reference's quad and at least one other
+    const int ref_quad = n_quads - 1;
+    const bool ref_shared = (n_tests & 1) != 0;              // the last test sits in (x, z) of the reference's quad
+    GazeFinalizeArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    MultiTestArgs m[FVVDP_MAX_BANDS];
+    // Levels that the plain pass walks with the two-level kernel take its work decomposition (multitest_kernel.hpp), so that the
+    // partial sums -- and with them Q -- are that pass's bit for bit: mode 1 for its level A, mode 2 (SPLIT) for its level B.
+    int mode[FVVDP_MAX_BANDS] = {};
+    for (int b = 0; b < c->n_bands; ++b) {                   // every refusal before the first launch
+        memset(&m[b], 0, sizeof(m[b]));
+        fill_band_args(c, b, 0, n, false, nullptr, m[b].b);
+        MultiTestArgs& g = m[b];
+        g.pitch = STRIP_J; g.joff = 0; g.own_lo = 2; g.own_hi = 62; g.own_lo0 = 0;
+        g.kr = g.b.cr; g.n_big = g.b.n_chunks; g.kr2 = g.b.cr; g.row_mul = 1; g.k_lim = g.b.hc;
+        if (mode[b] == 0 && c->env.fuse_mode != 0 && band2_takes(c, b)) {
+            mode[b] = 1;
+            mode[b + 1] = 2;
+        }
+        if (mode[b] != 0) {
+            const int bA = mode[b] == 1 ? b : b - 1;
+            int n_strips, n_chunks, kr, n_big, kr2;
+            band2_plan(c, bA, n, n_strips, n_chunks, kr, n_big, kr2);
+            g.b.n_strips = n_strips;
+            g.b.n_chunks = n_chunks;
+            g.b.cr = 0;                                      // not used: the chunks are [ka, kb) of level-C rows
+            g.kr = kr; g.n_big = n_big; g.kr2 = kr2; g.k_lim = c->lh[bA + 2];
+            if (mode[b] == 1) { g.pitch = F2_PITCH; g.joff = F2_HL; g.own_lo = g.own_lo0 = F2_HL; g.own_hi = F2_HL + F2_PITCH; g.row_mul = 2; }
+            else { g.pitch = F2_PITCH / 2; g.joff = F2_HL / 2; g.own_lo = g.own_lo0 = F2_HL / 2; g.own_hi = (F2_HL + F2_PITCH) / 2; g.row_mul = 1; }
+        }
+        const int nblk = m[b].b.n_strips * m[b].b.n_chunks;
+        if ((size_t)n * nblk * 2 > (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+        m[b].b.n_items = nblk * n;
+        m[b].partial = work + off[b];
+        fa.f.nblk[b] = nblk;
+        fa.f.off[b] = (long long)off[b];
+        fa.f.npx[b] = (float)m[b].b.w * (float)m[b].b.h;
+    }
+    for (int b = 0; b < c->n_bands; ++b) {
+        Timed tm(c, 1 + b, st);
+        // groups: the reference's quad (slot 0 of the group) and the next group_max - 1 of the quads 0 .. ref_quad - 1; the first
+        // group writes the reference's next level and evaluates the test that shares its quad
+        int q0 = 0;
+        bool first = true;
+        do {
+            const int others = std::min(group_max - 1, ref_quad - q0);
+            const int nq = 1 + others;
+            const bool rx = first && ref_shared;
+            m[b].qslot[0] = ref_quad * n;
+            m[b].store[0] = first ? 1 : 0;
+            m[b].row[0] = (long long)(n_tests - 1) * (long long)row;        // read by the RX instantiations only
+            m[b].row[1] = 0;
+            for (int j = 1; j <= others; ++j) {
+                const int q = q0 + j - 1;
+                m[b].qslot[j] = q * n;
+                m[b].store[j] = 1;
+                m[b].row[2 * j] = (long long)(2 * q) * (long long)row;
+                m[b].row[2 * j + 1] = (long long)(2 * q + 1) * (long long)row;
+            }
+            if (c->env.debug_variant)
+                fprintf(stderr, "fvvdp: level %d: multitest_kernel<%d, %s>, n %d, quads %d.., n_strips %d, n_chunks %d, cr %d, store_ref %d, walk %d\n",
+                        b, nq, rx ? "true" : "false", n, q0, m[b].b.n_strips, m[b].b.n_chunks, m[b].b.cr, m[b].store[0], mode[b]);
+            if (mode[b] == 2) launch_multitest<true>(m[b], nq, rx, st);
+            else launch_multitest<false>(m[b], nq, rx, st);
+            q0 += others;
+            first = false;
+        } while (q0 < ref_quad);
+    }
+    const long long q_stride_t = (long long)c->n_bands * 2 * q_stride;
+    fa.f.partial = work;
+    fa.f.Q = d_Q;
+    fa.f.n_bands = c->n_bands;
+    fa.f.n = n;
+    fa.f.q_stride = q_stride;
+    fa.f.q_col0 = q_col0;
+    fa.f.tc = c->P / 2;
+    fa.f.inv_beta = 1.0f / c->prm.beta;
+    fa.partial_stride = (long long)row;
+    fa.q_stride_g = q_stride_t;
+    {
+        Timed tm(c, 1 + c->n_bands, st);
+        hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_tests), dim3(64), 0, st, fa);
+    }
+    if (pool && q_col0 + n == q_stride) {
+        for (int k = 0; k < n_tests; ++k) {          // the pooling kernel of fvvdp_bands_forward_pool, once per test
+            PoolArgs pa;
+            fill_pool_args(pa, d_Q + (size_t)k * q_stride_t, c->n_bands, 2, q_stride, q_stride, pool, d_jod + k);
+            hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_bands_forward_tests(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, void* d_work,
+                                         size_t work_bytes, void* stream) {
+    return bands_forward_tests_core(c, n, n_tests, d_Q, q_stride, q_col0, d_work, work_bytes, nullptr, nullptr, stream);
+}
+
+extern "C" int fvvdp_bands_forward_tests_pool(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, void* d_work,
+                                              size_t work_bytes, const fvvdp_pool_params* pool, float* d_jod, void* stream) {
+    if (!pool) return fail(FVVDP_EINVAL, "null argument");
+    return bands_forward_tests_core(c, n, n_tests, d_Q, q_stride, q_col0, d_work, work_bytes, pool, d_jod, stream);
 }
 
 // ---- placement of level 0, at context creation ------------------------------------------------------------------------------

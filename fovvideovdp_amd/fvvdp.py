@@ -462,6 +462,25 @@ class fvvdp:
         from .gazes import predict_gazes
         return predict_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
 
+    def predict_tests(self, tests, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+        """Extension: T test clips scored against ONE reference in one pass -- a bitrate ladder, one source through several
+        codecs or presets, a rendering-quality sweep.  `tests`: a list or tuple of T >= 1 clips, each with the shape, dtype and
+        `dim_order` of `reference`.  Returns (Q_JOD, stats): Q_JOD a [T] fp32 device tensor, stats['Q_per_ch']
+        [T, bands, 2, frames] (numpy), the other keys as predict makes them.  Row k is bit-identical to
+        predict(tests[k], reference, dim_order, frames_per_second) on this metric, whatever the other tests are, however many
+        there are, whatever `batch_frames` is and at every frame size.  The reference is ingested and its level 0 written once per pair of tests
+        instead of once per test, and the pyramid pass evaluates what depends on the reference only (its own pyramid, L_bkg,
+        the CSF look-up) once per group of up to five tests (include/fvvdp_hip_tests.h).  Every array source predict accepts
+        (uint8 / uint16 / float32 / float16 / bfloat16, C = 1 or 3, every temporal padding, code-value tables and user
+        photometry on integer input, batch_frames shorter than the clip), clips of at least 2 frames.  The out-of-range
+        warning is issued once per call.  Refused, each with a sentence: a foveated metric or a `fixation_point` (loop
+        predict), a metric that makes heat maps, a single frame (predict_images with the reference repeated), tests whose
+        shape or dtype differs from the reference's, inputs that require grad, fvvdp_video_source objects and YUV frame
+        sources.  Scratch: ceil((T + 1) / 2) x predict's; beyond `self.tests_scratch_bytes` (None: 96 GB or 40 % of the device)
+        the tests are taken in several passes, each with the reference -- same results."""
+        from .multitest import predict_tests
+        return predict_tests(self, tests, reference, dim_order, frames_per_second, fixation_point)
+
     def jod_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
         """Extension: the JODs of one clip under G gaze traces as a differentiable [G] fp32 tensor on the metric's device, for
         losses over a gaze distribution such as `(10 - metric.jod_gazes(x, ref, grid, frames_per_second=30)).mean()` or the

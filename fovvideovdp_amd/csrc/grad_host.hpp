@@ -69,6 +69,23 @@ static void grad_layout(int width, int height, int n_bands, int n, int planes, G
     L.total = off;
 }
 
+// The workspace of the reference's backward (ref_grad_launch.hip, tests_grad_launch.hip): the test side's layout (coef | GLR in
+// the place of GL | GG) followed by the GX maps
+struct RefGradLayout {
+    GradLayout L;
+    size_t gx[FVVDP_MAX_BANDS];
+};
+
+static void ref_grad_layout(int width, int height, int n_bands, int n, int planes, RefGradLayout& R) {
+    grad_layout(width, height, n_bands, n, planes, R.L);
+    size_t off = R.L.total;
+    for (int b = 0; b < n_bands; ++b) {
+        R.gx[b] = off;
+        off += align64((size_t)n * planes * R.L.w[b] * R.L.h[b]);
+    }
+    R.L.total = off;
+}
+
 // video_coef_kernel for the n frames [f0, f0 + n) of a clip of n_frames (coefficients [n][2][n_bands] into d_coef) and
 // video_level0_kernel on the batch's 2n planes (level 0 of the workspace `ws` into d_g0_batch).  The kernels are defined in
 // video_grad_launch.hip only, so are these functions
@@ -112,6 +129,15 @@ static int grad_check_maps(const fvvdp_band_maps* maps, int n_bands) {
     for (int b = 0; b < n_bands; ++b)
         if (!maps[b].d_D || !maps[b].d_contrast || !maps[b].d_lbkg || !maps[b].d_S)
             return grad_fail(FVVDP_EINVAL, "band %d: every map (D, contrast, L_bkg, S) is required", b);
+    return FVVDP_OK;
+}
+
+// the slope planes of the reference's backward: a host array of one device pointer per band
+static int check_slopes(const float* const* h_slope_ptrs, int n_bands) {
+    if (!h_slope_ptrs) return grad_fail(FVVDP_EINVAL, "null argument");
+    for (int b = 0; b < n_bands; ++b)
+        if (!h_slope_ptrs[b] || reinterpret_cast<uintptr_t>(h_slope_ptrs[b]) % 4 != 0)
+            return grad_fail(FVVDP_EINVAL, "band %d: the slope plane is required, aligned to 4 bytes", b);
     return FVVDP_OK;
 }
 

@@ -18,29 +18,7 @@
 #include "ref_grad_kernels.hpp"
 #include "grad_host.hpp"
 
-// the test side's layout (coef | GLR in the place of GL | GG) followed by the GX maps
-struct RefGradLayout {
-    GradLayout L;
-    size_t gx[FVVDP_MAX_BANDS];
-};
-
-static void ref_grad_layout(int width, int height, int n_bands, int n, int planes, RefGradLayout& R) {
-    grad_layout(width, height, n_bands, n, planes, R.L);
-    size_t off = R.L.total;
-    for (int b = 0; b < n_bands; ++b) {
-        R.gx[b] = off;
-        off += align64((size_t)n * planes * R.L.w[b] * R.L.h[b]);
-    }
-    R.L.total = off;
-}
-
-static int check_slopes(const float* const* h_slope_ptrs, int n_bands) {
-    if (!h_slope_ptrs) return grad_fail(FVVDP_EINVAL, "null argument");
-    for (int b = 0; b < n_bands; ++b)
-        if (!h_slope_ptrs[b] || reinterpret_cast<uintptr_t>(h_slope_ptrs[b]) % 4 != 0)
-            return grad_fail(FVVDP_EINVAL, "band %d: the slope plane is required, aligned to 4 bytes", b);
-    return FVVDP_OK;
-}
+// (RefGradLayout, ref_grad_layout and check_slopes: grad_host.hpp, shared with tests_grad_launch.hip)
 
 // the reference layer gradients of every band (CH channels per thread) and the sweep on the n CH planes
 template <int CH>

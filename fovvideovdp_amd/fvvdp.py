@@ -499,6 +499,33 @@ class fvvdp:
         from .gaze_grad import jod_gazes
         return jod_gazes(self, test, reference, fixation_points, dim_order, frames_per_second)
 
+    def jod_tests(self, tests, reference, dim_order="BCFHW", frames_per_second=0, wrt="tests"):
+        """Extension: the JODs of T test clips against ONE reference as a differentiable [T] fp32 tensor on the metric's device,
+        for losses over a ladder such as `(10 - metric.jod_tests(recons, src, frames_per_second=30)).mean()` -- a multi-rate
+        codec's T reconstructions of one source, a pre-filter in front of T encoders, a renderer at several quality settings.
+        `tests` as predict_tests takes them: a list or tuple of T >= 1 clips shaped like `reference`.  Row k is bit-identical to
+        predict_tests(tests, reference, ...)[0][k], and so to jod_video(tests[k], reference) and to predict: the forward makes
+        predict_tests' launches.  `wrt`: "tests" (default) -- backward() puts grad[k] dJOD_k/dtests[k] into every test that
+        requires grad, bit-identical to jod_video's gradient, a test that does not require grad costs no backward work, and
+        the reference is a constant (one that requires grad is refused); "reference" -- backward() puts
+        sum_k grad[k] dJOD_k/dreference into `reference`, the tests are constants (one that requires grad is refused); "both"
+        -- both from one backward.  Anything else: ValueError.  The reference's backward shares among the tests whatever is
+        linear after the pointwise layer gradient: the layer gradients of up to four tests are summed by one launch that reads
+        the planes that depend on the reference only once, and the coarse-to-fine sweep, level 0, the temporal transpose and
+        the display model's derivative run once per backward batch or clip instead of once per test
+        (include/fvvdp_hip_tests_grad.h); its memory does not grow with T.  Accepted, on every clip: what jod_video accepts
+        (float32, float16 or bfloat16 samples, C = 1 or 3, one clip of at least 2 frames with B = 1, closed-form display
+        models, every temporal padding, filters of up to 64 taps, any layout, on host or device); when the float dtypes of
+        the clips differ all are upcast with .float() inside autograd's view, and every gradient arrives in its caller
+        tensor's dtype.  Refused, each with a sentence: what predict_tests refuses (a foveated metric, a heat-map metric,
+        source objects, a single frame, a `tests` that is no non-empty list or tuple) and what jod_video refuses (integer or
+        float64 samples, user photometry, too many taps, shapes that differ).  Nothing is synchronised with the host: no
+        out-of-range warning.  Double backward is not supported.  The gradients do not depend on `self.grad_batch`, on the
+        grouping of the tests into launches nor on `self.tests_grad_sets` (the map sets a backward batch keeps resident,
+        default 4), bit for bit."""
+        from .tests_grad import jod_tests
+        return jod_tests(self, tests, reference, dim_order, frames_per_second, wrt)
+
     # ---- the model parameters as variables (extension; include/fvvdp_hip_params.h, param_grad.py) ---------------------
     # the parameters a calibration can fit, in the order of the vectors below: the first six act per band pixel (masking model,
     # sensitivity gain, spatial pooling exponent), the last six in do_pooling_and_jods

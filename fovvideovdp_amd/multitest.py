@@ -96,6 +96,24 @@ def _on_device(metric, streams, dim_order, fps, width, height, N):
     h2d = sum(s.numel() * s.element_size() for s in streams if s.device != dev)
     # every clip crosses to the device once, the reference included, and lies there as the ingest kernels read it
     streams = [reshuffle_dims(s.to(dev), in_dims=dim_order, out_dims="BCFHW").contiguous() for s in streams]
+    res, pl = launch_passes(metric, streams, fps, width, height, N, "predict_tests needs a display model the ingest kernels "
+                            "evaluate (float input behind a user photometry class goes through predict(), one test per call)")
+    n_bands, nq = pl.n_bands, pl.n_bands * 2 * N
+    metric.last_h2d_bytes = h2d
+    res_h = metric._to_host(res)                          # the one host synchronisation of the call
+    stats = {'Q_per_ch': res_h[:T * nq].view(T, n_bands, 2, N).numpy(), 'rho_band': pl.rho_band,
+             'frames_per_second': fps, 'width': width, 'height': height, 'N_frames': N}
+    if int(res_h[T * nq:T * nq + 1].view(torch.int32)[0]) != 0:
+        logging.warning("Pixel outside the valid range 0-1")
+    return res[T * nq + 1:], stats
+
+
+def launch_passes(metric, streams, fps, width, height, N, refusal):
+    """The launches of predict_tests for the T + 1 contiguous [1, C, N, H, W] device clips `streams` (the tests, then the
+    reference): the one launch loop of predict_tests and of tests_grad.jod_tests.  Returns (res, plan): res the device tensor
+    Q_per_ch [T][bands][2][N] | range flag | JOD [T], nothing of it read back; plan the clip plan of the call.  `refusal`: the
+    sentence for a source whose display model the ingest kernels do not evaluate."""
+    dev, T = metric.device, len(streams) - 1
 
     def source(a, b):
         return fvvdp_video_source_array(streams[a], streams[b], fps, dim_order="BCFHW",
@@ -103,9 +121,8 @@ def _on_device(metric, streams, dim_order, fps, width, height, N):
 
     pl = metric._clip_plan(source(0, T))                  # the batches predict() takes: same work decomposition, same sums
     if isinstance(pl.feeder, _PipelinedSourceFeeder):
-        raise RuntimeError("predict_tests needs a display model the ingest kernels evaluate (float input behind a user photometry "
-                           "class goes through predict(), one test per call)")
-    n_bands, nq = pl.n_bands, pl.n_bands * 2 * N
+        raise RuntimeError(refusal)
+    nq = pl.n_bands * 2 * N
     res = torch.zeros(T * nq + 1 + T, dtype=torch.float32, device=dev)          # Q_per_ch of every test | range flag | JOD of every test
     oob = res[T * nq:T * nq + 1].view(torch.int32)
     # Scratch: a pass over t tests holds (t // 2 + 1) x batch frame slots.  The batch stays predict()'s (the chunk heights, and with
@@ -120,13 +137,7 @@ def _on_device(metric, streams, dim_order, fps, width, height, N):
     for k0 in range(0, T, per_pass):
         ks = list(range(k0, min(k0 + per_pass, T)))
         _one_pass(metric, pl, source, ks, T, res[k0 * nq:(k0 + len(ks)) * nq], oob, res[T * nq + 1 + k0:], width, height, N)
-    metric.last_h2d_bytes = h2d
-    res_h = metric._to_host(res)                          # the one host synchronisation of the call
-    stats = {'Q_per_ch': res_h[:T * nq].view(T, n_bands, 2, N).numpy(), 'rho_band': pl.rho_band,
-             'frames_per_second': fps, 'width': width, 'height': height, 'N_frames': N}
-    if int(res_h[T * nq:T * nq + 1].view(torch.int32)[0]) != 0:
-        logging.warning("Pixel outside the valid range 0-1")
-    return res[T * nq + 1:], stats
+    return res, pl
 
 
 def _one_pass(metric, pl, source, ks, ref, Q, oob, jod, width, height, N):

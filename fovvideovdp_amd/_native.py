@@ -42,6 +42,12 @@ class YuvPlanes(C.Structure):
                 ("chroma_stride", C.c_size_t)]
 
 
+class ResizeStream(C.Structure):
+    """fvvdp_resize_stream (include/fvvdp_hip_resize.h): one stream at its own frame size, strides in elements."""
+    _fields_ = [("d_data", C.c_void_p), ("dtype", C.c_int32), ("channels", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("frame_stride", C.c_size_t), ("plane_stride", C.c_size_t)]
+
+
 class Geom(C.Structure):
     _fields_ = [("display_size_m", C.c_float * 2), ("distance_m", C.c_float), ("ppd_centre", C.c_float)]
 
@@ -257,6 +263,23 @@ YUV_GRAD_SYMBOLS = {
 }
 YUV_GRAD_MAX_TAPS = 32                   # FVVDP_YUV_GRAD_MAX_TAPS
 
+# include/fvvdp_hip_resize.h: clips whose streams have frame sizes of their own -- the resize fused into the ingest, and its adjoint
+# (bound by lib() as well)
+RESIZE_SYMBOLS = {
+    "fvvdp_temporal_channels_resized": (C.c_int, [C.c_void_p, C.POINTER(ResizeStream), C.POINTER(ResizeStream), C.c_int,
+                                                  C.POINTER(Eotf), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "fvvdp_resize_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(ResizeStream), C.c_void_p, C.c_int,
+                                    C.POINTER(Eotf), C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+RESIZE_MAX_TAPS = 32                     # FVVDP_RESIZE_MAX_TAPS
+
+
+def resize_grad_table_bytes(width, height):
+    """FVVDP_RESIZE_GRAD_TABLE_BYTES"""
+    return (2 * (width + height) * 4 + 255) // 256 * 256
+
+
 # include/fvvdp_hip_tests_grad.h: gradients of many tests' video JODs with respect to their one reference (bound by lib() as well)
 TESTS_GRAD_SYMBOLS = {
     "fvvdp_tests_ref_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -272,21 +295,22 @@ _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Eighteen translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Nineteen translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
     respect to the reference (ref_grad_launch.hip), the sums for the gradients with respect to the model parameters
     (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip), the sums for the gradient with
     respect to the display's photometry (display_grad_launch.hip), the gradients of the difference map (map_grad_launch.hip), the
-    float YUV planes with their gradients (yuv_grad_launch.hip) and the gradients of many tests with respect to their one reference
-    (tests_grad_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    float YUV planes with their gradients (yuv_grad_launch.hip), the gradients of many tests with respect to their one reference
+    (tests_grad_launch.hip) and the clips resized inside the ingest with the resize's adjoint (resize_launch.hip) -- are compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
-                                                                                                                              "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h")]
+                                                                                                                              "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h",
+                                                                                                                              "fvvdp_hip_resize.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -327,6 +351,10 @@ def build(force=False, verbose=False):
     # gradients of many tests with respect to their one reference (include/fvvdp_hip_tests_grad.h).  Default flags, as
     # ref_grad_launch.hip: ref_layer_one must compile to the arithmetic it has there
     units += [(os.path.join(csrc, "tests_grad_launch.hip"), [], os.path.join(objdir, "tests_grad_launch.o"))]
+    # clips resized inside the ingest, and the resize's adjoint (include/fvvdp_hip_resize.h).  -ffp-contract=off for the reason
+    # given for yuv_grad_launch.hip: the interpolation of the test and of the reference stream are two copies of scalar code, and the
+    # adjoint recomputes the test's values to decide the clip as the forward decided it -- all three must round alike
+    units += [(os.path.join(csrc, "resize_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "resize_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -355,7 +383,8 @@ def lib():
                 list(VIDEO_GRAD_SYMBOLS.items()) + list(GAZE_SYMBOLS.items()) + list(GAZE_GRAD_SYMBOLS.items()) + \
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
-                list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()):
+                list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()) + \
+                list(RESIZE_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -1068,6 +1068,21 @@ int fvvdp_ctx_yuv_planes_begin(fvvdp_ctx* c, int chroma_420, const fvvdp_eotf* e
     return FVVDP_OK;
 }
 
+// The context's side of fvvdp_temporal_channels_resized (resize_launch.hip, include/fvvdp_hip_resize.h), as the function above:
+// the context's frame size is the target of the resize.  The range of level 0 is the display model's with `channels` weights: every
+// interpolated value is clipped to [0, 1] before the model (bicubic overshoot included), and each closed-form model clamps its output.
+int fvvdp_ctx_resized_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
+                            int n_out, int slot0, int* width, int* height, L0Addr* out) {
+    if (c->P != 4) return fail(FVVDP_EINVAL, "the resizing ingest is for video contexts (planes == 4)");
+    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");
+    luminance_slots(c, slot0, n_out);
+    luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
+    *width = c->W;
+    *height = c->H;
+    *out = level_addr(c, 0, slot0);
+    return FVVDP_OK;
+}
+
 extern "C" int fvvdp_load_channels_planar(fvvdp_ctx* c, const float* d_R, int n, int slot0, void* stream) {
     if (!c || !d_R) return fail(FVVDP_EINVAL, "null argument");
     if (n < 1 || slot0 < 0 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");

@@ -413,6 +413,41 @@ class fvvdp:
         return jod_video_yuv(self, test, reference, frames_per_second, width, height, bit_depth, chroma_ss, color_space,
                              fixation_point, full_screen_resize)
 
+    def predict_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCFHW",
+                        frames_per_second=30, fixation_point=None):
+        """Extension: predict for a test and a reference clip that each have a frame size of their OWN -- a bitrate-ladder rung,
+        a render-resolution sweep or a super-resolution output shown full screen.  Both clips have the same frame and channel
+        counts (C = 1 or 3) and are float32, or uint8 scaled by 1/255, on host or device, in any `dim_order` predict takes.
+        `resize_resolution=(width, height)` is the size the metric judges at (default: the display geometry's resolution).  A
+        stream of another size is resized inside the ingest kernel with the arithmetic of torch.nn.functional.interpolate
+        (`full_screen_resize`: "bilinear", "bicubic", "nearest" or "area"; align_corners=False, no antialiasing); a stream that
+        has the target size is read as it is.  Per stream and target pixel: interpolate every channel, clip to [0, 1] (the clip
+        belongs to the resize, as in the reference's reader: no out-of-range warning), display model, luminance.  No clip at the
+        target size is stored.  Returns (Q_JOD, stats) as predict does, stats at the target size.  When both clips already have
+        the target size the call is predict's, unchanged.  Accepted: closed-form display models (sRGB, gamma, PQ, linear,
+        absolute), every temporal padding, foveated or not (`fixation_point` in target pixels), clips of at least 2 frames,
+        temporal filters of up to 32 taps (120 frames per second).  Refused, each with a sentence and before any device work: an
+        unknown mode, half-precision, float64 or 16-bit samples, a look-up-table or user photometry, differing frame or channel
+        counts, longer filters, single images."""
+        from .resize_grad import predict_resized
+        return predict_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
+                               fixation_point)
+
+    def jod_video_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCFHW",
+                          frames_per_second=30, fixation_point=None):
+        """Extension: jod_video for clips with frame sizes of their own (see predict_resized for the resize), for losses such as
+        `10 - metric.jod_video_resized(net(x_small), ref_full, frames_per_second=30)`.  Returns the JOD as a 0-d fp32 tensor on the
+        metric's device; under torch.no_grad() it equals predict_resized's bit for bit.  When `test` (float32) requires grad,
+        backward() puts dJOD/dtest into the caller's tensor AT THE TEST'S OWN RESOLUTION, on host or device, whatever its layout:
+        the adjoint of the resize is one gather per test sample in a fixed order (no atomics), so the gradient does not depend on
+        `self.grad_batch` and repeats bit for bit.  A sample gets an exact zero where every target pixel it reaches is clipped or
+        clamped by the display model, where a downscale skips it, and in a frame no temporal window shows.  The reference (float32
+        or uint8) is a constant; one that requires grad is refused.  When both clips already have the target size the call is
+        jod_video's.  Double backward is not supported."""
+        from .resize_grad import jod_video_resized
+        return jod_video_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
+                                 fixation_point)
+
     def diff_map_images(self, test, reference, dim_order="BCHW", fixation_point=None, units="jod"):
         """Extension: the difference maps of B still-image pairs as a differentiable [B, H, W] fp32 tensor on the metric's
         device, for per-pixel losses such as `(mask * metric.diff_map_images(x, ref)).sum()`, a worst-pixel or top-k loss, or a

@@ -269,6 +269,40 @@ class YuvClipSetup(ClipSetup):
                                                          0, _ptr(oob), self.stream))
 
 
+def resize_stream(x):
+    """fvvdp_resize_stream of a device clip [C, N, h, w] (float32 or uint8; rows and planes dense)."""
+    return nat.ResizeStream(x.data_ptr(), nat.FVVDP_U8 if x.dtype is torch.uint8 else nat.FVVDP_F32, x.shape[0], x.shape[3],
+                            x.shape[2], x.stride(1), x.stride(0))
+
+
+class ResizedClipSetup(ClipSetup):
+    """ClipSetup for a pair of clips with frame sizes of their own (resize_grad): t and r are [C, N, h, w] device tensors as
+    resize_stream takes them, mode the FVVDP_RESIZE_* code, size the target (width, height) -- self.W and self.H, the size the
+    pyramid runs at; the ingest is fvvdp_temporal_channels_resized.  Taps, window list, schedule, launch and write_maps are
+    ClipSetup's."""
+
+    def __init__(self, metric, t, fps, r, mode, size, prm=None, pp=None):
+        self.t, self.r, self.mode = t, r, mode
+        self.C, self.N = t.shape[0], t.shape[1]
+        self.W, self.H = size
+        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
+        self.dtype, self.e = metric._image_eotf(torch.float32)
+        self.w = metric._rgb2y()
+        self.fl, self.taps = metric._temporal_taps(fps)
+        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
+        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
+        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
+        self._finish(metric, 4, prm, pp)
+
+    def ingest(self, lib, t, r, b0, nb, oob):
+        """(oob: the range flag of the other ingests stays as it is -- the clip to [0, 1] belongs to the resize)"""
+        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
+        ts, rs = resize_stream(t), resize_stream(r)
+        nat.check(lib.fvvdp_temporal_channels_resized(self.ctx.handle, C.byref(ts), C.byref(rs), self.mode, C.byref(self.e),
+                                                      nat.fptr(self.w), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      nat.fptr(self.taps), self.fl, nb, 0, self.stream))
+
+
 def forward_clip(s, fix):
     """JOD (0-d) and Q_per_ch [n_bands, 2, N] on the device: the launches of predict(..., sync=False), no flag read back."""
     nq = s.n_bands * 2 * s.N

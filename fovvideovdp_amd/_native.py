@@ -291,11 +291,35 @@ TESTS_GRAD_SYMBOLS = {
 }
 TESTS_GRAD_GROUP_MAX = 4                 # FVVDP_TESTS_GRAD_GROUP_MAX
 
+# include/fvvdp_hip_held.h: clips whose streams have frame counts of their own -- held frames in the ingest, and the transpose of the
+# hold in the last kernel of the backward (bound by lib() as well)
+class HeldStream(C.Structure):
+    """fvvdp_held_stream (include/fvvdp_hip_held.h): one stream with its own strides (in elements) and frame count."""
+    _fields_ = [("d_data", C.c_void_p), ("chan_stride", C.c_size_t), ("frame_stride", C.c_size_t), ("n_frames", C.c_int32)]
+
+
+HELD_SYMBOLS = {
+    "fvvdp_temporal_channels_held": (C.c_int, [C.c_void_p, C.POINTER(HeldStream), C.POINTER(HeldStream), C.c_int, C.c_int,
+                                               C.POINTER(Eotf), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "fvvdp_video_grad_input_held": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(Eotf),
+                                              C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+HELD_MAX_TAPS = 32                       # FVVDP_HELD_MAX_TAPS
+
+
+def held_map_bytes(n_display):
+    """FVVDP_HELD_MAP_BYTES"""
+    return (n_display * 4 + 255) // 256 * 256
+
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Nineteen translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-five translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
@@ -303,14 +327,16 @@ def build(force=False, verbose=False):
     (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip), the sums for the gradient with
     respect to the display's photometry (display_grad_launch.hip), the gradients of the difference map (map_grad_launch.hip), the
     float YUV planes with their gradients (yuv_grad_launch.hip), the gradients of many tests with respect to their one reference
-    (tests_grad_launch.hip) and the clips resized inside the ingest with the resize's adjoint (resize_launch.hip) -- are compiled concurrently and linked into one shared library."""
+    (tests_grad_launch.hip), the clips resized inside the ingest with the resize's adjoint (resize_launch.hip) and the clips with
+    held frames (held_launch.hip with -DHELD_PART=0..5: the ingest per sample type, then the C ABI with the backward's kernel) -- are
+    compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
                                                                                                                               "fvvdp_hip_video_grad.h", "fvvdp_hip_gaze.h", "fvvdp_hip_gaze_grad.h",
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
                                                                                                                               "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h",
-                                                                                                                              "fvvdp_hip_resize.h")]
+                                                                                                                              "fvvdp_hip_resize.h", "fvvdp_hip_held.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -355,6 +381,10 @@ def build(force=False, verbose=False):
     # given for yuv_grad_launch.hip: the interpolation of the test and of the reference stream are two copies of scalar code, and the
     # adjoint recomputes the test's values to decide the clip as the forward decided it -- all three must round alike
     units += [(os.path.join(csrc, "resize_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "resize_launch.o"))]
+    # clips whose streams have frame counts of their own (include/fvvdp_hip_held.h): the held ingest once per sample type
+    # (-DHELD_PART=0..4, new instantiations of the ring bodies of temporal_launch.hip), and the C ABI with the backward's kernel (5)
+    units += [(os.path.join(csrc, "held_launch.hip"), ["-DHELD_PART=%d" % k], os.path.join(objdir, "held_part%d.o" % k))
+              for k in range(6)]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -384,7 +414,7 @@ def lib():
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
                 list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()) + \
-                list(RESIZE_SYMBOLS.items()):
+                list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -1083,6 +1083,24 @@ int fvvdp_ctx_resized_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, 
     return FVVDP_OK;
 }
 
+// The context's side of fvvdp_temporal_channels_held (held_launch.hip): what temporal_channels_core does with the context before
+// its launches -- the slots, the luminance range behind the pyramid pass's dropped clamps, the display block as the kernels take
+// it -- and the two environment switches of the array ingest (*scalar: FVVDP_TEMPORAL_SCALAR, *debug: FVVDP_DEBUG_VARIANT).
+int fvvdp_ctx_held_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
+                         int n_out, int slot0, int* width, int* height, L0Addr* out, EotfDev* e, int* scalar, int* debug) {
+    if (c->P != 4) return fail(FVVDP_EINVAL, "the held-frame ingest is for video contexts (planes == 4)");
+    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n_out, c->max_frames);
+    luminance_slots(c, slot0, n_out);
+    luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
+    *width = c->W;
+    *height = c->H;
+    *out = level_addr(c, 0, slot0);
+    *e = make_eotf(eotf);
+    *scalar = c->env.temporal_scalar ? 1 : 0;
+    *debug = c->env.debug_variant ? 1 : 0;
+    return FVVDP_OK;
+}
+
 extern "C" int fvvdp_load_channels_planar(fvvdp_ctx* c, const float* d_R, int n, int slot0, void* stream) {
     if (!c || !d_R) return fail(FVVDP_EINVAL, "null argument");
     if (n < 1 || slot0 < 0 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");

@@ -242,6 +242,23 @@ struct TemporalArgs {
                            // frames of a stream are separate allocations (fvvdp_temporal_channels_frames)
 };
 
+// S2 (held clips, held_kernels.hpp): stream 1 has a stride pair of its own -- two size_t {chan_stride, frame_stride} that follow the
+// TemporalArgs in the kernel-argument segment (HeldTemporalArgs).  S2 = false: the one pair of the block, and the code it always was.
+struct Stream1Strides {
+    size_t chan_stride, frame_stride;
+};
+template <bool S2>
+__device__ __forceinline__ Stream1Strides stream1_strides(const TemporalArgs& a) {
+    if constexpr (S2) {
+        typedef const size_t __attribute__((address_space(4)))* karg_size_p;
+        typedef const char __attribute__((address_space(4)))* karg_p;
+        const karg_size_p q = (karg_size_p)((karg_p)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(TemporalArgs));
+        return Stream1Strides{q[0], q[1]};
+    } else {
+        return Stream1Strides{a.chan_stride, a.frame_stride};
+    }
+}
+
 // Entry of a caller-built code-value table.  The range the caller STATED for the table (fvvdp_eotf.L_min / L_max; the host passes
 // -FLT_MAX / FLT_MAX when none was stated) is enforced here: the pyramid pass drops clamps on the strength of that range
 // (clamps_never_bind in fvvdp_hip.hip), so it must hold whatever the table contains.  A table that keeps its word is unchanged
@@ -491,8 +508,9 @@ typedef const vtapf_a4 __attribute__((address_space(4)))* karg_taps_p;
 // of the next frame are fetched while the current one is filtered (software prefetch, one frame ahead).
 // Reference: fvvdp.py:294-300 (R[:,2cc+s] = sum_k window[s][k] * F[cc].flip(0)[k]).
 constexpr int TDIST = 1;        // frames of raw samples in flight per thread; 2 and 4 measured slower (VGPRs -> occupancy)
-template <int FL, int PX, int SRC>
+template <int FL, int PX, int SRC, bool S2 = false>
 __device__ __forceinline__ void temporal_ring_body(const TemporalArgs a) {
+    const Stream1Strides s1 = stream1_strides<S2>(a);
     __shared__ float lutw[SRC == SRC_U8 ? 768 : 1];
     if constexpr (SRC == SRC_U8) {
         build_lutw(lutw, a.e, a.C, a.w, threadIdx.x, 256);
@@ -524,9 +542,9 @@ __device__ __forceinline__ void temporal_ring_body(const TemporalArgs a) {
 #pragma unroll
     for (int d = 0; d < TDIST; ++d) {
         const size_t off = (size_t)idx0[d < total ? d : total - 1] * a.frame_stride;
-        const size_t off1 = (size_t)idx1[d < total ? d : total - 1] * a.frame_stride;
+        const size_t off1 = (size_t)idx1[d < total ? d : total - 1] * s1.frame_stride;
         nx[d][0] = fetch_frame<SRC, PX>(a.src[0], off, a.chan_stride, a.C, px);
-        nx[d][1] = fetch_frame<SRC, PX>(a.src[1], off1, a.chan_stride, a.C, px);
+        nx[d][1] = fetch_frame<SRC, PX>(a.src[1], off1, s1.chan_stride, a.C, px);
     }
     for (int v0 = 0; v0 < total; v0 += FL) {
 #pragma unroll
@@ -536,9 +554,9 @@ __device__ __forceinline__ void temporal_ring_body(const TemporalArgs a) {
                 const RawFrame<SRC, PX> cur0 = nx[u % TDIST][0], cur1 = nx[u % TDIST][1];
                 if (v + TDIST < total) {
                     const size_t off = (size_t)idx0[v + TDIST] * a.frame_stride;
-                    const size_t off1 = (size_t)idx1[v + TDIST] * a.frame_stride;
+                    const size_t off1 = (size_t)idx1[v + TDIST] * s1.frame_stride;
                     nx[u % TDIST][0] = fetch_frame<SRC, PX>(a.src[0], off, a.chan_stride, a.C, px);
-                    nx[u % TDIST][1] = fetch_frame<SRC, PX>(a.src[1], off1, a.chan_stride, a.C, px);
+                    nx[u % TDIST][1] = fetch_frame<SRC, PX>(a.src[1], off1, s1.chan_stride, a.C, px);
                 }
                 {
                     float L0[PX], L1[PX];
@@ -683,7 +701,7 @@ __device__ __forceinline__ void wave_lds_order() {
 // table look-ups, every step has control-flow joins and the compiler falls back to s_waitcnt vmcnt(0).
 constexpr int K1_STORE_AUX = 2;    // cache policy of the level-0 stores: 2 = nt.  0 / 1 (sc0) / 16 (sc1) / 18: this kernel within its per-process
                                    // scatter, but the pyramid pass that follows is 2 % slower behind stores that are not nt
-template <int FL, int PX, int SRC, int TD, int CC, int KIND>
+template <int FL, int PX, int SRC, int TD, int CC, int KIND, bool S2 = false>
 __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const float* lutw, float4* s_t, const int block = (int)blockIdx.x) {
     // the window index lists are the only dynamically indexed members of the argument block: read them straight from the
     // kernel-argument segment (scalar loads), otherwise the whole 2.9 KB block can end up copied to scratch
@@ -709,7 +727,12 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
     auto prefetch = [&](int v, RawVecFrame<SRC, PX>& f0, RawVecFrame<SRC, PX>& f1) {
         const int vv = min(v, total - 1);
         f0 = fetch_vec<SRC, PX>(a.src[0], (size_t)idx0[vv] * a.frame_stride + pl, a.chan_stride, CC);
-        f1 = fetch_vec<SRC, PX>(a.src[1], (size_t)idx1[vv] * a.frame_stride + pl, a.chan_stride, CC);
+        if constexpr (S2) {
+            const Stream1Strides s1 = stream1_strides<true>(a);
+            f1 = fetch_vec<SRC, PX>(a.src[1], (size_t)idx1[vv] * s1.frame_stride + pl, s1.chan_stride, CC);
+        } else {
+            f1 = fetch_vec<SRC, PX>(a.src[1], (size_t)idx1[vv] * a.frame_stride + pl, a.chan_stride, CC);
+        }
     };
     // newest frame -> ring slot u.  The pair is pinned where it is produced: the compiler otherwise sinks the channel sums
     // to their first use (many steps later), keeping three table values per pixel alive instead of one luminance.
@@ -825,10 +848,10 @@ __device__ __forceinline__ void temporal_vec_body(const TemporalArgs& a, const f
     if (is_oob(bad) && a.oob) atomicOr(a.oob, 1);
 }
 
-template <int FL, int PX, int SRC, int TD, int KIND>
+template <int FL, int PX, int SRC, int TD, int KIND, bool S2 = false>
 __device__ __forceinline__ void temporal_vec_cc(const TemporalArgs& a, const float* lutw, float4* s_t, const int block = (int)blockIdx.x) {
-    if (a.C == 3) temporal_vec_body<FL, PX, SRC, TD, 3, KIND>(a, lutw, s_t, block);
-    else temporal_vec_body<FL, PX, SRC, TD, 1, KIND>(a, lutw, s_t, block);
+    if (a.C == 3) temporal_vec_body<FL, PX, SRC, TD, 3, KIND, S2>(a, lutw, s_t, block);
+    else temporal_vec_body<FL, PX, SRC, TD, 1, KIND, S2>(a, lutw, s_t, block);
 }
 
 // waves per SIMD the register allocation aims at (uint8: 116 / 128 / 168 VGPRs for the 8 / 16 / 32-slot ring)

@@ -15,6 +15,7 @@
 //   video_input_kernel   dtest_c[j]   = w_c EOTF'(V_c[j]) sum_{p : idx[p] = j} A[p],  A[p] = sum_cc sum_k taps[cc][k] g0[p-(fl-1)+k][cc]
 #pragma once
 
+#ifndef VG_TRANSPOSE_ONLY      // (held_launch.hip takes the pieces of the temporal transpose below and none of these kernels)
 // ---- coefficients ---------------------------------------------------------------------------------------------------------
 struct VideoCoefArgs {
     const float* Q;         // Q_per_ch of the forward, [n_bands][2][N]
@@ -143,6 +144,8 @@ __global__ __launch_bounds__(256) void video_level0_kernel(const VideoLevel0Args
     const size_t o = ((size_t)k * a.h + y) * a.w + x;
     a.g0[o] = a.GL0[o] + reduce_t(a.GG1 + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
 }
+
+#endif  // VG_TRANSPOSE_ONLY
 
 // ---- temporal transpose + display model: the mirror image of temporal_vec_kernel ---------------------------------------------
 // A lane owns PX consecutive pixels for the whole launch and walks the window-list positions p = 0 .. N + fl - 2 once.  Position

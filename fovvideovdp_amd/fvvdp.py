@@ -448,6 +448,43 @@ class fvvdp:
         return jod_video_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
                                  fixation_point)
 
+    def predict_held(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, test_frames=1,
+                     reference_frames=1):
+        """Extension: predict for a test and a reference clip that each have a frame COUNT of their own -- a 30 fps encode on a
+        120 Hz panel, a 40 fps render against a 120 fps ground truth, 24 fps film with 3:2 pulldown, a ladder rung at half the
+        frame rate.  Each stream is shown by sample-and-hold through a frame map: `test_frames` / `reference_frames` is an int
+        k >= 1 (display frame v shows frame v // k) or a 1-D integer sequence, array or tensor m of one entry per display frame
+        (display frame v shows frame m[v]; non-decreasing, inside the stream; a repeat holds the frame, a skipped frame is never
+        shown and has no influence).  Both maps must lead to one number N >= 2 of display frames (else ValueError, naming both
+        counts).  `frames_per_second` is the rate of the N display frames; the taps, the temporal padding and `fixation_point`
+        ([x, y] or [N, 2]) refer to display frames.  The result equals
+        predict(test.index_select(frames, m_t), reference.index_select(frames, m_r), ...) bit for bit (JOD and Q_per_ch), and
+        no expanded clip is ever made: the ingest reads each stream through its map, a dense planar device clip in place.
+        Accepted: every array sample type predict takes (uint8, uint16, float32, float16, bfloat16; a mixed pair is unpacked
+        to float32 first), C = 1 or 3, host or device, any `dim_order`, foveated or not, every temporal padding,
+        `batch_frames=`, display rates of up to 128 frames per second (32 taps).  Refused, each with a sentence and before any
+        device work: a float, decreasing, out-of-range or wrong-length map, k < 1, N < 2, longer filters, a heat-map metric,
+        video source objects (and with them frame sharding), float samples behind a user photometry class.  When both maps
+        are the identity the call is predict's, unchanged."""
+        from .held import predict_held
+        return predict_held(self, test, reference, dim_order, frames_per_second, fixation_point, test_frames, reference_frames)
+
+    def jod_video_held(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, test_frames=1,
+                       reference_frames=1, wrt="test"):
+        """Extension: jod_video for clips with frame counts of their own (see predict_held for the frame maps), for losses such
+        as `10 - metric.jod_video_held(net(x15), ref60, frames_per_second=60, test_frames=4)`.  Returns the JOD as a 0-d fp32
+        tensor on the metric's device, bit-identical to predict_held's.  backward() puts dJOD/dtest into the caller's tensor AT
+        THE TEST'S OWN FRAME COUNT: the adjoint of index_select along the frames runs inside the last kernel of the backward
+        (a fixed sum per source frame over the display frames that show it, no atomics), so no gradient at the display's rate
+        exists, the result does not depend on `self.grad_batch` and repeats bit for bit.  A frame no display frame shows gets
+        exact zeros.  Accepted: what jod_video accepts (float32 / float16 / bfloat16 with the gradient in the dtype of the
+        input, closed-form display models, wrt="test" | "reference" | "both", every padding, foveated or not), display rates
+        of up to 128 frames per second.  The tensors saved for backward are the source clips.  When both maps are the
+        identity the call is jod_video's."""
+        from .held import jod_video_held
+        return jod_video_held(self, test, reference, dim_order, frames_per_second, fixation_point, test_frames, reference_frames,
+                              wrt)
+
     def diff_map_images(self, test, reference, dim_order="BCHW", fixation_point=None, units="jod"):
         """Extension: the difference maps of B still-image pairs as a differentiable [B, H, W] fp32 tensor on the metric's
         device, for per-pixel losses such as `(mask * metric.diff_map_images(x, ref)).sum()`, a worst-pixel or top-k loss, or a

@@ -303,6 +303,57 @@ class ResizedClipSetup(ClipSetup):
                                                       nat.fptr(self.taps), self.fl, nb, 0, self.stream))
 
 
+def held_stream(x):
+    """fvvdp_held_stream of a device clip [1, C, F, H, W] whose frames are dense (H x W contiguous; held.dense_planar)."""
+    return nat.HeldStream(x.data_ptr(), *held_strides(x), x.shape[2])
+
+
+def held_strides(x):
+    """(chan_stride, frame_stride) of the clip [1, C, F, H, W]; an axis of size 1 has no stride to speak of: one frame's size."""
+    hw = x.shape[3] * x.shape[4]
+    return (x.stride(1) if x.shape[1] > 1 else hw), (x.stride(2) if x.shape[2] > 1 else hw)
+
+
+class HeldClipSetup(ClipSetup):
+    """ClipSetup for a pair of clips with frame counts of their own (held.py): t and r are [1, C, F_s, H, W] device tensors as
+    held_stream takes them, of one dtype; m_t and m_r the frame maps (int32 [N]: display frame -> source frame).  self.N is the
+    number of DISPLAY frames: taps, window list, schedule, gaze, launch and write_maps are ClipSetup's at the display's rate; the
+    ingest is fvvdp_temporal_channels_held on the window list sent through each stream's map."""
+
+    def __init__(self, metric, t, fps, r, m_t, m_r, prm=None, pp=None):
+        self.t, self.r = t, r
+        self.m_t, self.m_r = np.ascontiguousarray(m_t, dtype=np.int32), np.ascontiguousarray(m_r, dtype=np.int32)
+        _, self.C, _, self.H, self.W = t.shape
+        self.N = len(self.m_t)
+        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
+        self.dtype, self.e = metric._image_eotf(t.dtype)
+        self.w = metric._rgb2y()
+        self.fl, self.taps = metric._temporal_taps(fps)
+        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
+        self.idx_t, self.idx_r = self.m_t[self.widx], self.m_r[self.widx]      # the per-stream lists handed to the ingest
+        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
+        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
+        self._finish(metric, 4, prm, pp)
+
+    def ingest(self, lib, t, r, b0, nb, oob):
+        i32p = C.POINTER(C.c_int32)
+        it = np.ascontiguousarray(self.idx_t[b0:b0 + self.fl - 1 + nb])
+        ir = np.ascontiguousarray(self.idx_r[b0:b0 + self.fl - 1 + nb])
+        ts, rs = held_stream(t), held_stream(r)
+        nat.check(lib.fvvdp_temporal_channels_held(self.ctx.handle, C.byref(ts), C.byref(rs), self.dtype, self.C, C.byref(self.e),
+                                                   nat.fptr(self.w), it.ctypes.data_as(i32p), ir.ctypes.data_as(i32p),
+                                                   nat.fptr(self.taps), self.fl, nb, 0, _ptr(oob), self.stream))
+
+
+def held_fold_arrays(m, widx, fl):
+    """The head of the display-rate window list (its first `fl` positions) keyed by SOURCE frame through the frame map m: the two
+    arrays fvvdp_video_grad_input_held takes -- (source frame, position), every head position exactly once, sorted by frame and
+    then by position."""
+    m, widx = np.asarray(m), np.asarray(widx)
+    order = sorted((int(m[int(widx[p])]), p) for p in range(fl))
+    return np.asarray([f for f, _ in order], dtype=np.int32), np.asarray([p for _, p in order], dtype=np.int32)
+
+
 def forward_clip(s, fix):
     """JOD (0-d) and Q_per_ch [n_bands, 2, N] on the device: the launches of predict(..., sync=False), no flag read back."""
     nq = s.n_bands * 2 * s.N

@@ -98,16 +98,22 @@ __device__ __forceinline__ float layer_term(float c, float T, float R, float Dm,
     if (!(c != 0.0f && Dm > 0.0f && Dm < a.dmax_hi && T < m * a.cmax_hi)) return 0.0f;
     const float Tp = T * s, Rp = R * s;
     const float u = Tp - Rp, au = fabsf(u);
+    // The maps hold the contrasts rounded, and the forward forms D from the unrounded difference in the log2 domain
+    // (band_kernel.hpp): two contrasts an ulp apart can collapse in T s - R s here while the stored D is tiny and positive.
+    // Such a pixel is an identical pixel, as in ref_layer_one (its log below is -inf, and D^(beta-1) = inf times a zero is NaN).
+    // The rounded products are compared as well: where the compiler fuses T s - R s into a multiply-add, u is a rounding
+    // residual of the collapsed pair, not zero
+    if (!(au > 0.0f) || Tp == Rp) return 0.0f;
     const float aT = fabsf(Tp), aR = fabsf(Rp);
     const float M = a.k_mask * fminf(aT, aR);
     const float Mq = M > 0.0f ? fast_exp2(q * fast_log2(M)) : 0.0f;
     const float den = 1.0f + Mq;
-    const float lnum = a.p * fast_log2(au);                 // au == 0 (with D > 0 it cannot be): -inf, num = 0
+    const float lnum = a.p * fast_log2(au);
     const float num = fast_exp2(lnum);
     const float rden = fast_rcp(den);
     const float D = num * rden;
     // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
-    float dD = au > 0.0f ? copysignf(a.p * num * fast_rcp(au), u) * rden : 0.0f;
+    float dD = copysignf(a.p * num * fast_rcp(au), u) * rden;
     if (M > 0.0f && aT <= aR) {
         const float share = aT < aR ? 1.0f : 0.5f;
         dD -= share * copysignf(D * rden * q * Mq * fast_rcp(aT), Tp);

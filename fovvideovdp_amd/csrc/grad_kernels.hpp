@@ -93,20 +93,25 @@ __global__ __launch_bounds__(256) void adj_layer_kernel(const GradLayerArgs a) {
         const float s = B.S[(size_t)k * 2 * hw + px] * a.gain;
         const float Tp = T * s, Rp = R * s;
         const float u = Tp - Rp, au = fabsf(u);
-        const float aT = fabsf(Tp), aR = fabsf(Rp);
-        const float M = a.k_mask * fminf(aT, aR);
-        const float Mq = M > 0.0f ? powf(M, a.q) : 0.0f;
-        const float den = 1.0f + Mq;
-        const float num = powf(au, a.p);
-        const float D = num / den;
-        // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
-        float dD = au > 0.0f ? copysignf(a.p * num / au, u) / den : 0.0f;
-        if (M > 0.0f && aT <= aR) {
-            const float share = aT < aR ? 1.0f : 0.5f;
-            dD -= share * copysignf(D / den * a.q * Mq / aT, Tp);
+        // the maps hold the contrasts rounded: a difference the rounding collapsed is an identical pixel too, whatever D the
+        // forward stored for it (ref_layer_one, layer_term: the three layer kernels agree on every map).  The rounded products
+        // are compared as well: where the compiler fuses T s - R s into a multiply-add, u is a rounding residual, not zero
+        if (au > 0.0f && Tp != Rp) {
+            const float aT = fabsf(Tp), aR = fabsf(Rp);
+            const float M = a.k_mask * fminf(aT, aR);
+            const float Mq = M > 0.0f ? powf(M, a.q) : 0.0f;
+            const float den = 1.0f + Mq;
+            const float num = powf(au, a.p);
+            const float D = num / den;
+            // dD/dT': the difference term, and the masker term where |T'| is the smaller (ties split, as torch.minimum's backward)
+            float dD = copysignf(a.p * num / au, u) / den;
+            if (M > 0.0f && aT <= aR) {
+                const float share = aT < aR ? 1.0f : 0.5f;
+                dD -= share * copysignf(D / den * a.q * Mq / aT, Tp);
+            }
+            const float lb = B.L[(size_t)k * hw + px];
+            g = c * powf(D, a.beta - 1.0f) * dD * s * (B.m / lb);
         }
-        const float lb = B.L[(size_t)k * hw + px];
-        g = c * powf(D, a.beta - 1.0f) * dD * s * (B.m / lb);
     }
     B.GL[(size_t)k * hw + px] = g;
 }

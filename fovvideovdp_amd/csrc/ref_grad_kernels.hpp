@@ -49,8 +49,9 @@ __device__ __forceinline__ void ref_layer_one(float c, float T, float R, float D
     const float Tp = T * s, Rp = R * s;
     const float u = Tp - Rp, au = fabsf(u);
     // the maps hold the contrasts rounded: a difference the rounding collapsed is an identical pixel too (its log below is
-    // -inf, and D^(beta-1) = inf times a zero would be NaN)
-    if (!(au > 0.0f)) return;
+    // -inf, and D^(beta-1) = inf times a zero would be NaN).  The rounded products are compared as well: the compiler fuses
+    // T s - R s into a multiply-add here, which leaves a rounding residual of the collapsed pair in u instead of a zero
+    if (!(au > 0.0f) || Tp == Rp) return;
     const float aT = fabsf(Tp), aR = fabsf(Rp);
     const float M = a.k_mask * fminf(aT, aR);
     const float Mq = M > 0.0f ? fast_exp2(q * fast_log2(M)) : 0.0f;

@@ -24,7 +24,11 @@ extern "C" {
 #endif
 
 /* Bytes of device workspace fvvdp_images_grad needs for n pairs of width x height with n_bands band-pass levels (the same
- * n_bands as the context's).  Errors: FVVDP_EINVAL (null output, non-positive sizes, n_bands outside [1, FVVDP_MAX_BANDS]). */
+ * n_bands as the context's).  Layout, in floats, each part 64-float (256 B) aligned, (w_b, h_b) the ceil(/2) level sizes:
+ *   coef [n][n_bands] | GL_b [n][h_b][w_b] for b in [0, n_bands) | GG_L [n][h_L][w_L] for L in [1, n_bands]
+ * (the layout of fvvdp_video_grad_workspace with one plane per batch entry).  After the call coef holds the pooling coefficient
+ * of every pair and band, GL_b the gradient of the test's layer of band b and GG_L the gradient of the Gaussian level L.
+ * Errors: FVVDP_EINVAL (null output, non-positive sizes, n_bands outside [1, FVVDP_MAX_BANDS]). */
 int fvvdp_images_grad_workspace(int width, int height, int n_bands, int n, size_t* bytes);
 
 /* h_grad_ptrs[k][c][y][x] = gamma[k] * dJOD_k / dtest_k[c][y][x] for pairs k in [0, n).

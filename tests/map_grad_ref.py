@@ -144,8 +144,18 @@ def band_forward(layer, Rc, S, L, b, cc, k):
     return T, torch.clamp(D, max=k.dmax)
 
 
-def layer_gradient(weight, T, R, Dm, S, L, b, cc, k, terms=None):
-    """weight dD/dT' S gain m / L_bkg per pixel, with the zero conventions of adj_layer_kernel on the stored maps."""
+def collapsed(T, R, S, k):
+    """Where the fp32 maps give T s == R s with s = S gain, all in fp32: the difference of the stored contrasts is gone, whatever
+    D the forward stored, and every layer kernel treats the pixel as an identical one.  (A convention on fp32 maps, so it is
+    stated in fp32; float64 maps that keep |T' - R'| well above an ulp are never collapsed.)"""
+    s32 = S.detach().float() * torch.tensor(k.gain, dtype=torch.float32)
+    return T.detach().float() * s32 == R.detach().float() * s32
+
+
+def layer_gradient(weight, T, R, Dm, S, L, b, cc, k, terms=None, mutant=None):
+    """weight dD/dT' S gain m / L_bkg per pixel, with the zero conventions of adj_layer_kernel on the stored maps.
+    mutant: a deliberately wrong variant, for the tests that show a comparison can see it ("tie_share_one": the masker term of a
+    tie |T'| == |R'| goes to T' whole; "masker_to_larger": the masker term goes to the larger of |T'|, |R'|)."""
     m = 1.0 if b == 0 else 2.0
     s = S * k.gain
     Tp, Rp = T * s, R * s
@@ -160,12 +170,17 @@ def layer_gradient(weight, T, R, Dm, S, L, b, cc, k, terms=None):
     safe_au = torch.where(au > 0, au, torch.ones_like(au))
     dD0 = torch.where(au > 0, torch.sign(u) * k.p * num / safe_au / den, torch.zeros_like(u))
     safe_aT = torch.where(aT > 0, aT, torch.ones_like(aT))
-    share = torch.where(aT < aR, torch.ones_like(aT), torch.full_like(aT, 0.5))
+    share = torch.where(aT < aR, torch.ones_like(aT), torch.full_like(aT, 1.0 if mutant == "tie_share_one" else 0.5))
     masker = share * torch.sign(Tp) * D / den * q * Mq / safe_aT
-    dD = dD0 - torch.where((M > 0) & (aT <= aR), masker, torch.zeros_like(masker))
+    has_masker = (M > 0) & (aT <= aR)
+    if mutant == "masker_to_larger":
+        masker = torch.where(aT > aR, masker / share, masker)
+        has_masker = (M > 0) & (aT >= aR)
+    dD = dD0 - torch.where(has_masker, masker, torch.zeros_like(masker))
     live = (weight != 0) & (Dm > 0) & (Dm < k.dmax * (1.0 - CLAMP_EPS)) & (T < m * k.cmax * (1.0 - CLAMP_EPS))
+    live = live & ~collapsed(T, R, S, k)
     if terms is not None:                 # the sum of the absolute values of the two terms of dD, scaled like the result
-        both = dD0.abs() + torch.where((M > 0) & (aT <= aR), masker.abs(), torch.zeros_like(masker))
+        both = dD0.abs() + torch.where(has_masker, masker.abs(), torch.zeros_like(masker))
         terms.append(torch.where(live, weight.abs() * both * s * (m / L), torch.zeros_like(dD)))
     return torch.where(live, weight * dD * s * (m / L), torch.zeros_like(dD))
 

@@ -589,14 +589,7 @@ static bool eotf_lut_range_stated(const fvvdp_eotf* e) {
 }
 static EotfDev make_eotf(const fvvdp_eotf* e) {
     EotfDev d;
-    d.kind = e->kind;
-    d.scale = e->Y_peak - e->Y_black;
-    d.y_black = e->Y_black;
-    d.y_peak = e->Y_peak;
-    d.gamma = e->gamma;
-    d.l_min = e->L_min;
-    d.l_max = e->L_max;
-    d.lut = e->d_lut;
+    ingest_fill_display(d, e);
     if (e->kind == FVVDP_EOTF_LUT && !eotf_lut_range_stated(e)) {
         // no (usable) range stated for the table: its entries pass as they are, and luminance_range() treats level 0 as unknown
         d.l_min = -FLT_MAX;
@@ -702,6 +695,65 @@ static bool clamps_never_bind(const fvvdp_ctx* c, int b, int n_levels) {
            lo >= 2.0f * c->y_lo && hi <= 0.5f * c->y_hi;             // (3) well inside the Y axis of the CSF table
 }
 
+// The context's side of an ingest (temporal_launch.hpp): the one place where the slots and the value range of level 0 are noted,
+// in this order, for the ingests of this file and of yuv_grad_launch.hip, resize_launch.hip and held_launch.hip.  The range is the
+// display model's with `channels` weights: what the ingests put in front of the model (the YUV matrix, a resize with bicubic
+// overshoot) is clipped to [0, 1] before it, and each closed-form model clamps its output.
+int fvvdp_ctx_ingest_begin(fvvdp_ctx* c, const char* what, bool even_size, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y,
+                           const float* h_taps, int fl, int n_out, int slot0, IngestBegin* b) {
+    if (what && c->P != 4) return fail(FVVDP_EINVAL, "%s is for video contexts (planes == 4)", what);
+    if (c->P == 2 && fl != 1) return fail(FVVDP_EINVAL, "still-image context (planes == 2) needs fl == 1");
+    if (even_size && ((c->W | c->H) & 1)) return fail(FVVDP_EINVAL, "4:2:0 needs even frame dimensions");
+    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n_out, c->max_frames);
+    luminance_slots(c, slot0, n_out);
+    luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
+    b->W = c->W;
+    b->H = c->H;
+    b->out = level_addr(c, 0, slot0);
+    b->e = make_eotf(eotf);
+    b->scalar = c->env.temporal_scalar;
+    b->debug = c->env.debug_variant;
+    return FVVDP_OK;
+}
+
+static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* d_ref, int dtype, int C,
+                                  size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf,
+                                  const float* h_rgb2y, const int32_t* h_frame_idx, const int32_t* h_frame_idx1,
+                                  const float* h_taps, int fl, int n_out, int slot0, int32_t* d_oob_flag, void* stream);
+
+// The two-pass path of 33..64 taps (129-256 fps) for a source the 64-slot ring is not instantiated for: every source frame of the
+// window -> fp32 luminance once, then the 64-slot ring on those frames.  `convert(uniq, lum)` launches the conversion of the source
+// frames uniq[0 .. n) (ascending, each once) into lum [2 streams][n][HW].  The events and the luminance range of the call belong to
+// the outer call: the inner one sees plain luminance frames.
+template <class Convert>
+static int two_pass_ingest(fvvdp_ctx* c, const int32_t* h_frame_idx, const float* h_taps, int fl, int n_out, int slot0,
+                           int32_t* d_oob_flag, void* stream, Convert convert) {
+    const int total = fl - 1 + n_out, HW = c->W * c->H;
+    std::vector<int> uniq(h_frame_idx, h_frame_idx + total);
+    std::sort(uniq.begin(), uniq.end());
+    uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
+    const int nu = (int)uniq.size();
+    {
+        const int rc = grow_lum_buf(c, (size_t)2 * nu * HW, fl, reinterpret_cast<hipStream_t>(stream));
+        if (rc != FVVDP_OK) return rc;
+    }
+    convert(uniq, c->lum_buf);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> pos(total);
+    for (int u = 0; u < total; ++u) pos[u] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), h_frame_idx[u]) - uniq.begin());
+    fvvdp_eotf none;
+    memset(&none, 0, sizeof(none));
+    none.kind = FVVDP_EOTF_NONE;
+    const bool timing = c->timing;
+    c->timing = false;
+    c->lum_hold += 1;
+    const int rc2 = temporal_channels_core(c, c->lum_buf, c->lum_buf + (size_t)nu * HW, FVVDP_F32, 1, 0, (size_t)HW, &none, nullptr,
+                                           pos.data(), nullptr, h_taps, fl, n_out, slot0, d_oob_flag, stream);
+    c->timing = timing;
+    c->lum_hold -= 1;
+    return rc2;
+}
+
 // h_frame_idx1: per-stream frame indices of the reference stream, or nullptr = the same as h_frame_idx
 static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* d_ref, int dtype, int C,
                                   size_t chan_stride, size_t frame_stride, const fvvdp_eotf* eotf,
@@ -712,14 +764,27 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
     if (C != 1 && C != 3) return fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (C == 3 && !h_rgb2y) return fail(FVVDP_EINVAL, "rgb2y weights required for C == 3");
     if (fl < 1 || fl > FVVDP_MAX_TAPS) return fail(FVVDP_EINVAL, "filter length %d out of range", fl);
-    if (c->P == 2 && fl != 1) return fail(FVVDP_EINVAL, "still-image context (planes == 2) needs fl == 1");
-    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n_out, c->max_frames);
     if (eotf->kind == FVVDP_EOTF_LUT && (dtype >= FVVDP_F32 || !eotf->d_lut)) return fail(FVVDP_EINVAL, "FVVDP_EOTF_LUT needs an integer source and a table");
     if (eotf->kind != FVVDP_EOTF_LUT && dtype == FVVDP_U8) return fail(FVVDP_EINVAL, "uint8 sources need FVVDP_EOTF_LUT (uint16: table or closed form)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int HW = c->W * c->H;
-    luminance_slots(c, slot0, n_out);
-    luminance_range(c, eotf, C, h_rgb2y, h_taps, fl);
+    IngestBegin b;
+    {
+        const int rc = fvvdp_ctx_ingest_begin(c, nullptr, false, C, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b);
+        if (rc != FVVDP_OK) return rc;
+    }
+    const int HW = b.W * b.H;
+    // what the three kernel families below share: TemporalArgs, LumArgs and GenericArgs begin with the same members
+    auto fill_source = [&](auto& a) {
+        a.src[0] = d_test;
+        a.src[1] = d_ref;
+        a.chan_stride = chan_stride;
+        a.frame_stride = frame_stride;
+        a.C = C;
+        a.HW = HW;
+        a.e = b.e;
+        ingest_fill_weights(a.w, C, h_rgb2y);
+        a.oob = d_oob_flag;
+    };
     Timed tm(c, 0, st);
     // register-ring kernels: up to 32 taps for every sample type, up to 64 taps (129-256 fps) for the cases of k1_ring64_ok()
     // (uint8; 16-bit / float RGB behind an sRGB or PQ display; float luminance frames); the 1-pixel-per-lane ring needs no alignment.  The 64-slot ring is not instantiated
@@ -728,113 +793,55 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
                         k1_ring64_ok(dtype, C, eotf->kind);
     const bool ring_ok = ((c->P == 4) && (fl <= 32)) || ring64;
     if (ring_ok) {
-        const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : (fl <= 32 ? 32 : 64));
-        const int max_out = T_MAX_IDX - (FL - 1);
-        // output frames [t_begin, t_end) of this call into the level-0 buffer `level0`
-        auto run = [&](int t_begin, int t_end) -> int {
-            for (int t0 = t_begin; t0 < t_end; t0 += max_out) {
-                const int nn = (t_end - t0) < max_out ? (t_end - t0) : max_out;
-                TemporalArgs a;
-                memset(&a, 0, sizeof(a));
-                a.src[0] = d_test;
-                a.src[1] = d_ref;
-                a.chan_stride = chan_stride;
-                a.frame_stride = frame_stride;
-                a.C = C;
-                a.HW = HW;
-                a.e = make_eotf(eotf);
-                if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
-                a.n_out = nn;
-                a.fl = fl;
-                a.out = level_addr(c, 0, slot0 + t0);
-                a.oob = d_oob_flag;
-                for (int k = 0; k < fl; ++k) { a.taps2[k][0] = h_taps[k]; a.taps2[k][1] = h_taps[fl + k]; }
-                // virtual time of h_frame_idx: entry (fl-1+t) is the newest frame of output t; pad older history
-                const int pad = FL - fl;
-                for (int u = 0; u < FL - 1 + nn; ++u) {
-                    const int src = t0 + u - pad;         // index into h_frame_idx
-                    a.idx[u] = h_frame_idx[src < 0 ? 0 : src];
-                    a.idx1[u] = h_frame_idx1 ? h_frame_idx1[src < 0 ? 0 : src] : a.idx[u];
+        const int FL = ingest_ring_length(fl);
+        for (const IngestWindow wnd : IngestWindows(fl, n_out)) {
+            TemporalArgs a;
+            memset(&a, 0, sizeof(a));
+            fill_source(a);
+            a.out = b.out;
+            ingest_fill_window(a, wnd, slot0, h_taps, fl, h_frame_idx, h_frame_idx1);
+            // vector path needs the lane's PX consecutive samples to be naturally aligned
+            const int PXv = k1_px(FL);        // temporal_launch.hpp
+            const size_t al = ingest_sample_bytes(dtype) * PXv;
+            const bool vec_ok = !b.scalar && (HW % PXv == 0) && (HW >= PXv) &&
+                                (chan_stride % PXv == 0) && (frame_stride % PXv == 0) &&
+                                (reinterpret_cast<uintptr_t>(d_test) % al == 0) && (reinterpret_cast<uintptr_t>(d_ref) % al == 0);
+            bool ticketed = false;
+            if (vec_ok) {
+                // uint8, 9..16 taps (33-64 fps): resident workgroups that take their pixel blocks from a counter
+                // (temporal_vec_kernel; FVVDP_K1_TICKET=0: one workgroup per block).  Same blocks, same arithmetic.
+                const bool tickets = FL == 16 && c->env.k1_ticket != 0;
+                if (tickets && dtype == FVVDP_U8 && c->d_ticket) {
+                    if (hipMemsetAsync(c->d_ticket, 0, sizeof(int), st) == hipSuccess) a.ticket = c->d_ticket;
+                    else (void)hipGetLastError();
                 }
-                // vector path needs the lane's PX consecutive samples to be naturally aligned
-                const int PXv = k1_px(FL);        // temporal_launch.hpp
-                const int es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
-                const bool vec_ok = !c->env.temporal_scalar && (HW % PXv == 0) && (HW >= PXv) &&
-                                    (chan_stride % PXv == 0) && (frame_stride % PXv == 0) &&
-                                    (reinterpret_cast<uintptr_t>(d_test) % (size_t)(es * PXv) == 0) &&
-                                    (reinterpret_cast<uintptr_t>(d_ref) % (size_t)(es * PXv) == 0);
-                bool ticketed = false;
-                if (vec_ok) {
-                    // uint8, 9..16 taps (33-64 fps): resident workgroups that take their pixel blocks from a counter
-                    // (temporal_vec_kernel; FVVDP_K1_TICKET=0: one workgroup per block).  Same blocks, same arithmetic.
-                    const bool tickets = FL == 16 && c->env.k1_ticket != 0;
-                    if (tickets && dtype == FVVDP_U8 && c->d_ticket) {
-                        if (hipMemsetAsync(c->d_ticket, 0, sizeof(int), st) == hipSuccess) a.ticket = c->d_ticket;
-                        else (void)hipGetLastError();
-                    }
-                    ticketed = k1_launch_vec(FL, dtype, a, st);
-                } else if (FL == 64) {
-                    // the 64-slot ring exists as the 1-pixel-per-lane vector kernel only; it needs nothing but element alignment
-                    return fail(FVVDP_EINVAL, "source pointers must be aligned to their element size");
-                } else {
-                    k1_launch_ring(FL, dtype, a, st);
-                }
-                if (c->env.debug_variant)                // tests: which kernel this launch ran (one line per launch of a split call)
-                    fprintf(stderr, "fvvdp: array ingest: %s, FL %d, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 %d, tickets %d\n",
-                            vec_ok ? "vector" : "per-pixel", FL, fl, dtype, C, eotf->kind, nn, t0, ticketed ? 1 : 0);
+                ticketed = k1_launch_vec(FL, dtype, a, st);
+            } else if (FL == 64) {
+                // the 64-slot ring exists as the 1-pixel-per-lane vector kernel only; it needs nothing but element alignment
+                return fail(FVVDP_EINVAL, "source pointers must be aligned to their element size");
+            } else {
+                k1_launch_ring(FL, dtype, a, st);
             }
-            return FVVDP_OK;
-        };
-        {
-            const int rc = run(0, n_out);
-            if (rc != FVVDP_OK) return rc;
+            if (b.debug)                             // tests: which kernel this launch ran (one line per launch of a split call)
+                fprintf(stderr, "fvvdp: array ingest: %s, FL %d, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 %d, tickets %d\n",
+                        vec_ok ? "vector" : "per-pixel", FL, fl, dtype, C, eotf->kind, wnd.nn, wnd.t0, ticketed ? 1 : 0);
         }
     } else if (c->P == 4 && fl > 32 && fl <= 64 && !h_frame_idx1 && !c->env.temporal_scalar &&
                fl - 1 + n_out <= T_MAX_IDX && k1_ring64_ok(FVVDP_F32, 1, FVVDP_EOTF_NONE)) {
-        // 33..64 taps (129-256 fps) for a sample type / display model the 64-slot ring is not instantiated for: two passes.
-        // Every source frame of the window -> fp32 luminance once (luminance_frames_kernel), then the 64-slot ring on those
-        // frames.  The generic kernel below would evaluate the display model fl times per pixel and output frame.
-        const int total = fl - 1 + n_out;
-        std::vector<int> uniq(h_frame_idx, h_frame_idx + total);
-        std::sort(uniq.begin(), uniq.end());
-        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-        const int nu = (int)uniq.size();
-        {
-            const int rc = grow_lum_buf(c, (size_t)2 * nu * HW, fl, st);
-            if (rc != FVVDP_OK) return rc;
-        }
-        LumArgs la;
-        memset(&la, 0, sizeof(la));
-        la.src[0] = d_test;
-        la.src[1] = d_ref;
-        la.chan_stride = chan_stride;
-        la.frame_stride = frame_stride;
-        la.C = C;
-        la.HW = HW;
-        la.e = make_eotf(eotf);
-        if (C == 3) { la.w[0] = h_rgb2y[0]; la.w[1] = h_rgb2y[1]; la.w[2] = h_rgb2y[2]; } else { la.w[0] = 1.0f; }
-        la.n_frames = nu;
-        la.out = c->lum_buf;
-        la.oob = d_oob_flag;
-        for (int k = 0; k < nu; ++k) la.fr[k] = uniq[k];
-        k1_launch_luminance(dtype, la, st);
-        if (c->env.debug_variant)                        // (n_out: the frames converted; the inner call prints its own line)
-            fprintf(stderr, "fvvdp: array ingest: luminance, FL 0, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 0, tickets 0\n",
-                    fl, dtype, C, eotf->kind, nu);
-        std::vector<int32_t> pos(total);
-        for (int u = 0; u < total; ++u) pos[u] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), h_frame_idx[u]) - uniq.begin());
-        fvvdp_eotf none;
-        memset(&none, 0, sizeof(none));
-        none.kind = FVVDP_EOTF_NONE;
-        HIP_TRY(hipGetLastError());
-        const bool timing = c->timing;
-        c->timing = false;                  // the events of this call (both passes) belong to the outer timer
-        c->lum_hold += 1;                   // ... and so does the luminance range (the inner pass sees plain luminance frames)
-        const int rc2 = temporal_channels_core(c, c->lum_buf, c->lum_buf + (size_t)nu * HW, FVVDP_F32, 1, 0, (size_t)HW, &none, nullptr,
-                                               pos.data(), nullptr, h_taps, fl, n_out, slot0, d_oob_flag, stream);
-        c->timing = timing;
-        c->lum_hold -= 1;
-        return rc2;
+        // 33..64 taps for a sample type / display model the 64-slot ring is not instantiated for: two passes, the first of them
+        // luminance_frames_kernel.  The generic kernel below would evaluate the display model fl times per pixel and output frame.
+        return two_pass_ingest(c, h_frame_idx, h_taps, fl, n_out, slot0, d_oob_flag, stream, [&](const std::vector<int>& uniq, float* lum) {
+            LumArgs la;
+            memset(&la, 0, sizeof(la));
+            fill_source(la);
+            la.n_frames = (int)uniq.size();
+            la.out = lum;
+            std::copy(uniq.begin(), uniq.end(), la.fr);
+            k1_launch_luminance(dtype, la, st);
+            if (b.debug)                                 // (n_out: the frames converted; the inner call prints its own line)
+                fprintf(stderr, "fvvdp: array ingest: luminance, FL 0, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 0, tickets 0\n",
+                        fl, dtype, C, eotf->kind, la.n_frames);
+        });
     } else {
         // images, more than 64 taps and frame sizes without 4-sample alignment: one thread per pixel and output frame
         if (h_frame_idx1) return fail(FVVDP_EINVAL, "per-frame source pointers are supported for video with fl <= 32 (uint8: 64) only");
@@ -852,22 +859,14 @@ static int temporal_channels_core(fvvdp_ctx* c, const void* d_test, const void* 
             HIP_TRY(hipMemcpy(c->d_taps, h_taps, sizeof(float) * 2 * fl, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(c->d_idx, h_frame_idx, sizeof(int) * (fl - 1 + n_out), hipMemcpyHostToDevice));
         }
-        a.src[0] = d_test;
-        a.src[1] = d_ref;
-        a.chan_stride = chan_stride;
-        a.frame_stride = frame_stride;
-        a.C = C;
-        a.HW = HW;
-        a.e = make_eotf(eotf);
-        if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
+        fill_source(a);
         a.n_out = n_out;
         a.fl = fl;
-        a.out = level_addr(c, 0, slot0);
-        a.oob = d_oob_flag;
+        a.out = b.out;
         a.taps = c->d_taps;
         a.idx = c->d_idx;
         k1_launch_generic(c->P, dtype, a, st);
-        if (c->env.debug_variant)
+        if (b.debug)
             fprintf(stderr, "fvvdp: array ingest: generic, FL 0, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 0, tickets 0\n",
                     fl, dtype, C, eotf->kind, n_out);
     }
@@ -892,7 +891,7 @@ extern "C" int fvvdp_temporal_channels_frames(fvvdp_ctx* c, const void* const* h
     if (dtype < FVVDP_U8 || dtype > FVVDP_BF16) return fail(FVVDP_EINVAL, "Only uint8, uint16 and float32 (and float16, bfloat16 read as float32) is currently supported");
     if (fl < 1 || fl > ((eotf && k1_ring64_ok(dtype, C, eotf->kind)) ? 64 : 32) || c->P != 4)
         return fail(FVVDP_EUNSUPPORTED, "per-frame source pointers: video contexts with fl <= 32 (uint8, float luminance: 64) only");
-    const size_t es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
+    const size_t es = ingest_sample_bytes(dtype);
     // every frame is addressed as base + index * frame_stride with ONE base per stream: base = lowest frame address,
     // frame_stride = the coarsest granule (4 elements, else 1) that divides every distance; indices are 31-bit
     const void* const* fr[2] = {h_test_frames, h_ref_frames};
@@ -936,111 +935,58 @@ extern "C" int fvvdp_temporal_channels_yuv(fvvdp_ctx* c, const void* d_test, con
                                            const int32_t* h_frame_idx, const float* h_taps, int fl, int n_out, int slot0,
                                            int32_t* d_oob_flag, void* stream) {
     if (!c || !d_test || !d_ref || !fmt || !eotf || !h_rgb2y || !h_frame_idx || !h_taps) return fail(FVVDP_EINVAL, "null argument");
-    if (c->P != 4) return fail(FVVDP_EINVAL, "YUV ingest is for video contexts (planes == 4)");
     if (fmt->bit_depth < 8 || fmt->bit_depth > 16) return fail(FVVDP_EINVAL, "bit depth %d not supported", fmt->bit_depth);
-    if (fmt->chroma_420 && ((c->W | c->H) & 1)) return fail(FVVDP_EINVAL, "4:2:0 needs even frame dimensions");
     if (fl < 1 || fl > 64) return fail(FVVDP_EINVAL, "filter length %d out of range for the YUV path (1..64)", fl);
-    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");
     if (eotf->kind == FVVDP_EOTF_LUT) return fail(FVVDP_EINVAL, "YUV sources need a closed-form display model (RGB is fractional after the matrix)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    luminance_slots(c, slot0, n_out);
-    luminance_range(c, eotf, 3, h_rgb2y, h_taps, fl);        // (RGB is clamped to [0,1] before the display model)
-    Timed tm(c, 0, st);
-    if (fl > 32) {
-        // 33..64 taps (129-256 fps): every source frame of the window -> fp32 luminance once, then the 64-slot ring on the
-        // luminance frames (see temporal_channels_core)
-        const int total = fl - 1 + n_out;
-        if (total > T_MAX_IDX) return fail(FVVDP_EINVAL, "too many frames for one call");
-        const int HW = c->W * c->H;
-        std::vector<int> uniq(h_frame_idx, h_frame_idx + total);
-        std::sort(uniq.begin(), uniq.end());
-        uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
-        const int nu = (int)uniq.size();
-        {
-            const int rc = grow_lum_buf(c, (size_t)2 * nu * HW, fl, st);
-            if (rc != FVVDP_OK) return rc;
-        }
-        YuvLumArgs la;
-        memset(&la, 0, sizeof(la));
-        YuvArgs& a = la.y;
-        a.src[0] = d_test;
-        a.src[1] = d_ref;
-        a.frame_stride = frame_stride;
-        a.W = c->W;
-        a.H = c->H;
-        a.chroma420 = fmt->chroma_420 ? 1 : 0;
-        a.uvw = fmt->chroma_420 ? c->W / 2 : c->W;
-        a.uvh = fmt->chroma_420 ? c->H / 2 : c->H;
-        const float scale = (float)(1 << (fmt->bit_depth - 8));
-        a.wy = 1.0f / (scale * 219.0f);
-        a.wc = 1.0f / (scale * 224.0f);
-        for (int i = 0; i < 9; ++i) a.m[i] = fmt->ycbcr2rgb[i];
-        a.e = make_eotf(eotf);
-        a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2];
-        a.oob = d_oob_flag;
-        la.n_frames = nu;
-        la.out = c->lum_buf;
-        for (int k = 0; k < nu; ++k) la.fr[k] = uniq[k];
-        k1_launch_yuv_luminance(fmt->bit_depth > 8 ? 2 : 1, la, st);
-        HIP_TRY(hipGetLastError());
-        if (c->env.debug_variant)                        // tests: which ingest path ran (the per-pixel arithmetic takes the nine-term matrix)
-            fprintf(stderr, "fvvdp: yuv ingest: two-pass, FL 64, fl %d, bytes %d, chroma_420 %d, eotf kind %d, matrix nine-term\n",
-                    fl, fmt->bit_depth > 8 ? 2 : 1, a.chroma420, eotf->kind);
-        std::vector<int32_t> pos(total);
-        for (int u = 0; u < total; ++u) pos[u] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), h_frame_idx[u]) - uniq.begin());
-        fvvdp_eotf none;
-        memset(&none, 0, sizeof(none));
-        none.kind = FVVDP_EOTF_NONE;
-        const bool timing = c->timing;
-        c->timing = false;
-        c->lum_hold += 1;
-        const int rc2 = temporal_channels_core(c, c->lum_buf, c->lum_buf + (size_t)nu * HW, FVVDP_F32, 1, 0, (size_t)HW, &none, nullptr,
-                                               pos.data(), nullptr, h_taps, fl, n_out, slot0, d_oob_flag, stream);
-        c->timing = timing;
-        c->lum_hold -= 1;
-        return rc2;
+    IngestBegin b;
+    {
+        const int rc = fvvdp_ctx_ingest_begin(c, "YUV ingest", fmt->chroma_420 != 0, 3, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b);
+        if (rc != FVVDP_OK) return rc;
     }
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : 32);
-    const int max_out = T_MAX_IDX - (FL - 1);
-    for (int t0 = 0; t0 < n_out; t0 += max_out) {
-        const int nn = (n_out - t0) < max_out ? (n_out - t0) : max_out;
-        YuvArgs a;
-        memset(&a, 0, sizeof(a));
-        a.src[0] = d_test;
-        a.src[1] = d_ref;
-        a.frame_stride = frame_stride;
-        a.W = c->W;
-        a.H = c->H;
-        a.chroma420 = fmt->chroma_420 ? 1 : 0;
-        a.uvw = fmt->chroma_420 ? c->W / 2 : c->W;
-        a.uvh = fmt->chroma_420 ? c->H / 2 : c->H;
-        const float scale = (float)(1 << (fmt->bit_depth - 8));
-        a.wy = 1.0f / (scale * 219.0f);
-        a.wc = 1.0f / (scale * 224.0f);
-        for (int i = 0; i < 9; ++i) a.m[i] = fmt->ycbcr2rgb[i];
-        a.e = make_eotf(eotf);
-        a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2];
-        a.n_out = nn;
-        a.fl = fl;
-        a.out = level_addr(c, 0, slot0 + t0);
-        a.oob = d_oob_flag;
-        for (int k = 0; k < fl; ++k) { a.taps2[k][0] = h_taps[k]; a.taps2[k][1] = h_taps[fl + k]; }
-        const int pad = FL - fl;
-        for (int u = 0; u < FL - 1 + nn; ++u) {
-            const int src = t0 + u - pad;
-            a.idx[u] = h_frame_idx[src < 0 ? 0 : src];
-        }
-        const int bytes = fmt->bit_depth > 8 ? 2 : 1;
+    Timed tm(c, 0, st);
+    // what every launch of the call takes: the streams, the unpack, the display model (the window's part follows per launch)
+    YuvArgs base;
+    memset(&base, 0, sizeof(base));
+    base.src[0] = d_test;
+    base.src[1] = d_ref;
+    base.frame_stride = frame_stride;
+    ingest_fill_unpack(base, b.W, b.H, fmt);
+    base.e = b.e;
+    ingest_fill_weights(base.w, 3, h_rgb2y);
+    base.oob = d_oob_flag;
+    const int bytes = fmt->bit_depth > 8 ? 2 : 1;
+    if (fl > 32) {
+        // 33..64 taps (129-256 fps): two passes, the first of them yuv_luminance_frames_kernel
+        if (fl - 1 + n_out > T_MAX_IDX) return fail(FVVDP_EINVAL, "too many frames for one call");
+        return two_pass_ingest(c, h_frame_idx, h_taps, fl, n_out, slot0, d_oob_flag, stream, [&](const std::vector<int>& uniq, float* lum) {
+            YuvLumArgs la;
+            memset(&la, 0, sizeof(la));
+            la.y = base;
+            la.n_frames = (int)uniq.size();
+            la.out = lum;
+            std::copy(uniq.begin(), uniq.end(), la.fr);
+            k1_launch_yuv_luminance(bytes, la, st);
+            if (b.debug)                                 // tests: which ingest path ran (the per-pixel arithmetic takes the nine-term matrix)
+                fprintf(stderr, "fvvdp: yuv ingest: two-pass, FL 64, fl %d, bytes %d, chroma_420 %d, eotf kind %d, matrix nine-term\n",
+                        fl, bytes, base.chroma420, eotf->kind);
+        });
+    }
+    const int FL = ingest_ring_length(fl);
+    for (const IngestWindow wnd : IngestWindows(fl, n_out)) {
+        YuvArgs a = base;
+        a.out = b.out;
+        ingest_fill_window(a, wnd, slot0, h_taps, fl, h_frame_idx);
         // vector kernel: 4 consecutive pixels per lane -> rows, planes and frames must keep 4-sample alignment
         const size_t al = (size_t)bytes * 4;
-        const bool vec_ok = !c->env.temporal_scalar && FL <= 16 && (c->W % 4 == 0) && (frame_stride % 4 == 0) &&
+        const bool vec_ok = !b.scalar && FL <= 16 && (b.W % 4 == 0) && (frame_stride % 4 == 0) &&
                             (reinterpret_cast<uintptr_t>(d_test) % al == 0) && (reinterpret_cast<uintptr_t>(d_ref) % al == 0);
         if (vec_ok) {
             k1_launch_yuv_vec(FL, bytes, a.chroma420 != 0, c->env.yuv_general, a, st);
         } else {
             k1_launch_yuv(FL, bytes, a, st);
         }
-        if (c->env.debug_variant) {                      // tests: which instantiation was launched
+        if (b.debug) {                                   // tests: which instantiation was launched
             // the ITU shape that selects the four-term matrix (yuv_matrix_is_standard, temporal_launch.hip); the per-pixel kernel has the nine-term form only
             const bool itu = a.m[0] == 1.0f && a.m[3] == 1.0f && a.m[6] == 1.0f && a.m[1] == 0.0f && a.m[8] == 0.0f;
             fprintf(stderr, "fvvdp: yuv ingest: %s, FL %d, fl %d, bytes %d, chroma_420 %d, eotf kind %d, matrix %s\n",
@@ -1049,55 +995,6 @@ extern "C" int fvvdp_temporal_channels_yuv(fvvdp_ctx* c, const void* d_test, con
         }
     }
     HIP_TRY(hipGetLastError());
-    return FVVDP_OK;
-}
-
-// The context's side of fvvdp_temporal_channels_yuv_planes (yuv_grad_launch.hip, include/fvvdp_hip_yuv_grad.h): the checks the
-// function above makes on the context, the same bookkeeping of level 0's value range, the frame size and where slot0 lies.  Host
-// code only: the kernels and their launches live in that translation unit.
-int fvvdp_ctx_yuv_planes_begin(fvvdp_ctx* c, int chroma_420, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps,
-                               int fl, int n_out, int slot0, int* width, int* height, L0Addr* out) {
-    if (c->P != 4) return fail(FVVDP_EINVAL, "YUV ingest is for video contexts (planes == 4)");
-    if (chroma_420 && ((c->W | c->H) & 1)) return fail(FVVDP_EINVAL, "4:2:0 needs even frame dimensions");
-    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");
-    luminance_slots(c, slot0, n_out);
-    luminance_range(c, eotf, 3, h_rgb2y, h_taps, fl);
-    *width = c->W;
-    *height = c->H;
-    *out = level_addr(c, 0, slot0);
-    return FVVDP_OK;
-}
-
-// The context's side of fvvdp_temporal_channels_resized (resize_launch.hip, include/fvvdp_hip_resize.h), as the function above:
-// the context's frame size is the target of the resize.  The range of level 0 is the display model's with `channels` weights: every
-// interpolated value is clipped to [0, 1] before the model (bicubic overshoot included), and each closed-form model clamps its output.
-int fvvdp_ctx_resized_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
-                            int n_out, int slot0, int* width, int* height, L0Addr* out) {
-    if (c->P != 4) return fail(FVVDP_EINVAL, "the resizing ingest is for video contexts (planes == 4)");
-    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots out of range");
-    luminance_slots(c, slot0, n_out);
-    luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
-    *width = c->W;
-    *height = c->H;
-    *out = level_addr(c, 0, slot0);
-    return FVVDP_OK;
-}
-
-// The context's side of fvvdp_temporal_channels_held (held_launch.hip): what temporal_channels_core does with the context before
-// its launches -- the slots, the luminance range behind the pyramid pass's dropped clamps, the display block as the kernels take
-// it -- and the two environment switches of the array ingest (*scalar: FVVDP_TEMPORAL_SCALAR, *debug: FVVDP_DEBUG_VARIANT).
-int fvvdp_ctx_held_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
-                         int n_out, int slot0, int* width, int* height, L0Addr* out, EotfDev* e, int* scalar, int* debug) {
-    if (c->P != 4) return fail(FVVDP_EINVAL, "the held-frame ingest is for video contexts (planes == 4)");
-    if (n_out < 1 || slot0 < 0 || slot0 + n_out > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n_out, c->max_frames);
-    luminance_slots(c, slot0, n_out);
-    luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
-    *width = c->W;
-    *height = c->H;
-    *out = level_addr(c, 0, slot0);
-    *e = make_eotf(eotf);
-    *scalar = c->env.temporal_scalar ? 1 : 0;
-    *debug = c->env.debug_variant ? 1 : 0;
     return FVVDP_OK;
 }
 
@@ -1138,14 +1035,7 @@ extern "C" int fvvdp_yuv_frame_resized(const void* d_frame, const fvvdp_yuv_form
     YuvRgbArgs y;
     memset(&y, 0, sizeof(y));
     y.src = d_frame;
-    y.W = W; y.H = H;
-    y.chroma420 = fmt->chroma_420 ? 1 : 0;
-    y.uvw = fmt->chroma_420 ? W / 2 : W;
-    y.uvh = fmt->chroma_420 ? H / 2 : H;
-    const float scale = (float)(1 << (fmt->bit_depth - 8));
-    y.wy = 1.0f / (scale * 219.0f);
-    y.wc = 1.0f / (scale * 224.0f);
-    for (int i = 0; i < 9; ++i) y.m[i] = fmt->ycbcr2rgb[i];
+    ingest_fill_unpack(y, W, H, fmt);
     y.out = d_rgb_scratch;
     const dim3 block(256), g1((unsigned)(((long long)W * H + 255) / 256));
     if (fmt->bit_depth > 8) hipLaunchKernelGGL((yuv_rgb_planar_kernel<unsigned short>), g1, block, 0, st, y);
@@ -1157,7 +1047,7 @@ extern "C" int fvvdp_yuv_frame_resized(const void* d_frame, const fvvdp_yuv_form
     r.sx = (float)W / (float)out_w;
     r.sy = (float)H / (float)out_h;
     r.e = make_eotf(eotf);
-    r.w[0] = h_rgb2y[0]; r.w[1] = h_rgb2y[1]; r.w[2] = h_rgb2y[2];
+    ingest_fill_weights(r.w, 3, h_rgb2y);
     r.lum = d_lum;
     r.rgb_out = d_rgb_out;
     const dim3 g2((unsigned)(((long long)out_w * out_h + 255) / 256));
@@ -1195,14 +1085,14 @@ extern "C" int fvvdp_pu21_sse(const void* d_test, const void* d_ref, int dtype, 
     const unsigned int per = (unsigned int)((n_pixels + FVVDP_PSNR_SLICES - 1) / FVVDP_PSNR_SLICES);
     a.chunk = (per + 3u) & ~3u;
     a.e = make_eotf(eotf);
-    if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
+    ingest_fill_weights(a.w, C, h_rgb2y);
     for (int i = 0; i < 7; ++i) a.p[i] = pu->p[i];
     a.l_min = pu->L_min;
     a.l_max = pu->L_max;
     a.partial = d_partial;
     a.oob = d_oob_flag;
     // 4 consecutive samples per load where every plane and frame keeps 4-sample alignment
-    const int es = dtype == FVVDP_U8 ? 1 : (dtype == FVVDP_U16 ? 2 : 4);
+    const size_t es = ingest_sample_bytes(dtype);
     const bool vec_ok = (n_pixels % 4 == 0) && (chan_stride % 4 == 0) && (frame_stride % 4 == 0) &&
                         (reinterpret_cast<uintptr_t>(d_test) % (size_t)(es * 4) == 0) &&
                         (reinterpret_cast<uintptr_t>(d_ref) % (size_t)(es * 4) == 0);
@@ -2343,7 +2233,7 @@ extern "C" int fvvdp_images_channels(fvvdp_ctx* c, const void* const* h_test_ptr
     if (eotf->kind == FVVDP_EOTF_NONE) return fail(FVVDP_EINVAL, "images need a display model (kind != FVVDP_EOTF_NONE)");
     const int HW = c->W * c->H;
     if (C == 3 && chan_stride < (size_t)HW) return fail(FVVDP_EINVAL, "chan_stride %zu is below the image size %d", chan_stride, HW);
-    const size_t es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
+    const size_t es = ingest_sample_bytes(dtype);
     // PX = 4 when every group of four pixels is one naturally aligned load per channel
     bool vec = HW % 4 == 0 && (C == 1 || chan_stride % 4 == 0);
     for (int k = 0; k < n; ++k) {
@@ -2363,7 +2253,7 @@ extern "C" int fvvdp_images_channels(fvvdp_ctx* c, const void* const* h_test_ptr
     a.C = C;
     a.HW = HW;
     a.e = make_eotf(eotf);
-    if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
+    ingest_fill_weights(a.w, C, h_rgb2y);
     for (int k0 = 0; k0 < n; k0 += STILL_MAX_SLOTS) {           // the pointer table of one launch holds 128 pairs
         const int nk = (n - k0) < STILL_MAX_SLOTS ? (n - k0) : STILL_MAX_SLOTS;
         for (int k = 0; k < nk; ++k) {

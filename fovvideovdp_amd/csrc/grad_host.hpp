@@ -9,6 +9,7 @@
 #include <initializer_list>
 
 #include "grad_common.hpp"     // GradSweepArgs
+#include "ingest_host.hpp"     // the display block and the luminance weights
 
 int fvvdp_fail_from(int code, const char* msg);      // fvvdp_hip.hip: sets the message of fvvdp_last_error
 // adj_sweep_kernel on `planes` planes of one level.  The kernel is defined in grad_launch.hip only, so is this function
@@ -224,13 +225,7 @@ static hipError_t grad_sweep_levels(float* ws, const GradLayout& L, int n_bands,
 
 // a closed-form display model and the luminance weights of C channels, into a zeroed argument block
 static void grad_fill_eotf(EotfDev& e, float (&wgt)[3], const fvvdp_eotf* eotf, int C, const float* h_rgb2y) {
-    e.kind = eotf->kind;
-    e.scale = eotf->Y_peak - eotf->Y_black;
-    e.y_black = eotf->Y_black;
-    e.y_peak = eotf->Y_peak;
-    e.gamma = eotf->gamma;
-    e.l_min = eotf->L_min;
-    e.l_max = eotf->L_max;
+    ingest_fill_display(e, eotf);
     e.lut = nullptr;
-    if (C == 3) { wgt[0] = h_rgb2y[0]; wgt[1] = h_rgb2y[1]; wgt[2] = h_rgb2y[2]; } else { wgt[0] = 1.0f; }
+    ingest_fill_weights(wgt, C, h_rgb2y);
 }

@@ -2,7 +2,7 @@
 // held_kernels.hpp.  Compiled once per HELD_PART, as temporal_launch.hip is per K1_PART: parts 0..4 instantiate the held ingest for
 // one sample type each (uint8, uint16, float32, float16, bfloat16 -- the ring bodies are fully unrolled per ring length, channel
 // count and display model); part 5 holds the C ABI, the dispatcher and the backward's kernel.  The one function that needs a
-// context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_held_begin).
+// context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_ingest_begin).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cstddef>
@@ -75,10 +75,6 @@ void held_ingest_f32(int, bool, const HeldTemporalArgs&, hipStream_t);
 void held_ingest_f16(int, bool, const HeldTemporalArgs&, hipStream_t);
 void held_ingest_bf16(int, bool, const HeldTemporalArgs&, hipStream_t);
 
-// fvvdp_hip.hip
-int fvvdp_ctx_held_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
-                         int n_out, int slot0, int* width, int* height, L0Addr* out, EotfDev* e, int* scalar, int* debug);
-
 static int check_fl(int fl, const char* what) {
     if (fl < 1 || fl > FVVDP_MAX_TAPS) return grad_fail(FVVDP_EINVAL, "filter length %d outside [1, %d]", fl, FVVDP_MAX_TAPS);
     if (fl > FVVDP_HELD_MAX_TAPS)
@@ -119,20 +115,16 @@ extern "C" int fvvdp_temporal_channels_held(fvvdp_ctx* ctx, const fvvdp_held_str
         if (h_idx_ref[u] < 0 || h_idx_ref[u] >= ref->n_frames)
             return grad_fail(FVVDP_EINVAL, "list entry %d names frame %d outside the reference's [0, %d)", u, h_idx_ref[u], ref->n_frames);
     }
-    int W = 0, H = 0, scalar = 0, debug = 0;
-    L0Addr out;
-    EotfDev e;
-    GRAD_CHECK(fvvdp_ctx_held_begin(ctx, C, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &W, &H, &out, &e, &scalar, &debug));
-    const int HW = W * H;
-    const size_t es = dtype == FVVDP_U8 ? 1 : ((dtype == FVVDP_U16 || dtype >= FVVDP_F16) ? 2 : 4);
+    IngestBegin b;
+    GRAD_CHECK(fvvdp_ctx_ingest_begin(ctx, "the held-frame ingest", false, C, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b));
+    const int HW = b.W * b.H;
+    const size_t es = ingest_sample_bytes(dtype);
     GRAD_CHECK(check_stream(test, "test", C, (size_t)HW, es));
     GRAD_CHECK(check_stream(ref, "reference", C, (size_t)HW, es));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : 32);
-    const int max_out = T_MAX_IDX - (FL - 1);
-    for (int t0 = 0; t0 < n_out; t0 += max_out) {
-        const int nn = (n_out - t0) < max_out ? (n_out - t0) : max_out;
+    const int FL = ingest_ring_length(fl);
+    for (const IngestWindow wnd : IngestWindows(fl, n_out)) {
         HeldTemporalArgs h;
         memset(&h, 0, sizeof(h));
         TemporalArgs& a = h.a;
@@ -144,24 +136,14 @@ extern "C" int fvvdp_temporal_channels_held(fvvdp_ctx* ctx, const fvvdp_held_str
         h.frame_stride1 = ref->frame_stride;
         a.C = C;
         a.HW = HW;
-        a.e = e;
-        if (C == 3) { a.w[0] = h_rgb2y[0]; a.w[1] = h_rgb2y[1]; a.w[2] = h_rgb2y[2]; } else { a.w[0] = 1.0f; }
-        a.n_out = nn;
-        a.fl = fl;
-        a.out = out;
-        a.out.slot0 = slot0 + t0;
+        a.e = b.e;
+        ingest_fill_weights(a.w, C, h_rgb2y);
+        a.out = b.out;
         a.oob = d_oob_flag;
-        for (int k = 0; k < fl; ++k) { a.taps2[k][0] = h_taps[k]; a.taps2[k][1] = h_taps[fl + k]; }
-        // virtual time of the lists: entry (fl - 1 + t) is the newest frame of output t; older history is padded (zero taps)
-        const int pad = FL - fl;
-        for (int u = 0; u < FL - 1 + nn; ++u) {
-            const int s = t0 + u - pad;
-            a.idx[u] = h_idx_test[s < 0 ? 0 : s];
-            a.idx1[u] = h_idx_ref[s < 0 ? 0 : s];
-        }
+        ingest_fill_window(a, wnd, slot0, h_taps, fl, h_idx_test, h_idx_ref);       // (both lists are checked above)
         // the vector variant needs a lane's PX consecutive samples naturally aligned, in both streams
         const size_t PXv = (size_t)k1_px(FL);
-        const bool vec = !scalar && (size_t)HW % PXv == 0 && (size_t)HW >= PXv &&
+        const bool vec = !b.scalar && (size_t)HW % PXv == 0 && (size_t)HW >= PXv &&
                          (a.chan_stride | a.frame_stride | h.chan_stride1 | h.frame_stride1) % PXv == 0 &&
                          (reinterpret_cast<uintptr_t>(test->d_data) | reinterpret_cast<uintptr_t>(ref->d_data)) % (es * PXv) == 0;
         switch (dtype) {
@@ -172,9 +154,9 @@ extern "C" int fvvdp_temporal_channels_held(fvvdp_ctx* ctx, const fvvdp_held_str
             default: held_ingest_f32(FL, vec, h, st); break;
         }
         GRAD_HIP_TRY(hipGetLastError());
-        if (debug)                                  // tests: which kernel this launch ran
+        if (b.debug)                                // tests: which kernel this launch ran
             fprintf(stderr, "fvvdp: held ingest: %s, FL %d, fl %d, dtype %d, C %d, eotf kind %d, n_out %d, t0 %d\n",
-                    vec ? "vector" : "per-pixel", FL, fl, dtype, C, eotf->kind, nn, t0);
+                    vec ? "vector" : "per-pixel", FL, fl, dtype, C, eotf->kind, wnd.nn, wnd.t0);
     }
     return FVVDP_OK;
 }

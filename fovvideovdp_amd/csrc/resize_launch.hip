@@ -1,6 +1,6 @@
 // Clips whose streams have frame sizes of their own (include/fvvdp_hip_resize.h): argument checks and launches of the kernels of
 // resize_clip_kernels.hpp.  A translation unit of its own, as yuv_grad_launch.hip: it instantiates no kernel template of the other
-// units, and the one function that needs a context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_resized_begin).
+// units, and the one function that needs a context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_ingest_begin).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cmath>
@@ -12,16 +12,12 @@
 #include "fvvdp_hip.h"
 #include "fvvdp_hip_resize.h"
 #include "device_common.hpp"
-#include "temporal_kernels.hpp"
+#include "temporal_launch.hpp"     // fvvdp_ctx_ingest_begin
 #include "grad_common.hpp"
 #include "resize_clip_kernels.hpp"
 #include "grad_host.hpp"
 
 static_assert(FVVDP_RESIZE_MAX_TAPS == 32, "ResizedArgs::taps2");
-
-// fvvdp_hip.hip
-int fvvdp_ctx_resized_begin(fvvdp_ctx* c, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps, int fl,
-                            int n_out, int slot0, int* width, int* height, L0Addr* out);
 
 static int check_mode(int mode) {
     if (mode < FVVDP_RESIZE_NEAREST || mode > FVVDP_RESIZE_AREA) return grad_fail(FVVDP_EINVAL, "unknown resize mode %d", mode);
@@ -95,15 +91,14 @@ extern "C" int fvvdp_temporal_channels_resized(fvvdp_ctx* ctx, const fvvdp_resiz
     GRAD_CHECK(check_stream(ref, "reference", false));
     if (test->channels != ref->channels)
         return grad_fail(FVVDP_EINVAL, "test and reference differ in their channel counts (%d and %d)", test->channels, ref->channels);
-    int W = 0, H = 0;
-    L0Addr out;
-    GRAD_CHECK(fvvdp_ctx_resized_begin(ctx, test->channels, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &W, &H, &out));
+    // (the context's frame size is the target of the resize)
+    IngestBegin b;
+    GRAD_CHECK(fvvdp_ctx_ingest_begin(ctx, "the resizing ingest", false, test->channels, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b));
+    const int W = b.W, H = b.H;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : 32);
-    const int max_out = T_MAX_IDX - (FL - 1);
-    for (int t0 = 0; t0 < n_out; t0 += max_out) {
-        const int nn = (n_out - t0) < max_out ? (n_out - t0) : max_out;
+    const int FL = ingest_ring_length(fl);
+    for (const IngestWindow wnd : IngestWindows(fl, n_out)) {
         ResizedArgs a;
         memset(&a, 0, sizeof(a));
         a.src[0] = dev_stream(test, W, H);
@@ -111,19 +106,9 @@ extern "C" int fvvdp_temporal_channels_resized(fvvdp_ctx* ctx, const fvvdp_resiz
         a.Wo = W;
         a.Ho = H;
         grad_fill_eotf(a.e, a.w, eotf, test->channels, h_rgb2y);
-        a.n_out = nn;
-        a.fl = fl;
-        a.out = out;
-        a.out.slot0 = slot0 + t0;
-        for (int k = 0; k < fl; ++k) { a.taps2[k][0] = h_taps[k]; a.taps2[k][1] = h_taps[fl + k]; }
-        // virtual time of h_frame_idx: entry (fl - 1 + t) is the newest frame of output t; older history is padded (zero taps)
-        const int pad = FL - fl;
-        for (int u = 0; u < FL - 1 + nn; ++u) {
-            const int src = t0 + u - pad;
-            const int f = h_frame_idx[src < 0 ? 0 : src];
-            if (f < 0) return grad_fail(FVVDP_EINVAL, "frame index %d out of range", f);
-            a.idx[u] = f;
-        }
+        a.out = b.out;
+        if (const int32_t* f = ingest_fill_window(a, wnd, slot0, h_taps, fl, h_frame_idx))
+            return grad_fail(FVVDP_EINVAL, "frame index %d out of range", *f);
         if (FL == 8) launch_ring<8>(mode, a, st);
         else if (FL == 16) launch_ring<16>(mode, a, st);
         else launch_ring<32>(mode, a, st);

@@ -1,6 +1,7 @@
 // Stage 1 kernels: unpack + display photometry + luminance + temporal filter -> pyramid level 0.
 // Included by fvvdp_hip.hip (one translation unit).
 #pragma once
+#include "ingest_host.hpp"     // T_MAX_IDX
 // ------------------------------------------------------------------------------------------------------------
 // stage 1: unpack + display photometry + luminance + temporal FIR  ->  pyramid level 0 (interleaved planes)
 // ------------------------------------------------------------------------------------------------------------
@@ -223,7 +224,6 @@ struct Sampler {
     }
 };
 
-#define T_MAX_IDX 320   // history + outputs of one launch
 struct TemporalArgs {
     const void* src[2];
     size_t chan_stride, frame_stride;

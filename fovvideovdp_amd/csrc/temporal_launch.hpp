@@ -15,6 +15,20 @@ static inline bool k1_ring64_ok(int dtype, int C, int eotf_kind) {
     return dtype == FVVDP_F32 && C == 1 && eotf_kind == FVVDP_EOTF_NONE;                          // luminance frames
 }
 
+// The context's side of an ingest (fvvdp_hip.hip), for every entry point that writes a clip into level 0, in whichever translation
+// unit its kernels live.  Checks the context -- planes == 4 ("<what> is for video contexts"; what = nullptr: the array ingest, whose
+// still-image contexts take fl == 1), slots [slot0, slot0 + n_out) inside max_frames, even_size: the 4:2:0 rule on the frame size --
+// and keeps the books of level 0's value range for `channels` weights, which is what lets the pyramid pass drop its clamps: an
+// ingest that did not come through here would leave them dropped on the strength of an earlier call's range.
+struct IngestBegin {
+    int W, H;              // the context's frame size
+    L0Addr out;            // level 0 at slot0
+    EotfDev e;             // the display block as the kernels take it (a table without a stated range: any value passes)
+    bool scalar, debug;    // FVVDP_TEMPORAL_SCALAR, FVVDP_DEBUG_VARIANT
+};
+int fvvdp_ctx_ingest_begin(fvvdp_ctx* c, const char* what, bool even_size, int channels, const fvvdp_eotf* eotf, const float* h_rgb2y,
+                           const float* h_taps, int fl, int n_out, int slot0, IngestBegin* b);
+
 // FL in {8, 16, 32}; dtype FVVDP_U8 / U16 / F32 / F16 / BF16.  FL = 64: see k1_ring64_ok().
 bool k1_launch_vec(int FL, int dtype, const TemporalArgs& a, hipStream_t st);     // aligned sizes (see the call site); true: blocks handed out by the ticket counter
 void k1_launch_ring(int FL, int dtype, const TemporalArgs& a, hipStream_t st);    // any size

@@ -1,6 +1,6 @@
 // Planar YUV clips of float32 code values (include/fvvdp_hip_yuv_grad.h): argument checks and launches of the kernels of
 // yuv_grad_kernels.hpp.  A translation unit of its own: it instantiates no kernel template of the other units, and the one
-// function that needs a context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_yuv_planes_begin).
+// function that needs a context asks fvvdp_hip.hip for the context's side of the call (fvvdp_ctx_ingest_begin).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cstddef>
@@ -11,17 +11,13 @@
 #include "fvvdp_hip_video_grad.h"
 #include "fvvdp_hip_yuv_grad.h"
 #include "device_common.hpp"
-#include "temporal_kernels.hpp"
+#include "temporal_launch.hpp"     // fvvdp_ctx_ingest_begin
 #include "grad_common.hpp"
 #include "yuv_grad_kernels.hpp"
 #include "grad_host.hpp"
 
 static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == YG_MAX_FL, "fvvdp_video_grad_luminance has the reach of fvvdp_video_grad_input");
 static_assert(FVVDP_YUV_GRAD_MAX_TAPS == 32, "YuvPlanesArgs::taps2");
-
-// fvvdp_hip.hip
-int fvvdp_ctx_yuv_planes_begin(fvvdp_ctx* c, int chroma_420, const fvvdp_eotf* eotf, const float* h_rgb2y, const float* h_taps,
-                               int fl, int n_out, int slot0, int* width, int* height, L0Addr* out);
 
 static int check_format(const fvvdp_yuv_format* fmt, int width, int height) {
     if (fmt->bit_depth < 8 || fmt->bit_depth > 16) return grad_fail(FVVDP_EINVAL, "bit depth %d not supported", fmt->bit_depth);
@@ -40,15 +36,7 @@ static int check_planes(const fvvdp_yuv_planes* p, const char* what, size_t HW, 
 }
 
 static void fill_unpack(YuvUnpack& k, int width, int height, const fvvdp_yuv_format* fmt, const fvvdp_eotf* eotf, const float* h_rgb2y) {
-    k.W = width;
-    k.H = height;
-    k.chroma420 = fmt->chroma_420 ? 1 : 0;
-    k.uvw = fmt->chroma_420 ? width / 2 : width;
-    k.uvh = fmt->chroma_420 ? height / 2 : height;
-    const float scale = (float)(1 << (fmt->bit_depth - 8));
-    k.wy = 1.0f / (scale * 219.0f);
-    k.wc = 1.0f / (scale * 224.0f);
-    for (int i = 0; i < 9; ++i) k.m[i] = fmt->ycbcr2rgb[i];
+    ingest_fill_unpack(k, width, height, fmt);
     grad_fill_eotf(k.e, k.w, eotf, 3, h_rgb2y);
 }
 
@@ -92,9 +80,9 @@ extern "C" int fvvdp_temporal_channels_yuv_planes(fvvdp_ctx* ctx, const fvvdp_yu
     // the plane pointers before the context is touched: its frame size is not known yet, so the strides follow below
     GRAD_CHECK(check_planes(test, "test", 0, 0));
     GRAD_CHECK(check_planes(ref, "reference", 0, 0));
-    int W = 0, H = 0;
-    L0Addr out;
-    GRAD_CHECK(fvvdp_ctx_yuv_planes_begin(ctx, fmt->chroma_420, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &W, &H, &out));
+    IngestBegin b;
+    GRAD_CHECK(fvvdp_ctx_ingest_begin(ctx, "YUV ingest", fmt->chroma_420 != 0, 3, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b));
+    const int W = b.W, H = b.H;
     const size_t HW = (size_t)W * H;
     const bool c420 = fmt->chroma_420 != 0;
     const size_t uv = c420 ? (size_t)(W / 2) * (H / 2) : HW;
@@ -102,30 +90,18 @@ extern "C" int fvvdp_temporal_channels_yuv_planes(fvvdp_ctx* ctx, const fvvdp_yu
     GRAD_CHECK(check_planes(ref, "reference", HW, uv));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : 32);
-    const int max_out = T_MAX_IDX - (FL - 1);
+    const int FL = ingest_ring_length(fl);
     const bool vec = FL <= 16 && W % 4 == 0 && planes_vector_ok(test, c420) && planes_vector_ok(ref, c420);
-    for (int t0 = 0; t0 < n_out; t0 += max_out) {
-        const int nn = (n_out - t0) < max_out ? (n_out - t0) : max_out;
+    for (const IngestWindow wnd : IngestWindows(fl, n_out)) {
         YuvPlanesArgs a;
         memset(&a, 0, sizeof(a));
         a.src[0] = plane_set(test);
         a.src[1] = plane_set(ref);
         fill_unpack(a.k, W, H, fmt, eotf, h_rgb2y);
-        a.n_out = nn;
-        a.fl = fl;
-        a.out = out;
-        a.out.slot0 = slot0 + t0;
+        a.out = b.out;
         a.oob = d_oob_flag;
-        for (int k = 0; k < fl; ++k) { a.taps2[k][0] = h_taps[k]; a.taps2[k][1] = h_taps[fl + k]; }
-        // virtual time of h_frame_idx: entry (fl - 1 + t) is the newest frame of output t; older history is padded (zero taps)
-        const int pad = FL - fl;
-        for (int u = 0; u < FL - 1 + nn; ++u) {
-            const int src = t0 + u - pad;
-            const int f = h_frame_idx[src < 0 ? 0 : src];
-            if (f < 0) return grad_fail(FVVDP_EINVAL, "frame index %d out of range", f);
-            a.idx[u] = f;
-        }
+        if (const int32_t* f = ingest_fill_window(a, wnd, slot0, h_taps, fl, h_frame_idx))
+            return grad_fail(FVVDP_EINVAL, "frame index %d out of range", *f);
         if (vec) {
             if (FL == 8) launch_vec<8>(c420, a, st);
             else launch_vec<16>(c420, a, st);

@@ -168,26 +168,37 @@ def forward_images(s, fix):
 
 class ClipSetup(_Setup):
     """A call on one [1, C, N, H, W] clip t (and reference r, as ImageSetup): also the taps (`taps`: others than the metric's
-    own at fps), the window list and the batch schedule of the forward."""
+    own at fps), the window list and the batch schedule of the forward.  The subclasses below bring sources of other kinds and
+    the ingest that takes them; taps, window list, schedule, launch and write_maps are the ones here."""
 
     def __init__(self, metric, t, fps, r=None, eotf=None, prm=None, pp=None, taps=None):
-        self.t, self.r = t, r
-        _, self.C, self.N, self.H, self.W = t.shape
-        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, own = metric._image_eotf(t.dtype)             # float32, float16 or bfloat16 (image_grad.float_pair)
+        self.t, self.r, self.C = t, r, t.shape[1]
+        # (samples: float32, float16 or bfloat16 -- image_grad.float_pair)
+        self._clip(metric, t.shape[2], t.shape[4], t.shape[3], fps, 4, t.dtype, eotf=eotf, prm=prm, pp=pp, taps=taps)
+
+    def _clip(self, metric, N, W, H, fps, planes, samples, eotf=None, w=None, prm=None, pp=None, taps=None):
+        """The constructor tail of every clip setup, for N frames of W x H at fps and samples of the torch dtype `samples`; eotf,
+        w (luminance weights), prm, pp, taps: overrides of the metric's own."""
+        self.N, self.W, self.H = N, W, H
+        self.n_bands, self.rho_band = metric._band_count(W, H)
+        self.dtype, own = metric._image_eotf(samples)
         self.e = own if eotf is None else eotf
-        self.w = metric._rgb2y()
+        self.w = metric._rgb2y() if w is None else w
         self.fl, own = metric._temporal_taps(fps)
         self.taps = own if taps is None else taps
-        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
-        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
-        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
-        self._finish(metric, 4, prm, pp)
+        self.widx = window_frame_indices(N, self.fl, metric.temp_padding)
+        self.batch = metric._batch_size(W, H, planes, N, self.fl)
+        self.schedule = [nb for _, nb in batches(N, self.batch)]
+        self._finish(metric, planes, prm, pp)
+
+    def window(self, b0, nb, widx=None):
+        """What output frames [b0, b0 + nb) read of the window list (widx: of another list laid out alike), contiguous."""
+        return np.ascontiguousarray((self.widx if widx is None else widx)[b0:b0 + self.fl - 1 + nb])
 
     def ingest(self, lib, t, r, b0, nb, oob):
         """Level 0 of slots [0, nb) for output frames [b0, b0 + nb): the launch _make_feeder's feed makes."""
         HW = self.H * self.W
-        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
+        idx = self.window(b0, nb)
         nat.check(lib.fvvdp_temporal_channels(self.ctx.handle, _ptr(t), _ptr(r), self.dtype, self.C, self.N * HW, HW,
                                               C.byref(self.e), nat.fptr(self.w), idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                               nat.fptr(self.taps), self.fl, nb, 0, _ptr(oob), self.stream))
@@ -232,8 +243,7 @@ class PlanClipSetup(ClipSetup):
         self._finish(metric, pl.planes, prm, pp)
 
     def ingest(self, lib, t, r, b0, nb, oob):
-        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
-        self.feeder(self.ctx, idx, self.taps, self.fl, nb, oob, self.stream)
+        self.feeder(self.ctx, self.window(b0, nb), self.taps, self.fl, nb, oob, self.stream)
 
 
 def yuv_planes(planes):
@@ -244,24 +254,15 @@ def yuv_planes(planes):
 
 class YuvClipSetup(ClipSetup):
     """ClipSetup for a clip of float32 YUV planes (yuv_grad.jod_video_yuv): t and r are (Y, U, V) tuples as yuv_planes takes them,
-    fmt the fvvdp_yuv_format, w the luminance weights of the YUV colour space; the ingest is fvvdp_temporal_channels_yuv_planes.
-    Taps, window list, schedule, launch and write_maps are ClipSetup's."""
+    fmt the fvvdp_yuv_format, w the luminance weights of the YUV colour space; the ingest is fvvdp_temporal_channels_yuv_planes."""
 
     def __init__(self, metric, t, fps, r, fmt, w, prm=None, pp=None):
-        self.t, self.r, self.fmt = t, r, fmt
-        self.C = 3
-        self.N, self.H, self.W = t[0].shape
-        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, self.e = metric._image_eotf(torch.float32)
-        self.w = w
-        self.fl, self.taps = metric._temporal_taps(fps)
-        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
-        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
-        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
-        self._finish(metric, 4, prm, pp)
+        self.t, self.r, self.fmt, self.C = t, r, fmt, 3
+        N, H, W = t[0].shape
+        self._clip(metric, N, W, H, fps, 4, torch.float32, w=w, prm=prm, pp=pp)
 
     def ingest(self, lib, t, r, b0, nb, oob):
-        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
+        idx = self.window(b0, nb)
         tp, rp = yuv_planes(t), yuv_planes(r)
         nat.check(lib.fvvdp_temporal_channels_yuv_planes(self.ctx.handle, C.byref(tp), C.byref(rp), C.byref(self.fmt),
                                                          C.byref(self.e), nat.fptr(self.w),
@@ -278,25 +279,15 @@ def resize_stream(x):
 class ResizedClipSetup(ClipSetup):
     """ClipSetup for a pair of clips with frame sizes of their own (resize_grad): t and r are [C, N, h, w] device tensors as
     resize_stream takes them, mode the FVVDP_RESIZE_* code, size the target (width, height) -- self.W and self.H, the size the
-    pyramid runs at; the ingest is fvvdp_temporal_channels_resized.  Taps, window list, schedule, launch and write_maps are
-    ClipSetup's."""
+    pyramid runs at; the ingest is fvvdp_temporal_channels_resized."""
 
     def __init__(self, metric, t, fps, r, mode, size, prm=None, pp=None):
-        self.t, self.r, self.mode = t, r, mode
-        self.C, self.N = t.shape[0], t.shape[1]
-        self.W, self.H = size
-        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, self.e = metric._image_eotf(torch.float32)
-        self.w = metric._rgb2y()
-        self.fl, self.taps = metric._temporal_taps(fps)
-        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
-        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
-        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
-        self._finish(metric, 4, prm, pp)
+        self.t, self.r, self.mode, self.C = t, r, mode, t.shape[0]
+        self._clip(metric, t.shape[1], size[0], size[1], fps, 4, torch.float32, prm=prm, pp=pp)
 
     def ingest(self, lib, t, r, b0, nb, oob):
         """(oob: the range flag of the other ingests stays as it is -- the clip to [0, 1] belongs to the resize)"""
-        idx = np.ascontiguousarray(self.widx[b0:b0 + self.fl - 1 + nb])
+        idx = self.window(b0, nb)
         ts, rs = resize_stream(t), resize_stream(r)
         nat.check(lib.fvvdp_temporal_channels_resized(self.ctx.handle, C.byref(ts), C.byref(rs), self.mode, C.byref(self.e),
                                                       nat.fptr(self.w), idx.ctypes.data_as(C.POINTER(C.c_int32)),
@@ -317,28 +308,18 @@ def held_strides(x):
 class HeldClipSetup(ClipSetup):
     """ClipSetup for a pair of clips with frame counts of their own (held.py): t and r are [1, C, F_s, H, W] device tensors as
     held_stream takes them, of one dtype; m_t and m_r the frame maps (int32 [N]: display frame -> source frame).  self.N is the
-    number of DISPLAY frames: taps, window list, schedule, gaze, launch and write_maps are ClipSetup's at the display's rate; the
-    ingest is fvvdp_temporal_channels_held on the window list sent through each stream's map."""
+    number of DISPLAY frames, at whose rate the window list, the schedule and the gaze run; the ingest is
+    fvvdp_temporal_channels_held on the window list sent through each stream's map."""
 
     def __init__(self, metric, t, fps, r, m_t, m_r, prm=None, pp=None):
-        self.t, self.r = t, r
+        self.t, self.r, self.C = t, r, t.shape[1]
         self.m_t, self.m_r = np.ascontiguousarray(m_t, dtype=np.int32), np.ascontiguousarray(m_r, dtype=np.int32)
-        _, self.C, _, self.H, self.W = t.shape
-        self.N = len(self.m_t)
-        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
-        self.dtype, self.e = metric._image_eotf(t.dtype)
-        self.w = metric._rgb2y()
-        self.fl, self.taps = metric._temporal_taps(fps)
-        self.widx = window_frame_indices(self.N, self.fl, metric.temp_padding)
+        self._clip(metric, len(self.m_t), t.shape[4], t.shape[3], fps, 4, t.dtype, prm=prm, pp=pp)
         self.idx_t, self.idx_r = self.m_t[self.widx], self.m_r[self.widx]      # the per-stream lists handed to the ingest
-        self.batch = metric._batch_size(self.W, self.H, 4, self.N, self.fl)
-        self.schedule = [nb for _, nb in batches(self.N, self.batch)]
-        self._finish(metric, 4, prm, pp)
 
     def ingest(self, lib, t, r, b0, nb, oob):
         i32p = C.POINTER(C.c_int32)
-        it = np.ascontiguousarray(self.idx_t[b0:b0 + self.fl - 1 + nb])
-        ir = np.ascontiguousarray(self.idx_r[b0:b0 + self.fl - 1 + nb])
+        it, ir = self.window(b0, nb, self.idx_t), self.window(b0, nb, self.idx_r)
         ts, rs = held_stream(t), held_stream(r)
         nat.check(lib.fvvdp_temporal_channels_held(self.ctx.handle, C.byref(ts), C.byref(rs), self.dtype, self.C, C.byref(self.e),
                                                    nat.fptr(self.w), it.ctypes.data_as(i32p), ir.ctypes.data_as(i32p),

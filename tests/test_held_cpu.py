@@ -45,7 +45,7 @@ def test_held_header_is_exported_and_bound():
     lib = nat.lib()
     for name in names:
         assert getattr(lib, name).argtypes is not None, name
-    assert not hasattr(L, "fvvdp_ctx_held_begin")                               # the context's side of the ingest stays internal
+    assert not hasattr(L, "fvvdp_ctx_ingest_begin")                               # the context's side of the ingest stays internal
     assert not any("held" in n for n in declared("fvvdp_hip.h"))                # nothing is added to fvvdp_hip.h
     txt = open(os.path.join(ROOT, "include", "fvvdp_hip_held.h")).read()
     assert int(re.search(r"#define FVVDP_HELD_MAX_TAPS (\d+)", txt).group(1)) == nat.HELD_MAX_TAPS == 32

@@ -43,7 +43,7 @@ def test_resize_header_is_exported_and_bound():
     lib = nat.lib()
     for name in names:
         assert getattr(lib, name).argtypes is not None, name
-    assert not hasattr(L, "fvvdp_ctx_resized_begin")                            # the context's side of the ingest stays internal
+    assert not hasattr(L, "fvvdp_ctx_ingest_begin")                            # the context's side of the ingest stays internal
     txt = open(os.path.join(ROOT, "include", "fvvdp_hip_resize.h")).read()
     assert int(re.search(r"#define FVVDP_RESIZE_MAX_TAPS (\d+)", txt).group(1)) == nat.RESIZE_MAX_TAPS
     assert ctypes.sizeof(nat.ResizeStream) == 40

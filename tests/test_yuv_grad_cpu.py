@@ -46,7 +46,7 @@ def test_yuv_grad_header_is_exported_and_bound():
     lib = nat.lib()
     for name in names:
         assert getattr(lib, name).argtypes is not None, name
-    assert not hasattr(L, "fvvdp_ctx_yuv_planes_begin")                         # the context's side of the ingest stays internal
+    assert not hasattr(L, "fvvdp_ctx_ingest_begin")                         # the context's side of the ingest stays internal
     txt = open(os.path.join(ROOT, "include", "fvvdp_hip_yuv_grad.h")).read()
     assert int(re.search(r"#define FVVDP_YUV_GRAD_MAX_TAPS (\d+)", txt).group(1)) == nat.YUV_GRAD_MAX_TAPS
     assert ctypes.sizeof(nat.YuvPlanes) == 40 and ctypes.sizeof(nat.YuvFormat) == 44      # fvvdp_yuv_format keeps its layout

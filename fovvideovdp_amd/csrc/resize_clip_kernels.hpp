@@ -9,11 +9,11 @@
 // Backward, once per clip, after video_lum_input_kernel (yuv_grad_kernels.hpp) has made gL:
 //   resize_adjoint_d_kernel       d_c[oy][ox] = gL w_c EOTF'(v_c) where v_c lies in [0, 1], 0 where the clip binds
 //   resize_adjoint_gather_kernel  grad[c][y][x] = sum_oy wy(oy -> y) sum_ox wx(ox -> x) d_c[oy][ox]
-// The index arithmetic of one axis (rz_*_axis) is host and device code: the tap setup of the forward, the weights of the gather
-// and the host's candidate ranges all call the same functions.
+// The index arithmetic of one axis (rz_*_axis, resize_axis.hpp) is host and device code: the tap setup of the forward, the weights
+// of the gather and the host's candidate ranges all call the same functions.
 #pragma once
 
-constexpr int RZ_IDENTITY = 4;          // beside FVVDP_RESIZE_NEAREST .. AREA: the stream has the target's size
+#include "resize_axis.hpp"
 
 struct RzStream {
     const void* p;
@@ -23,100 +23,6 @@ struct RzStream {
     size_t fs, ps;          // elements between frames, between the planes of a frame
     float sx, sy;           // W / Wo, H / Ho in fp32 (torch: area_pixel_compute_scale without a scale factor)
 };
-
-#define RZ_HD __host__ __device__ __forceinline__
-
-// torch's cubic convolution coefficients, A = -0.75 (cubic_coeffs of resize_kernels.hpp, callable from the host as well)
-RZ_HD void rz_cubic_coeffs(float t, float (&c)[4]) {
-    const float A = -0.75f;
-    const float x0 = t + 1.0f, x1 = t, x2 = 1.0f - t, x3 = 2.0f - t;
-    c[0] = ((A * x0 - 5.0f * A) * x0 + 8.0f * A) * x0 - 4.0f * A;
-    c[1] = ((A + 2.0f) * x1 - (A + 3.0f)) * x1 * x1 + 1.0f;
-    c[2] = ((A + 2.0f) * x2 - (A + 3.0f)) * x2 * x2 + 1.0f;
-    c[3] = ((A * x3 - 5.0f * A) * x3 + 8.0f * A) * x3 - 4.0f * A;
-}
-// nearest_neighbor_compute_source_index: min(floor(dst * scale), in - 1)
-RZ_HD int rz_nearest_axis(int o, int n, float scale) {
-    const int i = (int)floorf((float)o * scale);
-    return i < n - 1 ? i : n - 1;
-}
-// area_pixel_compute_source_index(cubic=false) and guard_index_and_lambda: lower index, upper index, weight of the upper one
-RZ_HD void rz_bilinear_axis(int o, int n, float scale, int& i0, int& i1, float& l1) {
-    const float f = fmaxf(scale * ((float)o + 0.5f) - 0.5f, 0.0f);
-    i0 = (int)f;
-    if (i0 > n - 1) i0 = n - 1;
-    i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    l1 = fminf(fmaxf(f - (float)i0, 0.0f), 1.0f);
-}
-// area_pixel_compute_source_index(cubic=true): the coordinate is not clamped, every tap's index is
-RZ_HD void rz_cubic_axis(int o, int n, float scale, int (&idx)[4], float (&c)[4]) {
-    const float r = scale * ((float)o + 0.5f) - 0.5f;
-    const float fl = floorf(r);
-    const int i = (int)fl;
-    rz_cubic_coeffs(r - fl, c);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = i - 1 + k;
-        idx[k] = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);
-    }
-}
-// adaptive average pooling: [floor(o * in / out), ceil((o + 1) * in / out))
-RZ_HD void rz_area_axis(int o, int n, int n_out, int& a0, int& a1) {
-    a0 = (int)floorf((float)(o * n) / (float)n_out);
-    a1 = (int)ceilf((float)((o + 1) * n) / (float)n_out);
-    // (products below 2^24 are exact and the last window ends at n; beyond that the float could round past the plane)
-    if (a1 > n) a1 = n;
-    if (a0 > n - 1) a0 = n - 1;
-}
-
-// the weight target sample o of one axis gives source sample `src` (0: o does not reach it); taps folded onto one index add up
-template <int MODE>
-RZ_HD float rz_axis_weight(int o, int src, int n, int n_out, float scale) {
-    if constexpr (MODE == FVVDP_RESIZE_NEAREST) {
-        return rz_nearest_axis(o, n, scale) == src ? 1.0f : 0.0f;
-    } else if constexpr (MODE == FVVDP_RESIZE_BILINEAR) {
-        int i0, i1;
-        float l1;
-        rz_bilinear_axis(o, n, scale, i0, i1, l1);
-        return (i0 == src ? 1.0f - l1 : 0.0f) + (i1 == src ? l1 : 0.0f);
-    } else if constexpr (MODE == FVVDP_RESIZE_BICUBIC) {
-        int idx[4];
-        float c[4];
-        rz_cubic_axis(o, n, scale, idx, c);
-        float w = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w += idx[k] == src ? c[k] : 0.0f;
-        return w;
-    } else if constexpr (MODE == FVVDP_RESIZE_AREA) {
-        int a0, a1;
-        rz_area_axis(o, n, n_out, a0, a1);
-        return (src >= a0 && src < a1) ? 1.0f / (float)(a1 - a0) : 0.0f;
-    } else {
-        return o == src ? 1.0f : 0.0f;
-    }
-}
-
-// the lowest and highest source index target sample o of one axis reads (host: the candidate ranges of the gather)
-template <int MODE>
-RZ_HD void rz_axis_reach(int o, int n, int n_out, float scale, int& lo, int& hi) {
-    if constexpr (MODE == FVVDP_RESIZE_NEAREST) {
-        lo = hi = rz_nearest_axis(o, n, scale);
-    } else if constexpr (MODE == FVVDP_RESIZE_BILINEAR) {
-        float l1;
-        rz_bilinear_axis(o, n, scale, lo, hi, l1);
-    } else if constexpr (MODE == FVVDP_RESIZE_BICUBIC) {
-        int idx[4];
-        float c[4];
-        rz_cubic_axis(o, n, scale, idx, c);
-        lo = idx[0];
-        hi = idx[3];
-    } else if constexpr (MODE == FVVDP_RESIZE_AREA) {
-        rz_area_axis(o, n, n_out, lo, hi);
-        hi -= 1;
-    } else {
-        lo = hi = o;
-    }
-}
 
 // ---- what a target pixel reads: computed once, before the loop over the frames -------------------------------------------------
 template <int MODE>

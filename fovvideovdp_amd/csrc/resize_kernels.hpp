@@ -11,6 +11,8 @@
 // L2 / memory-side cache between the two kernels; the luminance frame then takes the float temporal kernels.
 #pragma once
 
+#include "resize_axis.hpp"
+
 struct YuvRgbArgs {
     const void* src;         // one frame: Y plane, U plane, V plane
     int W, H, uvw, uvh, chroma420;
@@ -123,9 +125,10 @@ __global__ __launch_bounds__(256) void resize_lum_kernel(const ResizeArgs a) {
             v[c] = acc;
         }
     } else {
-        // 'area' = adaptive_avg_pool2d: start = floor(o * in / out), end = ceil((o + 1) * in / out)
-        const int y0 = (int)floorf((float)(oy * a.H) / (float)a.Ho), y1 = (int)ceilf((float)((oy + 1) * a.H) / (float)a.Ho);
-        const int x0 = (int)floorf((float)(ox * a.W) / (float)a.Wo), x1 = (int)ceilf((float)((ox + 1) * a.W) / (float)a.Wo);
+        // 'area' = adaptive_avg_pool2d: the windows of resize_axis.hpp, ATen's integer start and end
+        int y0, y1, x0, x1;
+        rz_area_axis(oy, a.H, a.Ho, y0, y1);
+        rz_area_axis(ox, a.W, a.Wo, x0, x1);
         const float n = (float)((y1 - y0) * (x1 - x0));
         float acc[3] = {0.0f, 0.0f, 0.0f};
         for (int yy = y0; yy < y1; ++yy)               // the three planes side by side: three loads in flight per step instead of one

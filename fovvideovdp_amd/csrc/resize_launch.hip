@@ -18,13 +18,23 @@
 #include "grad_host.hpp"
 
 static_assert(FVVDP_RESIZE_MAX_TAPS == 32, "ResizedArgs::taps2");
+static_assert(FVVDP_RESIZE_MAX_AXIS == RZ_MAX_AXIS, "resize_axis.hpp");
 
 static int check_mode(int mode) {
     if (mode < FVVDP_RESIZE_NEAREST || mode > FVVDP_RESIZE_AREA) return grad_fail(FVVDP_EINVAL, "unknown resize mode %d", mode);
     return FVVDP_OK;
 }
 
-// pointer set and aligned to its sample, a size of at least 1 x 1 whose offsets fit an int, strides that hold a plane
+// the sizes the index arithmetic of resize_axis.hpp is exact for, of a stream and of the target alike (fvvdp_yuv_frame_resized
+// refuses the same sizes in the same words)
+static int check_axes(int width, int height, const char* what) {
+    if (width > RZ_MAX_AXIS || height > RZ_MAX_AXIS)
+        return grad_fail(FVVDP_EINVAL, "frame size out of range (1..%d per axis): %dx%d (%s)", RZ_MAX_AXIS, width, height, what);
+    return FVVDP_OK;
+}
+
+// pointer set and aligned to its sample, a size between 1 x 1 and RZ_MAX_AXIS per axis (every offset inside a plane fits an int,
+// the rows of the gather fit its grid), strides that hold a plane
 static int check_stream(const fvvdp_resize_stream* s, const char* what, bool float_only) {
     if (!s->d_data) return grad_fail(FVVDP_EINVAL, "null data pointer (%s)", what);
     if (s->dtype != FVVDP_F32 && (float_only || s->dtype != FVVDP_U8))
@@ -33,8 +43,8 @@ static int check_stream(const fvvdp_resize_stream* s, const char* what, bool flo
         return grad_fail(FVVDP_EINVAL, "data pointer must be aligned to 4 bytes (%s)", what);
     if (s->channels != 1 && s->channels != 3) return grad_fail(FVVDP_EINVAL, "The content must have either 1 or 3 colour channels.");
     if (s->width < 1 || s->height < 1) return grad_fail(FVVDP_EINVAL, "bad frame size %dx%d (%s)", s->width, s->height, what);
+    GRAD_CHECK(check_axes(s->width, s->height, what));
     const size_t hw = (size_t)s->width * s->height;
-    if (hw > 0x7FFFFFFFu) return grad_fail(FVVDP_EINVAL, "frame of %zu samples is too large (%s)", hw, what);
     if (s->plane_stride < hw) return grad_fail(FVVDP_EINVAL, "plane_stride %zu is below the plane size %zu (%s)", s->plane_stride, hw, what);
     // (frames may lie inside a plane, [C][N][H][W], or planes inside a frame: either stride holds one plane at least)
     if (s->frame_stride < hw) return grad_fail(FVVDP_EINVAL, "frame_stride %zu is below the plane size %zu (%s)", s->frame_stride, hw, what);
@@ -95,6 +105,7 @@ extern "C" int fvvdp_temporal_channels_resized(fvvdp_ctx* ctx, const fvvdp_resiz
     IngestBegin b;
     GRAD_CHECK(fvvdp_ctx_ingest_begin(ctx, "the resizing ingest", false, test->channels, eotf, h_rgb2y, h_taps, fl, n_out, slot0, &b));
     const int W = b.W, H = b.H;
+    GRAD_CHECK(check_axes(W, H, "target"));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     const int FL = ingest_ring_length(fl);
@@ -150,13 +161,11 @@ extern "C" int fvvdp_resize_grad(int out_width, int out_height, int n_frames, co
     if (!d_gL || !test || !d_grad || !eotf || !h_rgb2y || !d_work) return grad_fail(FVVDP_EINVAL, "null argument");
     if (out_width < 1 || out_height < 1 || n_frames < 1)
         return grad_fail(FVVDP_EINVAL, "bad shape %dx%d, %d frames", out_width, out_height, n_frames);
+    GRAD_CHECK(check_axes(out_width, out_height, "target"));
     const size_t HWo = (size_t)out_width * out_height;
-    if (HWo > 0x7FFFFFFFu) return grad_fail(FVVDP_EINVAL, "frame of %zu pixels is too large", HWo);
     GRAD_CHECK(check_mode(mode));
     GRAD_CHECK(grad_check_closed_form(eotf));
     GRAD_CHECK(check_stream(test, "test", true));
-    // grid dimensions of the gather: rows / 4 and frames * channels
-    if (test->height > 65535 * 4) return grad_fail(FVVDP_EINVAL, "bad frame size %dx%d (test)", test->width, test->height);
     if ((reinterpret_cast<uintptr_t>(d_gL) | reinterpret_cast<uintptr_t>(d_grad)) % 4 != 0)
         return grad_fail(FVVDP_EINVAL, "d_gL and d_grad must be aligned to 4 bytes");
     if (reinterpret_cast<uintptr_t>(d_work) % 256 != 0) return grad_fail(FVVDP_EINVAL, "workspace must be 256-byte aligned");

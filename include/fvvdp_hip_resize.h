@@ -8,8 +8,10 @@
  * antialiasing; FVVDP_RESIZE_NEAREST / BILINEAR / BICUBIC / AREA of fvvdp_hip.h), a stream of the target's size is read as it is.
  * Per stream and target pixel: the samples of every channel are interpolated, clipped to [0, 1], sent through the display model
  * and weighted into luminance -- what the reference's file reader does under --full-screen-resize.  No clip at the target size is
- * ever stored.  The conventions of fvvdp_hip.h apply (d_* device and h_* host pointers, return codes, fvvdp_last_error, `stream`
- * a hipStream_t passed as void*, asynchronous).
+ * ever stored.  Widths and heights, of either stream and of the target, lie in 1 .. FVVDP_RESIZE_MAX_AXIS: the index arithmetic
+ * runs in 32 bits (the `area` windows are ATen's integer start and end indices, whose products of an index and a size must stay
+ * below 2^31); anything larger is refused with FVVDP_EINVAL.  The conventions of fvvdp_hip.h apply (d_* device and h_* host
+ * pointers, return codes, fvvdp_last_error, `stream` a hipStream_t passed as void*, asynchronous).
  *
  * The backward of a clip of N frames:
  *   per batch, as fvvdp_hip_video_grad.h: fvvdp_temporal_channels_resized, fvvdp_bands_forward with every band's maps,
@@ -31,6 +33,9 @@ extern "C" {
  * per second have 30.  Longer filters are REFUSED with FVVDP_EUNSUPPORTED and a sentence. */
 #define FVVDP_RESIZE_MAX_TAPS 32
 
+/* Largest width or height of a stream or of the target, as for fvvdp_yuv_frame_resized. */
+#define FVVDP_RESIZE_MAX_AXIS 32768
+
 /* One stream.  Sample (c, y, x) of frame f is element d_data[f * frame_stride + c * plane_stride + y * width + x] (strides in
  * elements; rows contiguous).  dtype: FVVDP_F32, or FVVDP_U8 (the value is code * (1/255)). */
 typedef struct fvvdp_resize_stream {
@@ -51,8 +56,9 @@ typedef struct fvvdp_resize_stream {
  * gather, the interpolation in torch's order of operations, the clip, the display model, the luminance weights and a push into
  * the register ring of the temporal filters.  The out-of-range flag of the context's other ingests does not exist here: the
  * clip belongs to the resize.
- * Errors: FVVDP_EINVAL (null or misaligned pointer, sample type, channel counts, a stream size below 1, strides below the frame,
- * slots, unknown mode, a display model without a closed form, a still-image context), FVVDP_EUNSUPPORTED (fl). */
+ * Errors: FVVDP_EINVAL (null or misaligned pointer, sample type, channel counts, a stream or target size outside
+ * 1 .. FVVDP_RESIZE_MAX_AXIS per axis, strides below the frame, slots, unknown mode, a display model without a closed form, a
+ * still-image context), FVVDP_EUNSUPPORTED (fl). */
 int fvvdp_temporal_channels_resized(fvvdp_ctx* ctx, const fvvdp_resize_stream* test, const fvvdp_resize_stream* ref, int mode,
                                     const fvvdp_eotf* eotf, const float* h_rgb2y, const int32_t* h_frame_idx, const float* h_taps,
                                     int fl, int n_out, int slot0, void* stream);
@@ -73,8 +79,8 @@ int fvvdp_temporal_channels_resized(fvvdp_ctx* ctx, const fvvdp_resize_stream* t
  *                               targets that can reach it; inside the range the device decides membership and weight with the
  *                               forward's own index function (taps that the index clamp folds onto one border sample add up).
  * A test of the target's size is the pointwise case of the same two stages.  d_work: 256-byte aligned.
- * Errors: FVVDP_EINVAL (null or misaligned pointer, bad shape, a test that is not float32, strides, unknown mode, display model,
- * a workspace below one frame). */
+ * Errors: FVVDP_EINVAL (null or misaligned pointer, bad shape, a size outside 1 .. FVVDP_RESIZE_MAX_AXIS per axis, a test that is
+ * not float32, strides, unknown mode, display model, a workspace below one frame). */
 int fvvdp_resize_grad(int out_width, int out_height, int n_frames, const float* d_gL, const fvvdp_resize_stream* test,
                       float* d_grad, int mode, const fvvdp_eotf* eotf, const float* h_rgb2y, void* d_work, size_t work_bytes,
                       void* stream);

@@ -315,8 +315,8 @@ def torch_interpolate(img, out_h, out_w, mode, dtype=_F):
             out = term if out is None else out + term
         return out.astype(F)
     if mode == "area":
-        def win(o, n_in, n_out):
-            return (int(np.floor(F(o * n_in) / F(n_out))), int(np.ceil(F((o + 1) * n_in) / F(n_out))))
+        def win(o, n_in, n_out):            # ATen's integers (AdaptiveAveragePooling.cpp: start_index, end_index), not a float quotient
+            return (o * n_in) // n_out, 1 + ((o + 1) * n_in - 1) // n_out
         out = np.empty((C, out_h, out_w), dtype=F)
         wy = [win(o, H, out_h) for o in range(out_h)]
         wx = [win(o, W, out_w) for o in range(out_w)]
@@ -327,10 +327,10 @@ def torch_interpolate(img, out_h, out_w, mode, dtype=_F):
     raise RuntimeError("Unknown resize method '%s'" % mode)
 
 
-def yuv_unpack(frame, W, H, bit_depth, chroma_ss, color_space, resize_fn=None, resize_hw=None, dtype=_F):
+def yuv_unpack(frame, W, H, bit_depth, chroma_ss, color_space, resize_fn=None, resize_hw=None, dtype=_F, clip=True):
     """video_reader_yuv_pytorch.unpack + _fixed2float_upscale, pyfvvdp/video_source_file.py:219-276.
     frame: 1-D uint8/uint16 (Y plane, U plane, V plane) -> RGB [H,W,3] fp32 in [0,1]; with resize_fn / resize_hw = (height, width):
-    resized in RGB before the clip (:238-244)."""
+    resized in RGB before the clip (:238-244).  clip=False: the RGB of :237-243 before that last clip (what a resize takes in)."""
     F = dtype
     ypx = W * H
     uvh, uvw = (H // 2, W // 2) if chroma_ss == "420" else (H, W)
@@ -360,6 +360,8 @@ def yuv_unpack(frame, W, H, bit_depth, chroma_ss, color_space, resize_fn=None, r
     RGB = (Yuv @ M.T).astype(F)                                                                       # :237
     if resize_fn is not None and tuple(resize_hw) != (H, W):                                           # :238-243
         RGB = torch_interpolate(RGB.transpose(2, 0, 1), resize_hw[0], resize_hw[1], resize_fn, F).transpose(1, 2, 0)
+    if not clip:
+        return RGB
     return np.clip(RGB, 0, 1).astype(F)                                                                # :244
 
 

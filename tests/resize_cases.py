@@ -39,6 +39,39 @@ def rotation():
     return out
 
 
+# Long axes: (n_in, n_out) of one axis whose products of an index and a size go beyond 2^24, where the floor and ceil of a float32
+# quotient leave ATen's integer `area` windows -- 5805 -> 2903: the last float32 window would end one sample past the plane; 4100 ->
+# 4099 and 7680 -> 4097: one window bound each.  The other axis is LONG_SHORT, so a frame stays at a few hundred kilobytes.
+LONG_AXES = [(5805, 2903), (4100, 4099), (7680, 4097)]
+LONG_SHORT = (6, 8)
+
+
+def long_cases():
+    """Cases of the form of rotation() at the long axes, each as the height and as the width: `area` on every pair, the other three
+    modes on two pairs each; the 30 fps ring.  Two cases resize both streams (a uint8 reference of the test's size).  The display
+    is sRGB throughout, the one model of DISPLAYS whose derivative is well conditioned over all of [0, 1]; the adjoint's bound is
+    4 x the error of ONE float32 evaluation, and with some 300 000 target values per case the other two models make that error a
+    matter of which value the evaluation order happens to hit:
+      PQ     the derivative jumps to 0 at the display's peak; a frame has a value whose float32 and float64 forms lie on either
+             side of it, and the float32 restatement is then off by 7.6 times the sum of a sample's absolute terms;
+      gamma  the derivative V^1.4 has the relative condition number 1.4 / V, in-range values come as close to 0 as the margin
+             lets them (1e-4), and an `area` mean of samples around 0.5 carries a rounding error of about 3e-8: the term moves by
+             up to 4e-4 of itself.  On the CPU the float32 derivatives of one frame's targets (7680 -> 4097) are off by 8.8e-6 with
+             the windows summed in one order and by 3.0e-5 in the other; on the GPU the adjoint was off by 2.5e-5 where the
+             restatement was by 4.4e-6.
+    The rotation keeps both models, at sizes that meet neither."""
+    plan = [("area", 0, "h"), ("area", 0, "w"), ("area", 1, "h"), ("area", 1, "w"), ("area", 2, "h"), ("area", 2, "w"),
+            ("nearest", 0, "h"), ("nearest", 2, "w"), ("bilinear", 1, "w"), ("bilinear", 0, "h"), ("bicubic", 2, "h"), ("bicubic", 1, "w")]
+    out = []
+    for k, (mode, pair, along) in enumerate(plan):
+        n_in, n_out = LONG_AXES[pair]
+        source = (LONG_SHORT[0], n_in) if along == "h" else (n_in, LONG_SHORT[0])
+        target = (LONG_SHORT[1], n_out) if along == "h" else (n_out, LONG_SHORT[1])
+        out.append(dict(mode=mode, fps=30, source=source, target=target, C=(3, 1)[k % 2], ref_dtype=("uint8", "float32")[(k // 2) % 2],
+                        ref_source=source if k in (1, 6) else None, display="standard_fhd", padding=PADDINGS[(k + 1) % 3]))
+    return out
+
+
 def case_id(c):
     return "%s-%dfps-%dx%d-to-%dx%d-C%d-%s-%s-ref-%s%s" % (c["mode"], c["fps"], *c["source"], *c["target"], c["C"], c["display"], c["padding"],
                                                            c["ref_dtype"], "" if c["ref_source"] is None else "-%dx%d" % c["ref_source"])
@@ -54,7 +87,6 @@ def draw_clip(seed, C, N, source, target, mode, dtype="float32"):
         x = rng.uniform(-0.25, 1.25, (C, N, h, w)).astype(np.float32)
     if tuple(source) == tuple(target):
         return x, 0
-    Sy, Sx = (rref.axis_support(n, o, mode).astype(np.float64) for n, o in ((h, target[1]), (w, target[0])))
     redrawn = 0
     frames = x.reshape(C * N, h, w)                      # (a view: the frames that still have such a sample are worked on alone)
     active = np.arange(C * N)
@@ -64,7 +96,7 @@ def draw_clip(seed, C, N, source, target, mode, dtype="float32"):
         active, bad = active[keep], bad[keep]
         if not len(active):
             return x, redrawn
-        hit = np.matmul(np.matmul(Sy.T, bad.astype(np.float64)), Sx) > 0
+        hit = rref.reaches(bad, source, mode)
         n = int(hit.sum())
         redrawn += n
         sub = frames[active]

@@ -4,13 +4,17 @@ of fvvdp_temporal_channels_resized and fvvdp_resize_grad (include/fvvdp_hip_resi
 Forward, per stream:  resize -> clip to [0, 1] -> display model -> luminance weights -> temporal channels.
 Adjoint, per frame:   d_c = gL w_c EOTF'(v_c) where the pre-clip value v_c lies in [0, 1], else 0;  grad_c = Ay^T d_c Ax.
 
-The resize is written as two dense matrices, one per axis (every mode of torch's interpolate without antialiasing is separable).
-Tap INDICES, window bounds and interpolation WEIGHTS come from float32 arithmetic exactly as ATen does it (UpSample.h:
+The resize is written as two matrices, one per axis (every mode of torch's interpolate without antialiasing is separable): dense
+ones at the small sizes, the same taps applied one by one where a dense matrix would be large (DENSE_MAX).  Tap INDICES and
+interpolation WEIGHTS of `nearest`, `bilinear` and `bicubic` come from float32 arithmetic exactly as ATen does it (UpSample.h:
 area_pixel_compute_scale / _source_index, nearest_neighbor_compute_source_index, guard_index_and_lambda, the cubic coefficients
-with A = -0.75; AdaptiveAveragePooling.cpp: start_index / end_index) -- in float64 `nearest` and `area` would pick other pixels
-than the kernel at some size pairs.  Only the sums run in `dtype`.  tests/test_resize_cpu.py pins the matrices against
-torch.nn.functional.interpolate and the adjoint against torch autograd."""
+with A = -0.75) -- in float64 `nearest` would pick other pixels than the kernel at some size pairs.  The windows of `area` are
+ATen's INTEGERS (AdaptiveAveragePooling.cpp: start_index = (o * in) / out, end_index = 1 + ((o + 1) * in - 1) / out): floor and
+ceil of a float32 quotient give the same windows only while o * in stays below 2^24.  Only the sums run in `dtype`.
+tests/test_resize_cpu.py pins the matrices against torch.nn.functional.interpolate, up to 32768 samples per axis, and the adjoint
+against torch autograd."""
 import copy
+import functools
 
 import numpy as np
 
@@ -20,6 +24,7 @@ from yuv_grad_ref import eotf_args, eotf_grad          # noqa: F401  (eotf_args:
 orc = yref.orc
 F32, F64 = np.float32, np.float64
 MODES = ("nearest", "bilinear", "bicubic", "area")
+DENSE_MAX = 1 << 20          # entries of a dense axis matrix; beyond, resize and its adjoint apply the taps one by one
 
 
 def _cubic(t):
@@ -29,9 +34,11 @@ def _cubic(t):
     return [cc2(t + F32(1)), cc1(t), cc1(F32(1) - t), cc2(F32(2) - t)]
 
 
+@functools.lru_cache(maxsize=64)
 def axis_taps(n_in, n_out, mode):
-    """[(source indices [n_out] int64, weights [n_out] float32)] of one axis: one entry per tap, indices and weights computed in
-    float32 as ATen computes them.  Equal sizes: the identity, whatever the mode (such a stream is not resampled)."""
+    """[(source indices [n_out] int64, weights [n_out] float32)] of one axis: one entry per tap, indices and weights computed as ATen
+    computes them (float32; the windows of `area` in integers).  Equal sizes: the identity, whatever the mode (such a stream is not
+    resampled).  The arrays are shared between the callers: read only."""
     o = np.arange(n_out, dtype=F32)
     if n_in == n_out:
         return [(np.arange(n_out, dtype=np.int64), np.ones(n_out, F32))]
@@ -51,8 +58,8 @@ def axis_taps(n_in, n_out, mode):
         return [(np.clip(fl.astype(np.int64) - 1 + k, 0, n_in - 1), c[k].astype(F32)) for k in range(4)]
     if mode == "area":
         oi = np.arange(n_out, dtype=np.int64)
-        a0 = np.floor((oi * n_in).astype(F32) / F32(n_out)).astype(np.int64)
-        a1 = np.ceil(((oi + 1) * n_in).astype(F32) / F32(n_out)).astype(np.int64)
+        a0 = (oi * n_in) // n_out
+        a1 = 1 + ((oi + 1) * n_in - 1) // n_out
         taps = []
         for k in range(int((a1 - a0).max())):
             inside = a0 + k < a1
@@ -85,10 +92,59 @@ def unit(x, dtype=F64):
     return x.astype(dtype) / dtype(255) if x.dtype == np.uint8 else x.astype(dtype)
 
 
+def _dense(h, w, size):
+    return h * size[1] <= DENSE_MAX and w * size[0] <= DENSE_MAX
+
+
+def axis_apply(x, axis, n_out, mode, dtype=F64, absolute=False, support=False):
+    """axis_matrix(...) applied along `axis` of x without building it: the sum over the taps, in their order.  support: axis_support
+    in the matrix's place (every sample a target reads counts once, whatever its weight)."""
+    xm = np.moveaxis(np.asarray(x, dtype=dtype), axis, 0)
+    out = np.zeros((n_out,) + xm.shape[1:], dtype=dtype)
+    seen = []
+    for idx, w in axis_taps(xm.shape[0], n_out, mode):
+        wt = (np.abs(w) if absolute else w).astype(dtype)
+        if support:
+            wt = (~np.any([idx == j for j in seen], axis=0) if seen else np.ones(n_out, bool)).astype(dtype)
+            seen.append(idx)
+        out += wt.reshape((-1,) + (1,) * (xm.ndim - 1)) * xm[idx]
+    return np.moveaxis(out, 0, axis)
+
+
+def axis_apply_T(d, axis, n_in, mode, dtype=F64, absolute=False):
+    """The transpose of axis_matrix(...) applied along `axis` of d [.., n_out, ..] -> [.., n_in, ..]."""
+    dm = np.moveaxis(np.asarray(d, dtype=dtype), axis, 0)
+    out = np.zeros((n_in,) + dm.shape[1:], dtype=dtype)
+    for idx, w in axis_taps(n_in, dm.shape[0], mode):
+        wt = (np.abs(w) if absolute else w).astype(dtype)
+        np.add.at(out, idx, wt.reshape((-1,) + (1,) * (dm.ndim - 1)) * dm)
+    return np.moveaxis(out, 0, axis)
+
+
+def reaches(bad, source, mode):
+    """bad: boolean [..., Ho, Wo] -> boolean [..., h, w]: the source samples some marked target sample reads (a tap with weight 0
+    still reads); source = (w, h)."""
+    w, h = source
+    Ho, Wo = bad.shape[-2:]
+    if _dense(h, w, (Wo, Ho)):
+        Sy, Sx = axis_support(h, Ho, mode).astype(np.float64), axis_support(w, Wo, mode).astype(np.float64)
+        return np.matmul(np.matmul(Sy.T, bad.astype(np.float64)), Sx) > 0
+    hit = np.asarray(bad, dtype=bool)
+    for axis, n_in, n_out in ((-2, h, Ho), (-1, w, Wo)):
+        dm = np.moveaxis(hit, axis, 0)
+        out = np.zeros((n_in,) + dm.shape[1:], dtype=bool)
+        for idx, _ in axis_taps(n_in, n_out, mode):
+            np.logical_or.at(out, idx, dm)
+        hit = np.moveaxis(out, 0, axis)
+    return hit
+
+
 def resize(x, size, mode, dtype=F64, absolute=False):
     """x [..., h, w] (values) -> [..., Ho, Wo] before the clip; size = (Wo, Ho)."""
     Wo, Ho = size
     h, w = x.shape[-2:]
+    if not _dense(h, w, size):
+        return axis_apply(axis_apply(x, -2, Ho, mode, dtype, absolute), -1, Wo, mode, dtype, absolute).astype(dtype)
     Ay, Ax = axis_matrix(h, Ho, mode, dtype, absolute), axis_matrix(w, Wo, mode, dtype, absolute)
     return np.matmul(np.matmul(Ay, np.asarray(x, dtype=dtype)), Ax.T).astype(dtype)
 
@@ -140,6 +196,8 @@ def clip_adjoint(G, frame, size, mode, dtype=F64, absolute=False):
     d = np.where((v >= 0) & (v <= 1), np.asarray(G, dtype=F), F(0)).astype(F)
     if absolute:
         d = np.abs(d)
+    if not _dense(h, w, size):
+        return axis_apply_T(axis_apply_T(d, -2, h, mode, F, absolute), -1, w, mode, F, absolute).astype(F)
     Ay, Ax = axis_matrix(h, Ho, mode, F, absolute), axis_matrix(w, Wo, mode, F, absolute)
     return np.matmul(np.matmul(Ay.T, d), Ax).astype(F)
 

@@ -833,6 +833,92 @@ def test_yuv_full_screen_resize_random_sizes_vs_oracle(fv):
         assert abs(float(q) - float(oq)) < 2e-4, (k, fn, float(q), float(oq))
 
 
+# (mode, bit depth, long axis (n_in, n_out), long axis is the height): `area` on the three pairs of resize_cases.LONG_AXES in both
+# orientations, each other mode on one of them
+YUV_LONG = [("area", 8, (5805, 2903), True), ("area", 10, (5805, 2903), False), ("area", 10, (4100, 4099), True),
+            ("area", 8, (4100, 4099), False), ("area", 8, (7680, 4097), True), ("area", 10, (7680, 4097), False),
+            ("nearest", 10, (5805, 2903), False), ("bilinear", 8, (7680, 4097), True), ("bicubic", 10, (4100, 4099), False)]
+
+
+@pytest.mark.parametrize("fn,bd,axis,tall", YUV_LONG, ids=["%s-%dbit-%dto%d-%s" % (c[0], c[1], *c[2], "h" if c[3] else "w") for c in YUV_LONG])
+def test_yuv_full_screen_resize_long_axes(fv, fn, bd, axis, tall):
+    """`fvvdp_yuv_frame_resized` on skinny 4:4:4 frames (the other axis 6 -> 8) whose long axis takes an index times a size beyond
+    2^24: there the floor and ceil of a float32 quotient leave ATen's integer `area` windows, and at 5805 -> 2903 the last such window
+    ends one row (or column) past the plane.  Clipped RGB against the oracle's unpack within the 4e-6 of
+    test_yuv_full_screen_resize_random_sizes_vs_oracle, for `area` and `nearest` against torch's own interpolate of the oracle's
+    unclipped RGB as well; luminance within the 6e-5 of the g17 test.  The scratch buffer holds exactly 3 W H floats and NaN lies
+    behind it and behind the outputs: nothing non-finite comes out, nothing outside is written.
+
+    bilinear and bicubic: the kernel's unit is built with contraction, as torch's own builds are, so the coordinate
+    scale * (o + 0.5) - 0.5 is ONE fused multiply-subtract where the oracle's numpy rounds the product first.  The two are equal
+    except at the few targets whose product lies in [2^k, 2^k + 0.5) (the difference falls into the binade below and keeps bits the
+    rounded product lost); there they differ by eps(o), computed exactly below, and the interpolant -- slope at most 2 max|x|
+    (bilinear) or 4.2 max|x| (the cubic's coefficient derivatives add up to at most 4.2) -- by at most 6 eps max|x|, which the
+    bound of such a row or column gains.  7680 -> 4097: eps = 7.6e-6 at row 68 and 4.8e-7 at row 4, 0 elsewhere; measured
+    against the oracle 7.58e-6 at row 68 (torch on the CPU, which fuses too, is 1.8e-7 from the fused form)."""
+    import ctypes as C
+    import sys
+    from fovvideovdp_amd import _native as nat
+    from fovvideovdp_amd.display_model import native_eotf
+    from oracle import fvvdp_oracle as orc
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import yuv_channels_ref as yref
+    (H, Ho), (W, Wo) = (axis, (6, 8)) if tall else ((6, 8), axis)
+    frame = yref.yuv_clip(1, H, W, bd, "444", [bd, H, W])[1][0]               # every code, both clamps and the clip bind
+    m = fv.fvvdp(display_name="standard_fhd")
+    vs = fv.fvvdp_video_source_yuv_frames(frame[None], frame[None], 30, W, H, bit_depth=bd, chroma_ss="444",
+                                          display_photometry=m.display_photometry, full_screen_resize=fn, resize_resolution=(Wo, Ho))
+    desc = native_eotf(vs.dm_photometry)
+    dev = torch.device("cuda")
+    n_ws, n_out, guard = 3 * W * H, Ho * Wo, 4 * max(W, Wo) + 64
+    arena = torch.full((n_ws + guard + 4 * n_out + guard,), float("nan"), dtype=torch.float32, device=dev)
+    ws, g0 = arena[:n_ws], arena[n_ws:n_ws + guard]
+    lum, rgb, g1 = arena[n_ws + guard:][:n_out], arena[n_ws + guard + n_out:][:3 * n_out], arena[n_ws + guard + 4 * n_out:]
+    x = vs.test_yuv[0].to(dev)
+    fmt = nat.YuvFormat()
+    fmt.bit_depth, fmt.chroma_420 = bd, 0
+    for i, v in enumerate(np.asarray(vs.ycbcr2rgb, dtype=np.float32).reshape(-1)):
+        fmt.ycbcr2rgb[i] = float(v)
+    e = nat.Eotf()
+    e.kind, e.Y_peak, e.Y_black, e.gamma = desc[0], desc[1].get("Y_peak", 0.0), desc[1].get("Y_black", 0.0), desc[1].get("gamma", 1.0)
+    e.L_min, e.L_max = desc[1].get("L_min", 0.0), desc[1].get("L_max", 0.0)
+    w = np.ascontiguousarray(np.asarray(vs.color_to_luminance, dtype=np.float32))
+    nat.check(nat.lib().fvvdp_yuv_frame_resized(C.c_void_p(x.data_ptr()), C.byref(fmt), W, H, C.c_void_p(ws.data_ptr()), Wo, Ho,
+                                                nat.RESIZE_MODES[fn], C.byref(e), nat.fptr(w), C.c_void_p(lum.data_ptr()),
+                                                C.c_void_p(rgb.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(g0).all()) and bool(torch.isnan(g1).all())          # nothing outside the buffers was written
+    assert bool(torch.isfinite(ws).all()) and bool(torch.isfinite(lum).all()) and bool(torch.isfinite(rgb).all())
+    got = rgb.reshape(3, Ho, Wo).permute(1, 2, 0).cpu().numpy()
+    o_rgb = orc.yuv_unpack(frame, W, H, bd, "444", "bt709", fn, (Ho, Wo))
+    d = float(np.max(np.abs(got - o_rgb)))
+    assert (o_rgb == 0).any() and (o_rgb == 1).any()
+    line = "%s %d bit %dx%d -> %dx%d: RGB against the oracle %.3g" % (fn, bd, W, H, Wo, Ho, d)
+    raw = orc.yuv_unpack(frame, W, H, bd, "444", "bt709", clip=False)
+    tol = np.full((Ho, Wo, 1), 4e-6)
+    if fn in ("bilinear", "bicubic"):
+        def fused_gap(n_in, n_out):
+            p = np.float64(np.float32(n_in) / np.float32(n_out)) * (np.arange(n_out, dtype=np.float64) + 0.5)     # exact in float64
+            return np.abs((p - 0.5).astype(np.float32).astype(np.float64) - (p.astype(np.float32) - np.float32(0.5)))
+        eps = fused_gap(H, Ho)[:, None, None] + fused_gap(W, Wo)[None, :, None]
+        assert (eps > 0).mean() < 0.01 and eps.max() <= 2.0 ** -24 * max(H, W)
+        tol = tol + 6.0 * eps * float(np.abs(raw).max())
+        line += " (%.3g where the fused coordinate is the rounded one)" % float(np.max(np.abs(got - o_rgb)[(eps == 0)[:, :, 0]]))
+    assert (np.abs(got - o_rgb) < tol).all(), line
+    if fn in ("area", "nearest"):
+        t_rgb = torch.nn.functional.interpolate(torch.from_numpy(raw).permute(2, 0, 1)[None], size=(Ho, Wo), mode=fn)[0].clip(0, 1)
+        dt = float(np.max(np.abs(got - t_rgb.permute(1, 2, 0).numpy())))
+        line += ", against torch %.3g" % dt
+        assert dt < 4e-6, line
+    ph = orc.Photometry.load("standard_fhd", dtype=np.float32)
+    L, _ = ph.forward(o_rgb.transpose(2, 0, 1)[None, :, None])
+    k = orc.load_defaults()["color_spaces.json"]["sRGB"]["RGB2Y"]
+    o_lum = (L[:, 0:1] * np.float32(k[0]) + L[:, 1:2] * np.float32(k[1]) + L[:, 2:3] * np.float32(k[2]))[0, 0, 0]
+    d_lum = float(np.max(np.abs(lum.reshape(Ho, Wo).cpu().numpy() - o_lum) / np.maximum(np.abs(o_lum), 1e-2)))
+    print("\n" + line + ", luminance %.3g" % d_lum)
+    assert d_lum < 6e-5, d_lum
+
+
 def test_yuv_full_screen_resize_argument_checks(fv):
     from fovvideovdp_amd.synth import synth_yuv_pair
     ty, ry = synth_yuv_pair(2, 36, 64)

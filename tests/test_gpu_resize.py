@@ -7,7 +7,9 @@ fvvdp.jod_video_resized).
      bound relative to the sum of the absolute terms of every output sample, exact zeros, a NaN-filled output;
   3. end to end, forward: predict_resized against predict on the clip torch resized on the host;
   4. end to end, gradient: against the g25 goldens of the reference's autograd;
-  5. exactness and invariance.
+  5. exactness and invariance;
+  6. long axes (resize_cases.long_cases): 1. - 3. where a product of an index and a size goes beyond 2^24 and the `area` windows are
+     ATen's integers and no longer the floor and ceil of a float32 quotient.
 """
 import ctypes as C
 import os
@@ -31,6 +33,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 I32P = C.POINTER(C.c_int32)
 ROTATION = [pytest.param(c, id=rc.case_id(c)) for c in rc.rotation()]
+LONG = [pytest.param(c, id=rc.case_id(c)) for c in rc.long_cases()]
 
 
 def product_photometry(model):
@@ -75,6 +78,10 @@ def test_rotation_covers_the_matrix():
 
 @pytest.mark.parametrize("c", ROTATION)
 def test_ingest_per_pixel(c):
+    check_ingest_per_pixel(c)
+
+
+def check_ingest_per_pixel(c):
     m = fv.fvvdp(temp_padding=c["padding"], quiet=True, device=DEV, **product_photometry(c["display"]))
     fl, taps = m._temporal_taps(c["fps"])
     assert (8 if fl <= 8 else 16 if fl <= 16 else 32) == rc.RING[c["fps"]]
@@ -106,6 +113,15 @@ def test_ingest_per_pixel(c):
 # ---- 2. the adjoint alone ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("c", ROTATION)
 def test_adjoint_per_sample(c):
+    zero, _ = check_adjoint_per_sample(c)
+    if c["mode"] in ("nearest", "area") and c["source"] != (7, 5):
+        assert zero.any()                         # a clipped sample reaches few targets, all of them clipped (wider kernels mix it
+        #                                           with in-range neighbours: a sample with nothing but clipped targets is rare there)
+    if c["source"] == (240, 136) and c["mode"] == "nearest":
+        assert zero.mean() > 0.5                  # x0.5: three of four samples are skipped, and come back as written zeros
+
+
+def check_adjoint_per_sample(c):
     """Bound, per source sample and relative to the sum of the absolute values of its terms as the float64 reference gives it:
     4 x max(the same error of the float32 restatement, 4 x 2^-24) -- yuv_channels_ref.error_bound's construction.  The workspace
     holds two frames of the first stage, so three frames take two batches."""
@@ -143,17 +159,13 @@ def test_adjoint_per_sample(c):
     assert np.isfinite(got).all()                                                 # every sample was written (the buffer held NaN)
     zero = S == 0                                 # every target that reaches the sample is clipped, or a downscale skips it
     assert (got[zero] == 0).all() and (g64[zero] == 0).all()
-    if c["mode"] in ("nearest", "area") and c["source"] != (7, 5):
-        assert zero.any()                         # a clipped sample reaches few targets, all of them clipped (wider kernels mix it
-        #                                           with in-range neighbours: a sample with nothing but clipped targets is rare there)
-    if c["source"] == (240, 136) and c["mode"] == "nearest":
-        assert zero.mean() > 0.5                  # x0.5: three of four samples are skipped, and come back as written zeros
     e_ref = float((np.abs(g32.astype(np.float64) - g64)[~zero] / S[~zero]).max())
     err = float((np.abs(got.astype(np.float64) - g64)[~zero] / S[~zero]).max())
     bound = yref.error_bound(e_ref)
     print("\nresize adjoint %s: err %.3g e_ref %.3g bound %.3g, %d exact zeros of %d" % (rc.case_id(c), err, e_ref, bound, int(zero.sum()),
                                                                                         zero.size))
     assert err <= bound
+    return zero, e_ref
 
 
 # ---- 3. / 4. end to end ----------------------------------------------------------------------------------------------------------------
@@ -311,3 +323,50 @@ def test_grad_batch_placement_and_layout_give_equal_bits():
     (g2,) = torch.autograd.grad(case_call(m, name, t2, r), t2, create_graph=True)
     with pytest.raises(RuntimeError, match="once_differentiable|does not require grad"):
         g2.sum().backward()
+
+
+# ---- 6. long axes -----------------------------------------------------------------------------------------------------------------------
+def test_long_cases_cover_the_matrix():
+    L = rc.long_cases()
+    for along in (0, 1):                          # as the width, as the height
+        assert {(c["source"][along], c["target"][along]) for c in L if c["mode"] == "area" and c["source"][along] > 8} == set(rc.LONG_AXES)
+        assert {c["mode"] for c in L if c["source"][along] > 8} == set(rref.MODES)
+    assert all(min(c["source"]) == rc.LONG_SHORT[0] and min(c["target"]) == rc.LONG_SHORT[1] and c["fps"] == 30 for c in L)
+    assert all((o + 1) * n > 2 ** 24 for n, o in rc.LONG_AXES)
+    assert {c["C"] for c in L} == {1, 3} and {c["ref_dtype"] for c in L} == {"float32", "uint8"}
+    assert {c["display"] for c in L} == {"standard_fhd"} and {c["padding"] for c in L} == set(rc.PADDINGS)
+    assert any(c["ref_source"] is not None for c in L) and len({rc.case_id(c) for c in L}) == len(L)
+
+
+@pytest.mark.parametrize("c", LONG)
+def test_ingest_per_pixel_long_axes(c):
+    """test_ingest_per_pixel, its reference and its bound, on skinny frames with one long axis."""
+    check_ingest_per_pixel(c)
+
+
+@pytest.mark.parametrize("c", LONG)
+def test_adjoint_per_sample_long_axes(c):
+    """test_adjoint_per_sample, its reference and its bound, on skinny frames with one long axis: the host's candidate ranges and the
+    gather's weights at long axes.  A downscale by `nearest` skips every other sample of the long axis: written zeros."""
+    zero, e_ref = check_adjoint_per_sample(c)
+    assert e_ref <= 1e-4                          # the bound is float32 rounding, no decision that float32 and float64 take apart
+    if c["mode"] == "nearest":
+        assert zero.mean() > 0.4
+
+
+def test_value_against_predict_on_the_resized_clip_long_axis():
+    """predict_resized with `area` at 7680 x 6 -> 4097 x 8 against predict on the clip torch resized on the host."""
+    source, target, N = (7680, 6), (4097, 8), 6
+    test, _ = rc.draw_clip([61], 3, N, source, target, "area")
+    m = fv.fvvdp(display_name="standard_fhd", quiet=True, device=DEV)
+    t = torch.from_numpy(test)
+    resized = torch.nn.functional.interpolate(t.permute(1, 0, 2, 3), size=(target[1], target[0]), mode="area").clip(0, 1).permute(1, 0, 2, 3)
+    rng = np.random.default_rng(62)
+    r = (resized + torch.from_numpy(rng.normal(0, 0.05, resized.shape).astype(np.float32))).clip(0, 1).contiguous()
+    want, wstats = m.predict(resized.contiguous(), r, dim_order="CFHW", frames_per_second=30)
+    got, stats = m.predict_resized(t, r, full_screen_resize="area", resize_resolution=target, frames_per_second=30, dim_order="CFHW")
+    d = abs(float(got) - float(want))
+    print("\narea %dx%d -> %dx%d: predict on the resized clip %.7f predict_resized %.7f difference %.3g" % (*source, *target, float(want),
+                                                                                                          float(got), d))
+    assert 0 < float(want) < 10 and d <= PARITY_TOL
+    assert stats["Q_per_ch"].shape == wstats["Q_per_ch"].shape and (stats["width"], stats["height"]) == target

@@ -24,6 +24,12 @@ WEIGHT_ULPS = 4              # see test_axis_matrices_are_torchs
 NEW_KERNELS = ["void resized_ring_kernel<%d, %d, %d>" % (fl, 2 if fl <= 16 and m <= 1 else 1, m) for fl in (8, 16, 32) for m in range(4)] + \
     ["void resize_adjoint_d_kernel<%d>" % m for m in range(5)] + ["void resize_adjoint_gather_kernel<%d>" % m for m in range(5)]
 PAIRS = [(s, t) for s in rc.SOURCES for t in rc.TARGETS]
+# One axis (n_in, n_out), both directions: index times size goes beyond 2^24, where the floor and ceil of a float32 quotient leave
+# ATen's integer `area` windows (at 5805 -> 2903 the last float32 window would end at n_in + 1), up to the largest size the entry
+# points take
+LARGE_AXES = [p for a, b in ((4100, 4099), (4320, 4319), (7680, 4097), (5805, 2903), (8192, 8191), (32768, 30000), (32768, 32767))
+              for p in ((a, b), (b, a))]
+COMB = 16                    # see comb_matrix: above twice the widest support of LARGE_AXES (four taps; `area` windows of at most 3)
 
 
 def declared(header):
@@ -92,6 +98,16 @@ def test_argument_checks_need_no_device():
     assert adj(work=1025) == -1 and b"256-byte aligned" in lib.fvvdp_last_error()
     one = nat.resize_grad_table_bytes(60, 34) + 4 * 3 * Wo * Ho
     assert adj(bytes_=one - 1) == -1 and b"needed for one frame" in lib.fvvdp_last_error()
+    # 1 .. 32768 per axis, stream and target alike, in the words of fvvdp_yuv_frame_resized: the index arithmetic runs in 32 bits
+    out_of_range = b"frame size out of range (1..32768 per axis)"
+    assert adj(t=stream(width=32769, height=1)) == -1 and out_of_range + b": 32769x1 (test)" in lib.fvvdp_last_error()
+    assert adj(t=stream(width=1, height=32769)) == -1 and out_of_range + b": 1x32769 (test)" in lib.fvvdp_last_error()
+    assert adj(t=stream(width=65536, height=32768)) == -1 and out_of_range in lib.fvvdp_last_error()
+    assert adj(width=32769) == -1 and out_of_range + b": 32769x68 (target)" in lib.fvvdp_last_error()
+    assert adj(height=1 << 30) == -1 and out_of_range in lib.fvvdp_last_error()
+    # the largest sizes pass this check: the call is refused by a later one
+    assert adj(t=stream(width=32768, height=2), bytes_=1) == -1 and b"needed for one frame" in lib.fvvdp_last_error()
+    assert adj(width=32768, height=32768, bytes_=1) == -1 and b"needed for one frame" in lib.fvvdp_last_error()
 
     # the ingest: everything that is checked before the context is looked at (a context needs a device)
     taps = np.ones((2, 40), np.float32)
@@ -113,6 +129,9 @@ def test_argument_checks_need_no_device():
     assert ing(r=stream(data=258)) == -1 and b"aligned to 4 bytes (reference)" in lib.fvvdp_last_error()
     assert ing(r=stream(C=1)) == -1 and b"differ in their channel counts (3 and 1)" in lib.fvvdp_last_error()
     assert ing(t=stream(height=-3)) == -1 and b"bad frame size" in lib.fvvdp_last_error()
+    assert ing(t=stream(width=1, height=32769)) == -1 and out_of_range + b": 1x32769 (test)" in lib.fvvdp_last_error()
+    assert ing(r=stream(dtype=nat.FVVDP_U8, width=40000, height=2)) == -1 and out_of_range + b": 40000x2 (reference)" in lib.fvvdp_last_error()
+    assert ing(t=stream(width=32768, height=2), r=stream(C=1)) == -1 and b"channel counts" in lib.fvvdp_last_error()
 
 
 def test_refusals_without_device():
@@ -212,6 +231,88 @@ def test_axis_matrices_are_torchs(mode):
             assert (A >= 0).all()
         # every mode reproduces a constant (a cubic coefficient has intermediates of up to 8 |A| = 6 and four roundings)
         assert np.abs(A.sum(axis=1) - 1).max() <= (4 * 4 * 6 if mode == "bicubic" else 8) * U24
+
+
+def comb_matrix(n_in, n_out, mode, along):
+    """torch's one-axis matrix [n_out, n_in] of a long axis, folded: torch resizes COMB combs -- comb k has a one at every index that
+    is k modulo COMB -- along axis `along` (-2: rows, -1: columns) while the other axis keeps its size.  A target's taps span fewer
+    than COMB samples, so entry [o, k] is the weight torch gives the one sample of o's support that is k modulo COMB."""
+    comb = (np.arange(n_in)[:, None] % COMB == np.arange(COMB)[None]).astype(np.float32)
+    if along == -2:
+        return _interp(torch.from_numpy(comb)[None, None], (COMB, n_out), mode)[0, 0].numpy()
+    return _interp(torch.from_numpy(comb.T.copy())[None, None], (n_out, COMB), mode)[0, 0].numpy().T
+
+
+@pytest.mark.parametrize("mode", rref.MODES)
+def test_axis_matrices_are_torchs_at_long_axes(mode):
+    """test_axis_matrices_are_torchs for LARGE_AXES, from the per-tap index arrays of axis_taps folded as comb_matrix folds torch's
+    (a dense 30000 x 32768 matrix is out of reach).  The same assertions: equal supports in every mode; `nearest` and `area` bit for
+    bit; the weights of the other two within WEIGHT_ULPS 2^-24 n_in, the bound derived there from the fused multiply-subtract of
+    torch's coordinate (not from any kernel).  Measured against torch on the CPU, largest at 5805 -> 2903: bilinear 2.4e-4, bicubic
+    3.0e-4 (bound 1.4e-3) -- half a unit in the last place of a coordinate above 4096; at 32768 -> 30000 8.6e-6 (bound 7.8e-3)."""
+    worst = {}
+    for n_in, n_out in LARGE_AXES:
+        taps = rref.axis_taps(n_in, n_out, mode)
+        every = np.stack([idx for idx, _ in taps])
+        assert int((every.max(axis=0) - every.min(axis=0)).max()) < COMB // 2
+        rows = np.arange(n_out)
+        A = np.zeros((n_out, COMB), np.float32)
+        S = np.zeros((n_out, COMB), bool)
+        for idx, w in taps:
+            assert idx.min() >= 0 and idx.max() <= n_in - 1
+            np.add.at(A, (rows, idx % COMB), w)
+            S[rows, idx % COMB] = True
+        for along in (-2, -1):
+            want = comb_matrix(n_in, n_out, mode, along)
+            if mode in ("nearest", "area"):
+                assert np.array_equal(A, want) and np.array_equal(A != 0, S), (mode, n_in, n_out, along)
+            assert not ((want != 0) & ~S).any() and not ((A != 0) & ~S).any(), (mode, n_in, n_out, along)
+            d = float(np.abs(A - want).max())
+            worst[(n_in, n_out)] = max(worst.get((n_in, n_out), 0.0), d)
+            assert d <= WEIGHT_ULPS * U24 * n_in, (mode, n_in, n_out, along, d)
+        if mode != "bicubic":
+            assert (A >= 0).all()
+        assert np.abs(A.astype(np.float64).sum(axis=1) - 1).max() <= (4 * 4 * 6 if mode == "bicubic" else 8) * U24
+    print("\n%s: max |weight - torch's| per pair %s" % (mode, {k: "%.3g" % v for k, v in worst.items()}))
+
+
+@pytest.mark.parametrize("mode", rref.MODES)
+def test_resize_is_torchs_interpolate_at_long_axes(mode):
+    """test_resize_is_torchs_interpolate with LARGE_AXES as the height and as the width of skinny images (the other axis 3 -> 5), and
+    its bound.  At 32768 -> 30000 the float32 windows of `area` differ from torch by 0.28 on 16 rows of such an image."""
+    rng = np.random.default_rng(11)
+    for n_in, n_out in LARGE_AXES:
+        for source, target in (((3, n_in), (5, n_out)), ((n_in, 3), (n_out, 5))):
+            x = rng.uniform(-0.25, 1.25, (3, 1, source[1], source[0])).astype(np.float32)
+            want = _interp(torch.from_numpy(x).permute(1, 0, 2, 3), target, mode).permute(1, 0, 2, 3).numpy()
+            got = rref.resize(x.astype(np.float64), target, mode)
+            scale = rref.resize(np.abs(x).astype(np.float64), target, mode, absolute=True)
+            # the largest number of samples a target reads and the sum of |x| over them, per axis as axis_support has them
+            T = int(rref.axis_apply(np.ones(source[1]), 0, target[1], mode, support=True).max()) * \
+                int(rref.axis_apply(np.ones(source[0]), 0, target[0], mode, support=True).max())
+            taps = rref.axis_apply(rref.axis_apply(np.abs(x), -2, target[1], mode, support=True), -1, target[0], mode, support=True)
+            assert want.shape == got.shape
+            d = np.abs(got - want)
+            assert (d <= (T + 4) * U24 * scale + WEIGHT_ULPS * U24 * sum(source) * taps).all(), (mode, source, target, float(d.max()))
+            assert (np.abs(rref.resize(x, target, mode, np.float32) - got) <= (T + 4) * U24 * scale).all()
+
+
+@pytest.mark.parametrize("n_in,n_out", [(5805, 2903), (7680, 4097)])
+def test_oracle_area_is_torchs_at_long_axes(n_in, n_out):
+    """oracle.torch_interpolate(mode="area"), the yardstick of fvvdp_yuv_frame_resized, against torch itself on skinny frames whose
+    long axis takes index times size beyond 2^24, in both orientations.  The same windows, so the two differ by the order of their
+    float32 sums alone: within the 8e-6 the g17 tests of the resize give `area` (measured: 0 -- both add a window of at most six samples row by row)."""
+    orc = rref.orc
+    rng = np.random.default_rng(n_in)
+    worst = 0.0
+    for h, w, Ho, Wo in ((n_in, 6, n_out, 8), (6, n_in, 8, n_out)):
+        x = rng.uniform(-0.25, 1.25, (3, h, w)).astype(np.float32)
+        want = torch.nn.functional.interpolate(torch.from_numpy(x)[None], size=(Ho, Wo), mode="area")[0].numpy()
+        got = orc.torch_interpolate(x, Ho, Wo, "area")
+        assert got.shape == want.shape and got.dtype == np.float32
+        worst = max(worst, float(np.abs(got - want).max()))
+    print("\noracle area %d -> %d: max |oracle - torch| %.3g" % (n_in, n_out, worst))
+    assert worst <= 8e-6
 
 
 @pytest.mark.parametrize("mode", rref.MODES)

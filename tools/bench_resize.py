@@ -12,6 +12,7 @@ what the document quotes.
 
     python tools/bench_resize.py                         # 960x540 -> 1920x1080 x 60 and 1920x1080 -> 3840x2160 x 60, both modes
     python tools/bench_resize.py --case 60x1080x1920 --mode bicubic
+    python tools/bench_resize.py --case 60x540x960 --mode area          # x2: windows of one sample, the cost of the index arithmetic
 """
 import argparse
 import json
@@ -94,7 +95,7 @@ def run_case(key, mode, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", action="append", choices=sorted(CASES), help="default: every case")
-    ap.add_argument("--mode", action="append", choices=("bilinear", "bicubic"), help="default: both")
+    ap.add_argument("--mode", action="append", choices=("bilinear", "bicubic", "nearest", "area"), help="default: bilinear and bicubic")
     ap.add_argument("--display", default="standard_4k")
     ap.add_argument("--fps", type=float, default=30.0)
     ap.add_argument("--warmup", type=int, default=2)

@@ -1,5 +1,6 @@
 // Stage 2, two pyramid levels per pass.  Included by fvvdp_hip.hip after band_kernel.hpp.
 #pragma once
+#include "pyramid_constants.hpp"   // F2_PITCH, F2_HL
 // ------------------------------------------------------------------------------------------------------------
 // band2_kernel: reads Gaussian level A (= level i) once, keeps level B (= i+1) in registers, writes level C (= i+2),
 // and accumulates sum(D^beta) of BOTH contrast bands i and i+1 in the same pass.
@@ -23,9 +24,6 @@
 // (fvvdp_lpyr_dec.py:126-142).  A level-B row past the bottom is the mirrored row (B[hb] = B[hb-1], B[hb+1] = B[hb-2]),
 // which is what both the reduce (symmetric) and the expand (clamp, only B[hb]) ask for.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int F2_PITCH = 54;    // level-B columns owned per wave: lanes 6..59, all the two-level halo leaves valid (the kernel is
-                                // co-bound -- its arithmetic alone takes as long as its data flow, profiles/r03_pyramid_bounds.md: 54 vs a line-aligned 52 columns measured +3.4 %)
-constexpr int F2_HL = 6;        // halo lanes on the left (4 on the right); even, so lane parity == column parity
 
 struct Band2Args {
     L0Addr A;               // level A, frame f at l0_frame(A, f): [h][w][P] (level 0 may live in two ranges, device_common.hpp)

@@ -1,6 +1,7 @@
 // Stage 2 kernel: one fused pass per pyramid level (reduce, expand, contrast, CSF, masking, pooling).
 // Included by fvvdp_hip.hip (one translation unit).
 #pragma once
+#include "pyramid_constants.hpp"   // STRIP_J
 // ------------------------------------------------------------------------------------------------------------
 // stage 2: fused pyramid level
 //   read Gaussian level i once, write level i+1 once, and in the same pass expand level i+1, form the contrast
@@ -14,8 +15,6 @@
 //   (test, ref) live in adjacent registers and go through packed fp32 math (v_pk_fma_f32), which also makes the
 //   test and reference planes bit-symmetric (identical inputs give exactly D = 0).
 // ------------------------------------------------------------------------------------------------------------
-constexpr int STRIP_J = 60;     // coarse columns produced per wave (64 lanes - 2 halo lanes each side)
-
 
 template <int P>
 struct Px {                 // one pixel: P/2 (test, ref) pairs

@@ -47,6 +47,13 @@ static int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(FVVDP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// returns the code of a check_* that refused
+#define CHECK_TRY(expr)                   \
+    do {                                  \
+        const int rc_ = (expr);           \
+        if (rc_ != FVVDP_OK) return rc_;  \
+    } while (0)
+
 extern "C" const char* fvvdp_last_error(void) { return g_err; }
 // the message of fvvdp_last_error for a failure in another translation unit of the library (grad_launch.hip); C++ linkage,
 // so the export map (fvvdp_*) keeps it out of the C ABI
@@ -63,6 +70,7 @@ int fvvdp_fail_from(int code, const char* msg) { return fail(code, "%s", msg); }
 #include "still_kernels.hpp"
 #include "psnr_kernel.hpp"
 #include "resize_kernels.hpp"
+#include "pyramid_host.hpp"
 
 // ------------------------------------------------------------------------------------------------------------
 // context
@@ -148,7 +156,7 @@ struct fvvdp_ctx {
     float lum_lo = 0.0f, lum_hi = 0.0f, lum_width = 0.0f;
     float* partial = nullptr;
     long long partial_off[FVVDP_MAX_BANDS]{};
-    int max_blk[FVVDP_MAX_BANDS]{};
+    size_t max_blk[FVVDP_MAX_BANDS]{};   // most work items per frame of any plan of the band (pyramid_item_bounds)
     int* d_ticket = nullptr;      // block counter of the resident temporal kernel (TemporalArgs::ticket), zeroed before every launch
     size_t partial_floats = 0;
     float4* csf = nullptr;        // [n_bands][32] slope-form records of the 1-D tables
@@ -169,7 +177,6 @@ struct fvvdp_ctx {
     bool maps_set = false;
     float* slope[FVVDP_MAX_BANDS]{};           // fvvdp_ctx_set_slope_maps: one more plane of the map-writing pass (owned by the caller)
     bool sub_valid = false;
-    float rho_lo = 0, rho_hi = 0, ecc_lo = 0, ecc_hi = 0;
     bool lut3_set[2] = {false, false};
     float* d_fix = nullptr;       // [max_frames][2]
     float* d_taps = nullptr;      // [2][FVVDP_MAX_TAPS]
@@ -334,73 +341,14 @@ static void vmm_free_all(fvvdp_ctx* c) {
     c->vmm.clear();
 }
 
-// strips cover coarse columns [0,62), [62,122), ... (see band_kernel)
-static int band_strips(int wc) { return wc <= 62 ? 1 : 1 + (wc - 62 + STRIP_J - 1) / STRIP_J; }
-
-static int band2_strips(int wb) { return (wb + F2_PITCH - 1) / F2_PITCH; }
-
-// two-level kernel: a chunk of kr level-C rows costs 2*kr steps of level A plus 7 halo steps and the prologue
-static void chunking2(int hc, int n_strips, int n, long long capacity, int kr_override, int& n_chunks, int& kr) {
-    double best = 1e300;
-    kr = hc;
-    for (int cand = 1; cand <= hc; ++cand) {
-        const long long chunks = (hc + cand - 1) / cand;
-        const long long waves = (long long)n * n_strips * chunks;
-        const long long rounds = (waves + capacity - 1) / capacity;
-        const double cost = (double)rounds * (2.0 * cand + 9.0) * (1.0 + 1e-4 * (double)chunks);
-        if (cost < best) { best = cost; kr = cand; }
-    }
-    if (kr_override >= 1) kr = kr_override > hc ? hc : kr_override;      // tuning override (FVVDP_BAND2_KR)
-    n_chunks = (hc + kr - 1) / kr;
-}
-
-static void chunking(int hc, int n_strips, int n, long long capacity, int& n_chunks, int& cr) {
-    // Every single-wave workgroup does the same amount of work (cr steps + the prologue for the two halo coarse
-    // rows, whose 7 extra fine rows are re-read from HBM: weighted as 8 steps), so the launch proceeds in "rounds"
-    // of `capacity` resident waves.  Pick the chunk height that minimises rounds x per-wave cost.
-    double best = 1e300;
-    cr = hc;
-    for (int cand = 2; cand <= hc || cand == 2; ++cand) {
-        const int c = cand > hc ? hc : cand;
-        const long long chunks = (hc + c - 1) / c;
-        const long long waves = (long long)n * n_strips * chunks;
-        const long long rounds = (waves + capacity - 1) / capacity;
-        const double cost = (double)rounds * ((double)c + 8.0) * (1.0 + 1e-4 * (double)chunks);
-        if (cost < best) { best = cost; cr = c; }
-        if (cand >= hc) break;
-    }
-    n_chunks = (hc + cr - 1) / cr;
-}
-
 static void choose_level0(fvvdp_ctx* c);
 
-// Does the plain pass walk levels b and b + 1 in one two-level launch (band2_kernel)?  Where it pays -- large levels, see
-// bands_forward_core -- and where the two-level border logic holds; FVVDP_BAND_FUSE=1 forces it wherever valid, =0 (the
-// caller's check) never.
-static bool band2_takes(const fvvdp_ctx* c, int b) {
-    const bool big = (long long)c->lw[b] * c->lh[b] >= 500000;      // (4K: levels 0+1 and 2+3; 2+3 in one launch: 3.06 -> 2.67 us per frame)
-    return (big || c->env.fuse_mode == 1) && b + 1 < c->n_bands && c->lw[b + 1] >= 4 && c->lh[b + 1] >= 4 &&
-           c->lw[b + 2] >= 2 && c->lh[b + 2] >= 2;
-}
+// The two-level walk (pyramid_host.hpp) of levels b, b + 1 of this context: whether the plain pass takes it, and its plan for
+// plan_n frames under the context's overrides.
+static bool band2_takes(const fvvdp_ctx* c, int b) { return band2_takes(c->lw, c->lh, c->n_bands, b, c->env.fuse_mode); }
 
-// Work decomposition of the two-level launch over levels b, b + 1 for plan_n frames: strips of level-B columns, chunks of level-C
-// rows -- the first n_big of kr rows, the others of kr2.
-static void band2_plan(const fvvdp_ctx* c, int b, int plan_n, int& n_strips, int& n_chunks, int& kr, int& n_big, int& kr2_out) {
-    const int hc = c->lh[b + 2];
-    n_strips = band2_strips(c->lw[b + 1]);
-    chunking2(hc, n_strips, plan_n, c->wave_capacity2, c->env.band2_kr, n_chunks, kr);
-    n_big = n_chunks;
-    kr2_out = kr;
-    // a launch of several rounds of tall chunks: the last chunk of every frame is cut into four and dispatched after
-    // all tall ones (band2_kernel's two phases)
-    const long long waves = (long long)plan_n * n_strips * n_chunks;
-    int kr2 = (waves >= 2 * c->wave_capacity2 && n_chunks >= 3 && kr >= 16) ? (kr + 3) / 4 : 0;
-    if (c->env.band2_kr2 >= 0) kr2 = c->env.band2_kr2;                  // tuning override (FVVDP_BAND2_KR2); 0 = uniform chunks
-    if (kr2 >= 1 && kr2 < kr && n_chunks >= 2) {
-        n_big = n_chunks - 1;
-        kr2_out = kr2;
-        n_chunks = n_big + (hc - n_big * kr + kr2 - 1) / kr2;
-    }
+static Band2Plan band2_plan(const fvvdp_ctx* c, int b, int plan_n) {
+    return band2_plan(c->lw[b + 1], c->lh[b + 2], plan_n, c->wave_capacity2, c->env.band2_kr, c->env.band2_kr2);
 }
 
 extern "C" int fvvdp_ctx_create(fvvdp_ctx** out, int width, int height, int n_bands, int planes, int max_frames,
@@ -418,33 +366,21 @@ extern "C" int fvvdp_ctx_create(fvvdp_ctx** out, int width, int height, int n_ba
     c->P = planes;
     c->max_frames = max_frames;
     c->prm = *prm;
-    int w = width, h = height;
+    pyramid_level_sizes(width, height, n_bands + 1, c->lw, c->lh);
     for (int i = 0; i <= n_bands; ++i) {
-        c->lw[i] = w;
-        c->lh[i] = h;
         c->rho_band[i] = h_rho_band[i];
-        if (i < n_bands && (w < 2 || h < 2)) {
+        if (i < n_bands && (c->lw[i] < 2 || c->lh[i] < 2)) {
+            const int w = c->lw[i], h = c->lh[i];
             delete c;
             return fail(FVVDP_EINVAL, "pyramid level %d is %dx%d: too many bands for this frame size", i, w, h);
         }
-        w = (w + 1) / 2;
-        h = (h + 1) / 2;
     }
     int rc = FVVDP_OK;
     for (int i = 0; i <= n_bands && rc == FVVDP_OK; ++i) {
         rc = dev_alloc(c, &c->level[i], (size_t)max_frames * c->lw[i] * c->lh[i] * planes);
     }
+    pyramid_item_bounds(c->lw, c->lh, n_bands, true, c->max_blk);
     size_t off = 0;
-    for (int b = 0; b < n_bands; ++b) {
-        const int n_strips = band_strips(c->lw[b + 1]);
-        const int max_chunks = (c->lh[b + 1] + 1) / 2;
-        c->max_blk[b] = n_strips * max_chunks;
-    }
-    for (int b = 0; b + 1 < n_bands; ++b) {       // two-level launches (bands b, b+1 share one work decomposition)
-        const int blk2 = band2_strips(c->lw[b + 1]) * c->lh[b + 2];
-        if (blk2 > c->max_blk[b]) c->max_blk[b] = blk2;
-        if (blk2 > c->max_blk[b + 1]) c->max_blk[b + 1] = blk2;
-    }
     for (int b = 0; b < n_bands; ++b) {
         c->partial_off[b] = (long long)off;
         off += (size_t)max_frames * c->max_blk[b] * 2;
@@ -568,13 +504,10 @@ extern "C" int fvvdp_ctx_set_csf_3d(fvvdp_ctx* c, int tc, const float* h_S_log, 
         c->h_axes[2][i] = h_ecc_sqrt[i];
     }
     HIP_TRY(hipMemcpy(c->d_axes, c->h_axes, sizeof(c->h_axes), hipMemcpyHostToDevice));
-    c->y_lo = exp2f(h_Y_log[0]);
-    c->y_hi = exp2f(h_Y_log[FVVDP_LUT_N - 1]);
+    const FovAxes fx = fov_axes(&c->h_axes[0][0], nullptr);
+    c->y_lo = fx.y_lo;
+    c->y_hi = fx.y_hi;
     c->sub_valid = false;
-    c->rho_lo = exp2f(h_rho_log[0]);
-    c->rho_hi = exp2f(h_rho_log[FVVDP_LUT_N - 1]);
-    c->ecc_lo = h_ecc_sqrt[0] * h_ecc_sqrt[0];
-    c->ecc_hi = h_ecc_sqrt[FVVDP_LUT_N - 1] * h_ecc_sqrt[FVVDP_LUT_N - 1];
     c->lut3_set[tc] = true;
     return FVVDP_OK;
 }
@@ -1192,14 +1125,14 @@ static int build_sublut(fvvdp_ctx* c, const fvvdp_geom* g, hipStream_t st) {
             ra.size_m0 = g->display_size_m[0];
             ra.size_m1 = g->display_size_m[1];
             ra.dist_m = g->distance_m;
-            const double delta = (1.0 / (double)g->ppd_centre) / 2.0 * M_PI / 180.0;
-            ra.delta_rad = (float)delta;
-            ra.cos_delta = (float)cos(delta);
+            const FovAxes fx = fov_axes(&c->h_axes[0][0], g);
+            ra.delta_rad = fx.delta_rad;
+            ra.cos_delta = fx.cos_delta;
             ra.rho_band = (float)c->rho_band[b];
-            ra.rho_lo = c->rho_lo;
-            ra.rho_hi = c->rho_hi;
-            ra.first = c->h_axes[1][0];
-            ra.inv_step = (float)(FVVDP_LUT_N - 1) / (c->h_axes[1][FVVDP_LUT_N - 1] - c->h_axes[1][0]);
+            ra.rho_lo = fx.rho_lo;
+            ra.rho_hi = fx.rho_hi;
+            ra.first = fx.first[1];
+            ra.inv_step = fx.inv_step[1];
             ra.i_lo = i_lo;
             ra.rw = rw;
             ra.axis = c->d_axes + FVVDP_LUT_N;
@@ -1275,30 +1208,40 @@ static int check_pool_params(const fvvdp_pool_params* prm) {
     return FVVDP_OK;
 }
 
-// Launch arguments of the one-level pass of band b (band_kernel, multigaze_kernel): the level, its work decomposition for
-// plan_n frames, the model constants and, foveated, the tables and the geometry.  Left to the caller: partial, n_items, the
-// map outputs.
-static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, bool fov, const fvvdp_geom* geom, BandArgs& a) {
-    memset(&a, 0, sizeof(a));
-    a.F = level_addr(c, b, b == 0 ? slot0 : 0);
-    a.Gc = c->level[b + 1];
-    a.w = c->lw[b];
-    a.h = c->lh[b];
-    a.wc = c->lw[b + 1];
-    a.hc = c->lh[b + 1];
-    a.n_strips = band_strips(a.wc);
-    chunking(a.hc, a.n_strips, plan_n, c->wave_capacity, a.n_chunks, a.cr);
-    if (c->env.band_cr >= 2) {                           // FVVDP_BAND_CR: taller chunks than chunking() picks (fewer, never more, than max_blk[] holds)
-        a.cr = c->env.band_cr > a.hc ? a.hc : c->env.band_cr;
-        a.n_chunks = (a.hc + a.cr - 1) / a.cr;
-    }
-    a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
-    a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
-    a.csf_y = c->csf_y;
+// ---- checks, fills and launches that the three pyramid passes share (plain and foveated, many gazes, many tests) -------------
+// a call that pools (pool != nullptr) needs the place for its JOD and valid exponents
+static int check_pool_request(const fvvdp_pool_params* pool, const float* d_jod) {
+    if (!pool) return FVVDP_OK;
+    if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
+    return check_pool_params(pool);
+}
+
+static int check_q_columns(int n, int q_stride, int q_col0) {
+    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    return FVVDP_OK;
+}
+
+// the caller's workspace of the many-gazes / many-tests pass: `need` bytes for count gazes / tests (`what`) of n frames
+static int check_workspace(const void* d_work, size_t work_bytes, size_t need, const char* what, int count, int n) {
+    if (((uintptr_t)d_work & 255) != 0) return fail(FVVDP_EINVAL, "the workspace must be 256-byte aligned");
+    if (work_bytes < need)
+        return fail(FVVDP_EINVAL, "workspace of %zu bytes is too small: %d %s x %d frames need %zu", work_bytes, count, what, n, need);
+    return FVVDP_OK;
+}
+
+// A plan's partial sums against the room they have (work items per frame against the band's bound, or floats against the band's
+// part of a workspace row).  tests/pyramid_plan_check.cpp proves on the CPU that no plan of pyramid_host.hpp exceeds its bound;
+// the check stays because it is cheap.
+static int check_plan_fits(size_t need, size_t room) {
+    if (need > room) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+    return FVVDP_OK;
+}
+
+// the model constants, in the members that BandArgs and Band2Args share by name
+template <class Args>
+static void fill_model_args(Args& a, const fvvdp_ctx* c) {
     a.y_first = c->y_first;
     a.y_inv_step = c->y_inv_step;
-    a.y_lo = c->y_lo;
-    a.y_hi = c->y_hi;
     a.ly_lo = log2f(c->y_lo);
     a.ly_hi = log2f(c->y_hi);
     a.lg_gain = log2f(c->prm.sens_gain);
@@ -1310,6 +1253,51 @@ static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, boo
     a.lbkg_min = c->prm.lbkg_min;
     a.cmax = c->prm.contrast_max;
     a.lg_dmax = log2f(c->prm.d_max);
+}
+
+// what finalize_kernel / finalize_gazes_kernel take beyond the per-band entries nblk[], off[], npx[] (filled as the bands are planned)
+static void fill_finalize(FinalizeArgs& fa, const fvvdp_ctx* c, const float* partial, float* d_Q, int n, int q_stride, int q_col0) {
+    fa.partial = partial;
+    fa.Q = d_Q;
+    fa.n_bands = c->n_bands;
+    fa.n = n;
+    fa.q_stride = q_stride;
+    fa.q_col0 = q_col0;
+    fa.tc = c->P / 2;
+    fa.inv_beta = 1.0f / c->prm.beta;
+}
+
+// the pooling kernel once per row (a clip, a gaze, a test) of Q_per_ch: row r at d_Q + r * row_stride, its JOD in d_jod[r]
+static void launch_pool_rows(const float* d_Q, long long row_stride, int rows, int n_bands, int q_stride,
+                             const fvvdp_pool_params* pool, float* d_jod, hipStream_t st) {
+    for (int r = 0; r < rows; ++r) {
+        PoolArgs pa;
+        fill_pool_args(pa, d_Q + (size_t)r * row_stride, n_bands, 2, q_stride, q_stride, pool, d_jod + r);
+        hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
+    }
+}
+
+// Launch arguments of the one-level pass of band b (band_kernel, multigaze_kernel): the level, its work decomposition for
+// plan_n frames, the model constants and, foveated, the tables and the geometry.  Left to the caller: partial, n_items, the
+// map outputs.
+static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, bool fov, const fvvdp_geom* geom, BandArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.F = level_addr(c, b, b == 0 ? slot0 : 0);
+    a.Gc = c->level[b + 1];
+    a.w = c->lw[b];
+    a.h = c->lh[b];
+    a.wc = c->lw[b + 1];
+    a.hc = c->lh[b + 1];
+    const BandPlan plan = chunking(a.hc, band_strips(a.wc), plan_n, c->wave_capacity, c->env.band_cr);
+    a.n_strips = plan.n_strips;
+    a.n_chunks = plan.n_chunks;
+    a.cr = plan.cr;
+    a.band_mul = (b == 0) ? 1.0f : 2.0f;                 // lpyr.get_band, fvvdp_lpyr_dec.py:57-63
+    a.csf = c->csf + (size_t)b * FVVDP_LUT_N;
+    a.csf_y = c->csf_y;
+    fill_model_args(a, c);
+    a.y_lo = c->y_lo;
+    a.y_hi = c->y_hi;
     if (fov) {
         a.sublut = c->sublut[b];
         a.axes = c->d_axes;
@@ -1320,9 +1308,6 @@ static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, boo
             a.size_m0 = geom->display_size_m[0];
             a.size_m1 = geom->display_size_m[1];
             a.dist_m = geom->distance_m;
-            const double delta = (1.0 / (double)geom->ppd_centre) / 2.0 * M_PI / 180.0;
-            a.delta_rad = (float)delta;
-            a.cos_delta = (float)cos(delta);
         } else {
             a.size_m0 = a.size_m1 = a.dist_m = 1.0f;
             a.mvx = c->map_vx[b];
@@ -1330,16 +1315,18 @@ static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, boo
             a.mrm = c->map_rm[b];
         }
         a.rho_band = (float)c->rho_band[b];
-        a.rho_lo = c->rho_lo;
-        a.rho_hi = c->rho_hi;
-        a.ecc_lo = c->ecc_lo;
-        a.ecc_hi = c->ecc_hi;
+        const FovAxes fx = fov_axes(&c->h_axes[0][0], geom);
+        a.delta_rad = fx.delta_rad;
+        a.cos_delta = fx.cos_delta;
+        a.rho_lo = fx.rho_lo;
+        a.rho_hi = fx.rho_hi;
+        a.ecc_lo = fx.ecc_lo;
+        a.ecc_hi = fx.ecc_hi;
         for (int ax = 0; ax < 3; ++ax) {
-            a.first[ax] = c->h_axes[ax][0];
-            a.inv_step[ax] = (float)(FVVDP_LUT_N - 1) / (c->h_axes[ax][FVVDP_LUT_N - 1] - c->h_axes[ax][0]);
-            const double step = ((double)c->h_axes[ax][FVVDP_LUT_N - 1] - (double)c->h_axes[ax][0]) / (FVVDP_LUT_N - 1);
-            a.frac_scale[ax] = (float)(step / (step + 1e-6));
-            a.grid_off[ax] = -a.first[ax] * a.inv_step[ax];
+            a.first[ax] = fx.first[ax];
+            a.inv_step[ax] = fx.inv_step[ax];
+            a.frac_scale[ax] = fx.frac_scale[ax];
+            a.grid_off[ax] = fx.grid_off[ax];
         }
         a.frame_w = c->W;
         a.frame_h = c->H;
@@ -1354,6 +1341,77 @@ static void fill_band_args(const fvvdp_ctx* c, int b, int slot0, int plan_n, boo
     }
 }
 
+// band b's entries of the finalize block: nblk work items per frame, their partial sums at `off`
+static void record_band(FinalizeArgs& fa, const fvvdp_ctx* c, int b, int nblk, long long off) {
+    fa.nblk[b] = nblk;
+    fa.off[b] = off;
+    fa.npx[b] = (float)c->lw[b] * (float)c->lh[b];
+}
+
+// The two-level launch (band2_kernel) of levels b, b + 1 for the n frames from slot0 on, in the work decomposition p.
+static void launch_band2(fvvdp_ctx* c, int b, int slot0, int n, const Band2Plan& p, hipStream_t st) {
+    Band2Args a;
+    memset(&a, 0, sizeof(a));
+    a.A = level_addr(c, b, b == 0 ? slot0 : 0);
+    a.Gc = c->level[b + 2];
+    a.w = c->lw[b];
+    a.h = c->lh[b];
+    a.wb = c->lw[b + 1];
+    a.hb = c->lh[b + 1];
+    a.wc = c->lw[b + 2];
+    a.hc = c->lh[b + 2];
+    a.n_strips = p.n_strips;
+    a.n_chunks = p.n_chunks;
+    a.kr = p.kr;
+    a.n_big = p.n_big;
+    a.kr2 = p.kr2;
+    a.n_frames = n;
+    a.mulA = (b == 0) ? 1.0f : 2.0f;
+    a.mulB = 2.0f;
+    a.csfA = c->csf + (size_t)b * FVVDP_LUT_N;
+    a.csfB = c->csf + (size_t)(b + 1) * FVVDP_LUT_N;
+    fill_model_args(a, c);
+    a.partialA = c->partial + c->partial_off[b];
+    a.partialB = c->partial + c->partial_off[b + 1];
+    Timed tm(c, 1 + b, st);
+    const bool inrange = clamps_never_bind(c, b, 2);
+    // Waves per workgroup: 4 adjacent strips walked in step (one barrier per stage).  Free-running single waves drift
+    // apart over a long launch (items started in the first round of a 4K x 60 launch, all in step, take 316 us, later
+    // ones 390 us); neighbours kept in step meet in the CU's vector cache on their shared halo columns and ask for one
+    // contiguous piece of each row.  Measured (profiles/r04_lockstep.md): -1.5 ... -6 % at 4K on five boxes, -2.6 % at
+    // 8K, 0 ... -3 % at 2560x1440; slower where the strips do not fill whole groups (a workgroup holds its four wave
+    // slots) and below 2560 columns (short launches stay in step by themselves).  Same work items, same partial sums.
+    int wpb = (a.w >= 2560 && a.n_strips % BAND2_WPB_MAX == 0) ? BAND2_WPB_MAX : 1;
+    { const int v = c->env.band2_wpb; if (v >= 1 && v <= BAND2_WPB_MAX && a.n_strips % v == 0) wpb = v; }      // FVVDP_BAND2_WPB
+    // work items handed out per XCD at run time (band2_kernel, `tickets`): launches of several rounds only;
+    // FVVDP_BAND2_TICKET=0 / 1 forces the static split / the counters
+    const int n_items = (a.n_strips / wpb) * a.n_chunks * n;
+    const long long waves2 = (long long)n * a.n_strips * a.n_chunks;
+    // Measured (profiles/r05_band2_tickets.md): 4K levels 0+1 (6000 items of ~300 us, 4 waves each) -0.4 ... -1.9 %; launches of
+    // many short items lose -- every workgroup's atomic is served at the memory side, ~0.3 us each and one after the other
+    // per counter (1080p levels 0+1, 8640 single-wave items: 8.8 -> 14.3 us per frame; 4K levels 2+3: 2.8 -> 3.7) -- so the
+    // counters are on only for the wide launches whose workgroups carry 4 strips
+    bool tickets = c->d_ticket && (c->env.band2_ticket == 1 ||
+                                   (c->env.band2_ticket != 0 && waves2 >= 2 * c->wave_capacity2 && wpb == BAND2_WPB_MAX && a.w >= 2560));
+    if (tickets && hipMemsetAsync(c->d_ticket, 0, 16 * sizeof(int), st) != hipSuccess) { (void)hipGetLastError(); tickets = false; }
+    a.n_items = n_items;
+    a.tickets = tickets ? c->d_ticket : nullptr;
+    const int n_wg = tickets ? ((n_items + n_items / 8 + 7) / 8 * 8) : n_items;
+    const dim3 grid2((unsigned int)n_wg), block2(64 * wpb);
+    if (c->env.debug_variant)                // tests: which variant was launched, and its plan (strips, chunk heights in level-C rows)
+        fprintf(stderr, "fvvdp: levels %d+%d: band2_kernel<%d, %s>, luminance range %s [%g, %g], widest plane range %g, %d waves per workgroup"
+                        ", n_strips %d, kr %d, kr2 %d, n_big %d, n_chunks %d, tickets %s\n",
+                b, b + 1, c->P, inrange ? "true" : "false", c->lum_state == 1 ? "known" : "unknown", c->lum_lo, c->lum_hi, c->lum_width, wpb,
+                a.n_strips, a.kr, a.kr2, a.n_big, a.n_chunks, tickets ? "on" : "off");
+    if (c->P == 4) {
+        if (inrange) hipLaunchKernelGGL((band2_kernel<4, true>), grid2, block2, 0, st, a);
+        else hipLaunchKernelGGL((band2_kernel<4, false>), grid2, block2, 0, st, a);
+    } else {
+        if (inrange) hipLaunchKernelGGL((band2_kernel<2, true>), grid2, block2, 0, st, a);
+        else hipLaunchKernelGGL((band2_kernel<2, false>), grid2, block2, 0, st, a);
+    }
+}
+
 // slot0: first level-0 frame slot of the batch (fvvdp_temporal_channels wrote slots [slot0, slot0 + n)); the levels below are
 // scratch of the pass itself and always use slots [0, n).
 // plan_n: the number of frames the work decomposition (chunk heights, and with them the grouping of the float partial sums
@@ -1365,15 +1423,9 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
     if (plan_n < 1) plan_n = n;
     if (!c || !d_Q) return fail(FVVDP_EINVAL, "null argument");
     if (slot0 < 0 || n < 1 || slot0 + n > c->max_frames) return fail(FVVDP_EINVAL, "slots [%d,%d) exceed max_frames %d", slot0, slot0 + n, c->max_frames);
-    if (pool) {
-        if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
-        int rc = check_pool_params(pool);
-        if (rc != FVVDP_OK) return rc;
-    }
-    const bool last_batch = (q_col0 + n == q_stride);            // this call completes the clip
-    const bool pool_now = pool && last_batch;
+    CHECK_TRY(check_pool_request(pool, d_jod));
     if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
-    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    CHECK_TRY(check_q_columns(n, q_stride, q_col0));
     const bool fov = h_fixation != nullptr;
     if (fov && !geom && !c->maps_set) return fail(FVVDP_EINVAL, "foveated mode needs the display geometry (or fvvdp_ctx_set_view_maps)");
     if (fov && !(c->lut3_set[0] && (c->P == 2 || c->lut3_set[1]))) return fail(FVVDP_ESTATE, "fvvdp_ctx_set_csf_3d not called");
@@ -1383,8 +1435,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
         // stream-ordered after the kernels of the previous call that still read d_fix; the source is pageable host
         // memory, which the runtime stages before the call returns
         HIP_TRY(hipMemcpyAsync(c->d_fix, h_fixation, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
-        int rc = build_sublut(c, geom, st);
-        if (rc != FVVDP_OK) return rc;
+        CHECK_TRY(build_sublut(c, geom, st));
     }
     FinalizeArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -1396,87 +1447,15 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
     // It pays where the one-level kernel is bound by HBM (large levels: 4K levels 0+1 39 vs 46 us per frame); the
     // two-level kernel's arithmetic takes as long as its data flow (its strips own 54 of 64 lanes), so small levels stay on the one-level kernel
     // (960x540 + 480x270: 3.1 vs 2.95 us).  FVVDP_BAND_FUSE=0 / 1 forces never / wherever valid (tests, A/B runs).
-    const int fuse_mode = c->env.fuse_mode;                      // 0 / 1, anything else: automatic
-    const bool fuse_ok = !fov && !any_maps && fuse_mode != 0;
+    const bool fuse_ok = !fov && !any_maps && c->env.fuse_mode != 0;
     for (int b = 0; b < c->n_bands; ++b) {
         if (fuse_ok && band2_takes(c, b)) {
-            Band2Args a;
-            memset(&a, 0, sizeof(a));
-            a.A = level_addr(c, b, b == 0 ? slot0 : 0);
-            a.Gc = c->level[b + 2];
-            a.w = c->lw[b];
-            a.h = c->lh[b];
-            a.wb = c->lw[b + 1];
-            a.hb = c->lh[b + 1];
-            a.wc = c->lw[b + 2];
-            a.hc = c->lh[b + 2];
-            band2_plan(c, b, plan_n, a.n_strips, a.n_chunks, a.kr, a.n_big, a.kr2);
-            a.n_frames = n;
-            a.mulA = (b == 0) ? 1.0f : 2.0f;
-            a.mulB = 2.0f;
-            a.csfA = c->csf + (size_t)b * FVVDP_LUT_N;
-            a.csfB = c->csf + (size_t)(b + 1) * FVVDP_LUT_N;
-            a.y_first = c->y_first;
-            a.y_inv_step = c->y_inv_step;
-            a.ly_lo = log2f(c->y_lo);
-            a.ly_hi = log2f(c->y_hi);
-            a.lg_gain = log2f(c->prm.sens_gain);
-            a.lg_k = log2f(c->prm.mask_k);
-            a.p = c->prm.mask_p;
-            a.q0 = c->prm.mask_q[0];
-            a.q1 = c->prm.mask_q[1];
-            a.beta = c->prm.beta;
-            a.lbkg_min = c->prm.lbkg_min;
-            a.cmax = c->prm.contrast_max;
-            a.lg_dmax = log2f(c->prm.d_max);
-            a.partialA = c->partial + c->partial_off[b];
-            a.partialB = c->partial + c->partial_off[b + 1];
-            const int nblk = a.n_strips * a.n_chunks;
-            if (nblk > c->max_blk[b] || nblk > c->max_blk[b + 1]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
-            {
-                Timed tm(c, 1 + b, st);
-                const bool inrange = clamps_never_bind(c, b, 2);
-                // Waves per workgroup: 4 adjacent strips walked in step (one barrier per stage).  Free-running single waves drift
-                // apart over a long launch (items started in the first round of a 4K x 60 launch, all in step, take 316 us, later
-                // ones 390 us); neighbours kept in step meet in the CU's vector cache on their shared halo columns and ask for one
-                // contiguous piece of each row.  Measured (profiles/r04_lockstep.md): -1.5 ... -6 % at 4K on five boxes, -2.6 % at
-                // 8K, 0 ... -3 % at 2560x1440; slower where the strips do not fill whole groups (a workgroup holds its four wave
-                // slots) and below 2560 columns (short launches stay in step by themselves).  Same work items, same partial sums.
-                int wpb = (a.w >= 2560 && a.n_strips % BAND2_WPB_MAX == 0) ? BAND2_WPB_MAX : 1;
-                { const int v = c->env.band2_wpb; if (v >= 1 && v <= BAND2_WPB_MAX && a.n_strips % v == 0) wpb = v; }      // FVVDP_BAND2_WPB
-                // work items handed out per XCD at run time (band2_kernel, `tickets`): launches of several rounds only;
-                // FVVDP_BAND2_TICKET=0 / 1 forces the static split / the counters
-                const int n_items = (a.n_strips / wpb) * a.n_chunks * n;
-                const long long waves2 = (long long)n * a.n_strips * a.n_chunks;
-                // Measured (profiles/r05_band2_tickets.md): 4K levels 0+1 (6000 items of ~300 us, 4 waves each) -0.4 ... -1.9 %; launches of
-                // many short items lose -- every workgroup's atomic is served at the memory side, ~0.3 us each and one after the other
-                // per counter (1080p levels 0+1, 8640 single-wave items: 8.8 -> 14.3 us per frame; 4K levels 2+3: 2.8 -> 3.7) -- so the
-                // counters are on only for the wide launches whose workgroups carry 4 strips
-                bool tickets = c->d_ticket && (c->env.band2_ticket == 1 ||
-                                               (c->env.band2_ticket != 0 && waves2 >= 2 * c->wave_capacity2 && wpb == BAND2_WPB_MAX && a.w >= 2560));
-                if (tickets && hipMemsetAsync(c->d_ticket, 0, 16 * sizeof(int), st) != hipSuccess) { (void)hipGetLastError(); tickets = false; }
-                a.n_items = n_items;
-                a.tickets = tickets ? c->d_ticket : nullptr;
-                const int n_wg = tickets ? ((n_items + n_items / 8 + 7) / 8 * 8) : n_items;
-                const dim3 grid2((unsigned int)n_wg), block2(64 * wpb);
-                if (c->env.debug_variant)                // tests: which variant was launched, and its plan (strips, chunk heights in level-C rows)
-                    fprintf(stderr, "fvvdp: levels %d+%d: band2_kernel<%d, %s>, luminance range %s [%g, %g], widest plane range %g, %d waves per workgroup"
-                                    ", n_strips %d, kr %d, kr2 %d, n_big %d, n_chunks %d, tickets %s\n",
-                                 b, b + 1, c->P, inrange ? "true" : "false", c->lum_state == 1 ? "known" : "unknown", c->lum_lo, c->lum_hi, c->lum_width, wpb,
-                                 a.n_strips, a.kr, a.kr2, a.n_big, a.n_chunks, tickets ? "on" : "off");
-                if (c->P == 4) {
-                    if (inrange) hipLaunchKernelGGL((band2_kernel<4, true>), grid2, block2, 0, st, a);
-                    else hipLaunchKernelGGL((band2_kernel<4, false>), grid2, block2, 0, st, a);
-                } else {
-                    if (inrange) hipLaunchKernelGGL((band2_kernel<2, true>), grid2, block2, 0, st, a);
-                    else hipLaunchKernelGGL((band2_kernel<2, false>), grid2, block2, 0, st, a);
-                }
-            }
-            for (int bb = b; bb <= b + 1; ++bb) {
-                fa.nblk[bb] = nblk;
-                fa.off[bb] = c->partial_off[bb];
-                fa.npx[bb] = (float)c->lw[bb] * (float)c->lh[bb];
-            }
+            const Band2Plan p = band2_plan(c, b, plan_n);
+            const int nblk = p.n_strips * p.n_chunks;
+            CHECK_TRY(check_plan_fits(nblk, std::min(c->max_blk[b], c->max_blk[b + 1])));
+            launch_band2(c, b, slot0, n, p, st);
+            record_band(fa, c, b, nblk, c->partial_off[b]);
+            record_band(fa, c, b + 1, nblk, c->partial_off[b + 1]);
             ++b;                                             // band b+1 is done as well
             continue;
         }
@@ -1492,7 +1471,7 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             dbg = a.dD || a.dC || a.dL || a.dS;
         }
         const int nblk = a.n_strips * a.n_chunks;
-        if (nblk > c->max_blk[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+        CHECK_TRY(check_plan_fits(nblk, c->max_blk[b]));
         a.n_items = nblk * n;
         if (c->env.debug_variant) debug_band_line(c, b, a, n, dbg, fov);
         {
@@ -1500,28 +1479,16 @@ static int bands_forward_core(fvvdp_ctx* c, int slot0, int n, float* d_Q, int q_
             if (c->P == 4) launch_band<4>(a, nblk * n, dbg, fov, st, c->slope[b]);
             else launch_band<2>(a, nblk * n, dbg, fov, st, c->slope[b]);
         }
-        fa.nblk[b] = nblk;
-        fa.off[b] = c->partial_off[b];
-        fa.npx[b] = (float)a.w * (float)a.h;
+        record_band(fa, c, b, nblk, c->partial_off[b]);
     }
-    fa.partial = c->partial;
-    fa.Q = d_Q;
-    fa.n_bands = c->n_bands;
-    fa.n = n;
-    fa.q_stride = q_stride;
-    fa.q_col0 = q_col0;
-    fa.tc = c->P / 2;
-    fa.inv_beta = 1.0f / c->prm.beta;
+    fill_finalize(fa, c, c->partial, d_Q, n, q_stride, q_col0);
     {
         Timed tm(c, 1 + c->n_bands, st);
         const int total = c->n_bands * 2 * n;
         hipLaunchKernelGGL(finalize_kernel, dim3(total), dim3(64), 0, st, fa);
     }
-    if (pool_now) {
-        PoolArgs pa;
-        fill_pool_args(pa, d_Q, c->n_bands, 2, q_stride, q_stride, pool, d_jod);
-        hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
-    }
+    if (pool && q_col0 + n == q_stride)                       // this call completes the clip
+        launch_pool_rows(d_Q, 0, 1, c->n_bands, q_stride, pool, d_jod, st);
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }
@@ -1540,17 +1507,9 @@ extern "C" int fvvdp_bands_forward_pool(fvvdp_ctx* c, int n, float* d_Q, int q_s
 
 // ---- one clip under many gazes (include/fvvdp_hip_gaze.h) --------------------------------------------------------------------
 // Floats of one gaze's row of the workspace (documented in the header) and, in off[], where every band starts in it.
+// The one-level bound of every band: the foveated pass never takes the two-level walk.
 static size_t gaze_row_floats(int width, int height, int n_bands, int n, size_t* off) {
-    size_t fl = 0;
-    int w = width, h = height;
-    for (int b = 0; b < n_bands; ++b) {
-        const int wc = (w + 1) / 2, hc = (h + 1) / 2;
-        if (off) off[b] = fl;
-        fl += (size_t)n * band_strips(wc) * ((hc + 1) / 2) * 2;
-        w = wc;
-        h = hc;
-    }
-    return (fl + 63) / 64 * 64;
+    return pyramid_row_floats(width, height, n_bands, n, false, off);
 }
 
 extern "C" int fvvdp_gaze_workspace(int width, int height, int n_bands, int n_gazes, int n, size_t* bytes) {
@@ -1576,29 +1535,19 @@ static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const floa
                                     int q_stride, int q_col0, const fvvdp_geom* geom, void* d_work, size_t work_bytes,
                                     const fvvdp_pool_params* pool, float* d_jod, void* stream) {
     if (!c || !d_gaze || !d_Q || !geom || !d_work) return fail(FVVDP_EINVAL, "null argument");
-    if (pool) {
-        if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
-        int rc = check_pool_params(pool);
-        if (rc != FVVDP_OK) return rc;
-    }
+    CHECK_TRY(check_pool_request(pool, d_jod));
     if (n_gazes < 1) return fail(FVVDP_EINVAL, "n_gazes must be >= 1, got %d", n_gazes);
     if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
-    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    CHECK_TRY(check_q_columns(n, q_stride, q_col0));
     if (gaze_stride < (size_t)2 * n) return fail(FVVDP_EINVAL, "gaze_stride %zu is less than 2 n = %d floats", gaze_stride, 2 * n);
     if (!(c->lut3_set[0] && (c->P == 2 || c->lut3_set[1])))
         return fail(FVVDP_EINVAL, "the context is not foveated (fvvdp_ctx_set_csf_3d not called)");
     if (c->maps_set) return fail(FVVDP_EINVAL, "view maps of a user geometry are set: the gaze pass covers the stock geometry only");
-    if (((uintptr_t)d_work & 255) != 0) return fail(FVVDP_EINVAL, "the workspace must be 256-byte aligned");
     size_t off[FVVDP_MAX_BANDS];
     const size_t row = gaze_row_floats(c->W, c->H, c->n_bands, n, off);
-    if (work_bytes < (size_t)n_gazes * row * sizeof(float))
-        return fail(FVVDP_EINVAL, "workspace of %zu bytes is too small: %d gazes x %d frames need %zu", work_bytes, n_gazes, n,
-                    (size_t)n_gazes * row * sizeof(float));
+    CHECK_TRY(check_workspace(d_work, work_bytes, (size_t)n_gazes * row * sizeof(float), "gazes", n_gazes, n));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    {
-        int rc = build_sublut(c, geom, st);
-        if (rc != FVVDP_OK) return rc;
-    }
+    CHECK_TRY(build_sublut(c, geom, st));
     float* work = reinterpret_cast<float*>(d_work);
     const int group_max = c->env.gaze_group >= 1 ? c->env.gaze_group : FVVDP_GAZE_GROUP_MAX;
     GazeFinalizeArgs fa;
@@ -1609,14 +1558,12 @@ static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const floa
     for (int b = 0; b < c->n_bands; ++b) {
         fill_band_args(c, b, 0, n, true, geom, m[b].b);
         const int nblk = m[b].b.n_strips * m[b].b.n_chunks;
-        if ((size_t)n * nblk * 2 > (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+        CHECK_TRY(check_plan_fits((size_t)n * nblk * 2, (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]));
         m[b].b.fix = nullptr;
         m[b].b.n_items = nblk * n;
         m[b].gaze_stride = (long long)gaze_stride;
         m[b].partial_stride = (long long)row;
-        fa.f.nblk[b] = nblk;
-        fa.f.off[b] = (long long)off[b];
-        fa.f.npx[b] = (float)m[b].b.w * (float)m[b].b.h;
+        record_band(fa.f, c, b, nblk, (long long)off[b]);
     }
     for (int b = 0; b < c->n_bands; ++b) {
         Timed tm(c, 1 + b, st);
@@ -1651,27 +1598,15 @@ static int bands_forward_gazes_core(fvvdp_ctx* c, int n, int n_gazes, const floa
         }
     }
     const long long q_stride_g = (long long)c->n_bands * 2 * q_stride;
-    fa.f.partial = work;
-    fa.f.Q = d_Q;
-    fa.f.n_bands = c->n_bands;
-    fa.f.n = n;
-    fa.f.q_stride = q_stride;
-    fa.f.q_col0 = q_col0;
-    fa.f.tc = c->P / 2;
-    fa.f.inv_beta = 1.0f / c->prm.beta;
+    fill_finalize(fa.f, c, work, d_Q, n, q_stride, q_col0);
     fa.partial_stride = (long long)row;
     fa.q_stride_g = q_stride_g;
     {
         Timed tm(c, 1 + c->n_bands, st);
         hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_gazes), dim3(64), 0, st, fa);
     }
-    if (pool && q_col0 + n == q_stride) {
-        for (int g = 0; g < n_gazes; ++g) {          // the single-gaze pooling kernel, once per gaze
-            PoolArgs pa;
-            fill_pool_args(pa, d_Q + (size_t)g * q_stride_g, c->n_bands, 2, q_stride, q_stride, pool, d_jod + g);
-            hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
-        }
-    }
+    if (pool && q_col0 + n == q_stride)              // the single-gaze pooling kernel, once per gaze
+        launch_pool_rows(d_Q, q_stride_g, n_gazes, c->n_bands, q_stride, pool, d_jod, st);
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }
@@ -1693,28 +1628,9 @@ extern "C" int fvvdp_bands_forward_gazes_pool(fvvdp_ctx* c, int n, int n_gazes, 
 
 // ---- many tests per reference (include/fvvdp_hip_tests.h) ------------------------------------------------------------------
 // Floats of one test's row of the workspace (documented in the header) and, in off[], where every band starts in it: per band the
-// larger of the one-level and the two-level bound of work items per frame, as fvvdp_ctx_create sizes the context's own partials.
+// larger of the one-level and the two-level bound of work items per frame, the bound of the context's own partials.
 static size_t tests_row_floats(int width, int height, int n_bands, int n, size_t* off) {
-    int lw[FVVDP_MAX_BANDS + 2], lh[FVVDP_MAX_BANDS + 2];
-    lw[0] = width;
-    lh[0] = height;
-    for (int i = 1; i <= n_bands + 1; ++i) {
-        lw[i] = (lw[i - 1] + 1) / 2;
-        lh[i] = (lh[i - 1] + 1) / 2;
-    }
-    size_t blk[FVVDP_MAX_BANDS];
-    for (int b = 0; b < n_bands; ++b) blk[b] = (size_t)band_strips(lw[b + 1]) * ((lh[b + 1] + 1) / 2);
-    for (int b = 0; b + 1 < n_bands; ++b) {
-        const size_t blk2 = (size_t)band2_strips(lw[b + 1]) * lh[b + 2];
-        if (blk2 > blk[b]) blk[b] = blk2;
-        if (blk2 > blk[b + 1]) blk[b + 1] = blk2;
-    }
-    size_t fl = 0;
-    for (int b = 0; b < n_bands; ++b) {
-        if (off) off[b] = fl;
-        fl += (size_t)n * blk[b] * 2;
-    }
-    return (fl + 63) / 64 * 64;
+    return pyramid_row_floats(width, height, n_bands, n, true, off);
 }
 
 extern "C" int fvvdp_tests_workspace(int width, int height, int n_bands, int n_tests, int n, size_t* bytes) {
@@ -1738,28 +1654,21 @@ static void launch_multitest(const MultiTestArgs& m, int nq, bool rx, hipStream_
 static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, void* d_work,
                                     size_t work_bytes, const fvvdp_pool_params* pool, float* d_jod, void* stream) {
     if (!c || !d_Q || !d_work) return fail(FVVDP_EINVAL, "null argument");
-    if (pool) {
-        if (!d_jod) return fail(FVVDP_EINVAL, "null argument");
-        int rc = check_pool_params(pool);
-        if (rc != FVVDP_OK) return rc;
-    }
+    CHECK_TRY(check_pool_request(pool, d_jod));
     if (n_tests < 1) return fail(FVVDP_EINVAL, "n_tests must be >= 1, got %d", n_tests);
     if (n < 1) return fail(FVVDP_EINVAL, "n must be >= 1, got %d", n);
     const int n_quads = n_tests / 2 + 1;                     // ceil((n_tests + 1) / 2): streams 0 .. n_tests, two per quad
     if ((long long)n_quads * n > c->max_frames)
         return fail(FVVDP_EINVAL, "%d tests x %d frames need %d x %d frame slots, the context has max_frames=%d", n_tests, n, n_quads, n,
                     c->max_frames);
-    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
+    CHECK_TRY(check_q_columns(n, q_stride, q_col0));
     if (c->P != 4) return fail(FVVDP_EINVAL, "a still-image context (2 planes): the tests pass covers video contexts (4 planes)");
     if (c->lut3_set[0] || c->lut3_set[1])
         return fail(FVVDP_EINVAL, "the context is foveated (fvvdp_ctx_set_csf_3d called): the tests pass covers the non-foveated metric");
     if (!c->csf_set) return fail(FVVDP_ESTATE, "fvvdp_ctx_set_csf_1d not called");
-    if (((uintptr_t)d_work & 255) != 0) return fail(FVVDP_EINVAL, "the workspace must be 256-byte aligned");
     size_t off[FVVDP_MAX_BANDS];
     const size_t row = tests_row_floats(c->W, c->H, c->n_bands, n, off);
-    if (work_bytes < (size_t)n_tests * row * sizeof(float))
-        return fail(FVVDP_EINVAL, "workspace of %zu bytes is too small: %d tests x %d frames need %zu", work_bytes, n_tests, n,
-                    (size_t)n_tests * row * sizeof(float));
+    CHECK_TRY(check_workspace(d_work, work_bytes, (size_t)n_tests * row * sizeof(float), "tests", n_tests, n));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* work = reinterpret_cast<float*>(d_work);
     int group_max = FVVDP_TESTS_GROUP_MAX;
@@ -1785,22 +1694,19 @@ static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q
         }
         if (mode[b] != 0) {
             const int bA = mode[b] == 1 ? b : b - 1;
-            int n_strips, n_chunks, kr, n_big, kr2;
-            band2_plan(c, bA, n, n_strips, n_chunks, kr, n_big, kr2);
-            g.b.n_strips = n_strips;
-            g.b.n_chunks = n_chunks;
+            const Band2Plan p = band2_plan(c, bA, n);
+            g.b.n_strips = p.n_strips;
+            g.b.n_chunks = p.n_chunks;
             g.b.cr = 0;                                      // not used: the chunks are [ka, kb) of level-C rows
-            g.kr = kr; g.n_big = n_big; g.kr2 = kr2; g.k_lim = c->lh[bA + 2];
+            g.kr = p.kr; g.n_big = p.n_big; g.kr2 = p.kr2; g.k_lim = c->lh[bA + 2];
             if (mode[b] == 1) { g.pitch = F2_PITCH; g.joff = F2_HL; g.own_lo = g.own_lo0 = F2_HL; g.own_hi = F2_HL + F2_PITCH; g.row_mul = 2; }
             else { g.pitch = F2_PITCH / 2; g.joff = F2_HL / 2; g.own_lo = g.own_lo0 = F2_HL / 2; g.own_hi = (F2_HL + F2_PITCH) / 2; g.row_mul = 1; }
         }
         const int nblk = m[b].b.n_strips * m[b].b.n_chunks;
-        if ((size_t)n * nblk * 2 > (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]) return fail(FVVDP_ESTATE, "internal: partial buffer too small");
+        CHECK_TRY(check_plan_fits((size_t)n * nblk * 2, (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]));
         m[b].b.n_items = nblk * n;
         m[b].partial = work + off[b];
-        fa.f.nblk[b] = nblk;
-        fa.f.off[b] = (long long)off[b];
-        fa.f.npx[b] = (float)m[b].b.w * (float)m[b].b.h;
+        record_band(fa.f, c, b, nblk, (long long)off[b]);
     }
     for (int b = 0; b < c->n_bands; ++b) {
         Timed tm(c, 1 + b, st);
@@ -1833,27 +1739,15 @@ static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q
         } while (q0 < ref_quad);
     }
     const long long q_stride_t = (long long)c->n_bands * 2 * q_stride;
-    fa.f.partial = work;
-    fa.f.Q = d_Q;
-    fa.f.n_bands = c->n_bands;
-    fa.f.n = n;
-    fa.f.q_stride = q_stride;
-    fa.f.q_col0 = q_col0;
-    fa.f.tc = c->P / 2;
-    fa.f.inv_beta = 1.0f / c->prm.beta;
+    fill_finalize(fa.f, c, work, d_Q, n, q_stride, q_col0);
     fa.partial_stride = (long long)row;
     fa.q_stride_g = q_stride_t;
     {
         Timed tm(c, 1 + c->n_bands, st);
         hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_tests), dim3(64), 0, st, fa);
     }
-    if (pool && q_col0 + n == q_stride) {
-        for (int k = 0; k < n_tests; ++k) {          // the pooling kernel of fvvdp_bands_forward_pool, once per test
-            PoolArgs pa;
-            fill_pool_args(pa, d_Q + (size_t)k * q_stride_t, c->n_bands, 2, q_stride, q_stride, pool, d_jod + k);
-            hipLaunchKernelGGL(pool_jod_kernel, dim3(1), dim3(256), 0, st, pa);
-        }
-    }
+    if (pool && q_col0 + n == q_stride)              // the pooling kernel of fvvdp_bands_forward_pool, once per test
+        launch_pool_rows(d_Q, q_stride_t, n_tests, c->n_bands, q_stride, pool, d_jod, st);
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }
@@ -2291,11 +2185,8 @@ extern "C" int fvvdp_images_forward_pool(fvvdp_ctx* c, int n, float* d_Q, int q_
     if (!c || !d_Q || !pool || !d_jod) return fail(FVVDP_EINVAL, "null argument");
     if (c->P != 2) return fail(FVVDP_EINVAL, "fvvdp_images_forward_pool needs a still-image context (planes == 2)");
     if (n < 1 || n > c->max_frames) return fail(FVVDP_EINVAL, "n=%d exceeds max_frames=%d", n, c->max_frames);
-    if (q_col0 < 0 || q_col0 + n > q_stride) return fail(FVVDP_EINVAL, "Q columns out of range");
-    {
-        int rc = check_pool_params(pool);
-        if (rc != FVVDP_OK) return rc;
-    }
+    CHECK_TRY(check_q_columns(n, q_stride, q_col0));
+    CHECK_TRY(check_pool_request(pool, d_jod));
     // work decomposition planned for FVVDP_IMAGES_PLAN_N slots whatever n is: a pair's Q does not depend on its batch
     int rc = bands_forward_core(c, 0, n, d_Q, q_stride, q_col0, h_fixation, geom, maps, nullptr, nullptr, stream,
                                 FVVDP_IMAGES_PLAN_N);

@@ -17,6 +17,7 @@
 #include "grad_common.hpp"
 #include "gaze_grad_kernels.hpp"
 #include "grad_host.hpp"
+#include "pyramid_host.hpp"
 
 // the limits of fvvdp_video_grad_frames: the 2n planes of a batch and the rows of level 0 are grid dimensions
 static int check_dims(int width, int height, int n_bands, int n, int n_gazes) {
@@ -126,22 +127,20 @@ extern "C" int fvvdp_gaze_grad_frames(int width, int height, int n_bands, int n,
     la.size_m0 = geom->display_size_m[0];
     la.size_m1 = geom->display_size_m[1];
     la.dist_m = geom->distance_m;
-    {   // as fill_band_args and fvvdp_ctx_set_csf_3d (fvvdp_hip.hip) derive them
-        const double delta = (1.0 / (double)geom->ppd_centre) / 2.0 * M_PI / 180.0;
-        la.delta_rad = (float)delta;
-        la.cos_delta = (float)cos(delta);
-        const float* ya = h_axes;
-        const float* ra = h_axes + FVVDP_LUT_N;
-        const float* ea = h_axes + 2 * FVVDP_LUT_N;
-        la.ly_lo = log2f(exp2f(ya[0]));
-        la.ly_hi = log2f(exp2f(ya[FVVDP_LUT_N - 1]));
-        la.rho_lo = exp2f(ra[0]);
-        la.rho_hi = exp2f(ra[FVVDP_LUT_N - 1]);
-        la.ecc_lo = ea[0] * ea[0];
-        la.ecc_hi = ea[FVVDP_LUT_N - 1] * ea[FVVDP_LUT_N - 1];
+    {   // the constants the forward's kernels take (fill_band_args, fvvdp_ctx_set_csf_3d in fvvdp_hip.hip)
+        const FovAxes fx = fov_axes(h_axes, geom);
+        la.delta_rad = fx.delta_rad;
+        la.cos_delta = fx.cos_delta;
+        // log2f of the float that exp2f of the knot rounds to, not the knot itself: the value the forward forms from its y_lo / y_hi
+        la.ly_lo = log2f(fx.y_lo);
+        la.ly_hi = log2f(fx.y_hi);
+        la.rho_lo = fx.rho_lo;
+        la.rho_hi = fx.rho_hi;
+        la.ecc_lo = fx.ecc_lo;
+        la.ecc_hi = fx.ecc_hi;
         for (int ax = 0; ax < 3; ++ax) {
-            la.first[ax] = h_axes[ax * FVVDP_LUT_N];
-            la.inv_step[ax] = (float)(FVVDP_LUT_N - 1) / (h_axes[ax * FVVDP_LUT_N + FVVDP_LUT_N - 1] - h_axes[ax * FVVDP_LUT_N]);
+            la.first[ax] = fx.first[ax];
+            la.inv_step[ax] = fx.inv_step[ax];
         }
     }
     const int cap = group_max ? group_max : FVVDP_GAZE_GROUP_MAX;      // smaller groups, more launches: same bits (tests, A/B runs)

@@ -3,7 +3,7 @@
 
 - the reference is `orc.Oracle(display, geometry=..., foveated=True, dtype=np.float64)` with `capture`, called per frame through
   `process_frame` on planar [P,H,W] input, and `orc.gausspyr_reduce(..., np.float64)` for the Gaussian levels;
-- `band_strips` / `chunking` restate the host's work decomposition (fvvdp_hip.hip) so that a test can say, without a GPU, which
+- `band_strips` / `chunking` restate the host's work decomposition (pyramid_host.hpp) so that a test can say, without a GPU, which
   loop phases of band_item a shape reaches, and `parse_plans` reads the FVVDP_DEBUG_VARIANT line of every one-level launch."""
 import functools
 import re
@@ -14,7 +14,7 @@ from oracle import fvvdp_oracle as orc
 
 F64 = np.float64
 N_FRAMES = 5
-STRIP_J = 60                      # coarse columns a strip advances by (band_kernel.hpp)
+STRIP_J = 60                      # coarse columns a strip advances by (pyramid_constants.hpp)
 WAVE_CAPACITY = 4096              # 16 resident single-wave workgroups x 256 CUs (MI355X); fewer on any smaller part
 
 # (H, W): the smallest shapes with an interior strip at level 0 (wc >= 123): 3, 3, 3, 4 and 5 strips, both parities of H and W
@@ -29,7 +29,7 @@ CUSTOM_GEOM = dict(distance_m=0.5, fov_diagonal=15.0)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# plan restatement (fvvdp_hip.hip: band_strips, chunking, fill_band_args)
+# plan restatement (pyramid_host.hpp: band_strips, chunking; fvvdp_hip.hip: fill_band_args)
 # ------------------------------------------------------------------------------------------------------------------------------
 def band_strips(wc):
     return 1 if wc <= 62 else 1 + (wc - 62 + STRIP_J - 1) // STRIP_J

@@ -38,12 +38,14 @@ def test_helper_is_the_float64_oracle():
 
 def test_restated_plan_matches_the_host_source():
     """The constants the restatement depends on, read from the sources it restates."""
-    with open(os.path.join(ROOT, "fovvideovdp_amd", "csrc", "band_kernel.hpp")) as f:
+    with open(os.path.join(ROOT, "fovvideovdp_amd", "csrc", "pyramid_constants.hpp")) as f:
         assert "constexpr int STRIP_J = %d;" % fr.STRIP_J in f.read()
+    with open(os.path.join(ROOT, "fovvideovdp_amd", "csrc", "pyramid_host.hpp")) as f:
+        plans = f.read()
+    assert "return wc <= 62 ? 1 : 1 + (wc - 62 + STRIP_J - 1) / STRIP_J;" in plans
+    assert "const double cost = (double)rounds * ((double)c + 8.0) * (1.0 + 1e-4 * (double)chunks);" in plans
     with open(os.path.join(ROOT, "fovvideovdp_amd", "csrc", "fvvdp_hip.hip")) as f:
         src = f.read()
-    assert "return wc <= 62 ? 1 : 1 + (wc - 62 + STRIP_J - 1) / STRIP_J;" in src
-    assert "const double cost = (double)rounds * ((double)c + 8.0) * (1.0 + 1e-4 * (double)chunks);" in src
     assert "long long wave_capacity = %d;" % fr.WAVE_CAPACITY in src
     assert 'num("FVVDP_BAND_CR", 0)' in src
 

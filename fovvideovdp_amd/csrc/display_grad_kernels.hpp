@@ -16,44 +16,13 @@
 // order, one partial per workgroup.  No atomics: the result repeats bit for bit.
 #pragma once
 
-#define DS_MAX_FL 64
 #define DS_MAX_PAIRS 128                // pointer-table entries of one display_image_sums_kernel launch
 #define DS_SUMS FVVDP_DISPLAY_SUMS
 #define DS_CHAIN 16                     // most fp32 terms a sum takes before it moves to fp64
 
-template <int PX>
-struct DsVec {
-    float v[PX];
-};
-// a lane past the frame reads nothing and carries zeros: it stays for the shuffles and the barrier of the reduction
-template <int PX>
-__device__ __forceinline__ DsVec<PX> ds_load(const float* p, bool live) {
-    DsVec<PX> r;
-#pragma unroll
-    for (int i = 0; i < PX; ++i) r.v[i] = 0.0f;
-    if (live) {
-        if constexpr (PX == 4) {
-            const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-            r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-        } else if constexpr (PX == 2) {
-            const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(p));
-            r.v[0] = t.x; r.v[1] = t.y;
-        } else {
-            r.v[0] = __builtin_nontemporal_load(p);
-        }
-    }
-    return r;
-}
-template <int PX>
-__device__ __forceinline__ void ds_store(float* p, const DsVec<PX>& r) {
-    if constexpr (PX == 4) __builtin_nontemporal_store(v4f{r.v[0], r.v[1], r.v[2], r.v[3]}, reinterpret_cast<v4f*>(p));
-    else if constexpr (PX == 2) __builtin_nontemporal_store(v2f{r.v[0], r.v[1]}, reinterpret_cast<v2f*>(p));
-    else __builtin_nontemporal_store(r.v[0], p);
-}
-
 // s w_c {1, a1(V), a2(V)} of the PX pixels x C channels of one frame: one fp32 chain of PX C <= 12 terms per sum, then fp64
 template <int PX>
-__device__ __forceinline__ void ds_accumulate(const DsVec<PX>& s, const DsVec<PX> (&V)[3], int C, const EotfDev& e,
+__device__ __forceinline__ void ds_accumulate(const LaneVec<PX>& s, const LaneVec<PX> (&V)[3], int C, const EotfDev& e,
                                               const float (&wgt)[3], double (&sum)[DS_SUMS]) {
     static_assert(PX * 3 <= DS_CHAIN, "a frame's terms are one fp32 chain");
     float acc[DS_SUMS] = {0.0f, 0.0f, 0.0f};
@@ -94,92 +63,41 @@ __device__ __forceinline__ void ds_block_reduce(const double (&sum)[DS_SUMS], do
 
 // ---- video: temporal transpose + the three products ------------------------------------------------------------------------
 struct DisplayVideoSumsArgs {
-    const float* g0;        // [N][2][HW]
+    TransposeArgs t;        // g0, head, sizes, taps and fold list
     const float* src;       // element (c, f, px) at c * chan_stride + f * frame_stride + px
-    float* head;            // [fl][HW]
     double* partial;        // [gridDim.x][DS_SUMS]
     size_t chan_stride, frame_stride;
-    int C, HW, N, fl;
+    int C;
     EotfDev e;
     float wgt[3];
-    float tapsT[DS_MAX_FL][2];      // {sustained, transient} tap of ring slot m
-    int fold_frame[DS_MAX_FL];      // [fl] sorted; padded with -1
-    int fold_pos[DS_MAX_FL];
 };
+static_assert(offsetof(DisplayVideoSumsArgs, t) == 0, "transpose_step and FoldCursor read the start of the kernel-argument segment");
 
-// FL: ring slots (fl rounded up to 8 / 16 / 32 / 64).  PX: pixels per lane (4 or 2: HW and the strides are multiples of PX and
-// the pointers PX-float aligned, so a lane's pixels are all inside the frame or all outside; 1: any size).  The walk over the
-// window positions is video_input_kernel's, statement for statement (see the comment there): s of frame j is the same value.
+// FL, PX: see TransposeRing.  The transpose of transpose_kernels.hpp, so s of frame j is the value video_input_kernel forms; a
+// lane past the frame reads nothing, carries zeros and stays for the shuffles and the barrier of the reduction.
 template <int FL, int PX>
 __global__ __launch_bounds__(256) void display_video_sums_kernel(const DisplayVideoSumsArgs a) {
     const size_t px = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
-    const bool live = px < (size_t)a.HW;
-    typedef const int __attribute__((address_space(4)))* karg_int_p;
-    typedef const char __attribute__((address_space(4)))* karg_p;
-    const karg_p ka = (karg_p)__builtin_amdgcn_kernarg_segment_ptr();
-    const karg_int_p fold_frame = (karg_int_p)(ka + offsetof(DisplayVideoSumsArgs, fold_frame));
-    const karg_int_p fold_pos = (karg_int_p)(ka + offsetof(DisplayVideoSumsArgs, fold_pos));
-    float ring[FL - 1][PX];                     // before step p: slot m = position p + m
-#pragma unroll
-    for (int m = 0; m < FL - 1; ++m)
-#pragma unroll
-        for (int i = 0; i < PX; ++i) ring[m][i] = 0.0f;
+    const bool live = px < (size_t)a.t.HW;
+    TransposeRing<FL, PX> ring = transpose_ring<FL, PX>();
     double sum[DS_SUMS] = {0.0, 0.0, 0.0};
-    int cur = 0;                                // cursor in the fold list (wave-uniform)
-    const int total = a.N + a.fl - 1;
-    const size_t HW = (size_t)a.HW;
+    const size_t HW = (size_t)a.t.HW;
+    FoldCursor<PX> fold(a.t.head, HW, px, a.t.fl, live);
+    const int total = a.t.N + a.t.fl - 1;
     for (int p = 0; p < total; ++p) {
-        const int j = p - (a.fl - 1);           // the frame that is complete after this step
-        const bool in = live && p < a.N;        // past the last output frame the open positions only drain
-        const DsVec<PX> gs = ds_load<PX>(a.g0 + (size_t)p * 2 * HW + px, in);
-        const DsVec<PX> gt = ds_load<PX>(a.g0 + ((size_t)p * 2 + 1) * HW + px, in);
-        DsVec<PX> V[3];                         // the samples of frame j, requested before the arithmetic
+        const int j = p - (a.t.fl - 1);         // the frame that is complete after this step
+        LaneVec<PX> gs, gt;
+        transpose_inputs<PX>(a.t.g0, p, a.t.N, HW, px, gs, gt, live);
+        LaneVec<PX> V[3];                       // the samples of frame j, requested before the arithmetic
         if (j >= 0) {
             const float* t = a.src + (size_t)j * a.frame_stride + px;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                if (c < a.C) V[c] = ds_load<PX>(t + (size_t)c * a.chan_stride, live);
+                if (c < a.C) V[c] = lane_load<PX>(t + (size_t)c * a.chan_stride, live);
         }
-        karg_p tp = ka + offsetof(DisplayVideoSumsArgs, tapsT);
-        if constexpr (FL > 8) asm volatile("" : "+s"(tp));
-        DsVec<PX> done;                         // position p
-#pragma unroll
-        for (int c = 0; c < FL / TAPC; ++c) {
-            karg_p tpc = tp + c * (8 * TAPC);
-            if constexpr (FL > 16) asm volatile("" : "+s"(tpc));
-            const vtapf tc = *(karg_taps_p)tpc;
-#pragma unroll
-            for (int kk = 0; kk < TAPC; ++kk) {
-                const int m = c * TAPC + kk;
-                const float fs = tc[2 * kk], ft = tc[2 * kk + 1];
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    const float old = m < FL - 1 ? ring[m][i] : 0.0f;
-                    float v = fmaf(fs, gs.v[i], fmaf(ft, gt.v[i], old));
-                    asm volatile("" : "+v"(v));
-                    if (m == 0) done.v[i] = v;
-                    else ring[m - 1][i] = v;
-                }
-            }
-            if constexpr (FL > 8) __builtin_amdgcn_sched_barrier(0);
-        }
-        if (p < a.fl && live) ds_store<PX>(a.head + (size_t)p * HW + px, done);
-        if (j >= 0) {
-            DsVec<PX> s;
-#pragma unroll
-            for (int i = 0; i < PX; ++i) s.v[i] = 0.0f;
-            while (cur < a.fl && fold_frame[cur] == j) {
-                const DsVec<PX> hd = ds_load<PX>(a.head + (size_t)fold_pos[cur] * HW + px, live);
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += hd.v[i];
-                ++cur;
-            }
-            if (j >= 1) {
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += done.v[i];
-            }
-            ds_accumulate<PX>(s, V, a.C, a.e, a.wgt, sum);
-        }
+        const LaneVec<PX> done = transpose_step<FL, PX>(ring, gs, gt);
+        if (p < a.t.fl && live) lane_store<PX>(a.t.head + (size_t)p * HW + px, done);
+        if (j >= 0) ds_accumulate<PX>(fold.frame_sum(j, done), V, a.C, a.e, a.wgt, sum);
     }
     ds_block_reduce(sum, a.partial + (size_t)blockIdx.x * DS_SUMS);
 }
@@ -205,7 +123,7 @@ __global__ __launch_bounds__(256) void display_image_sums_kernel(const DisplayIm
     double sum[DS_SUMS] = {0.0, 0.0, 0.0};
     if (live) {
         const int y = (int)(px / (size_t)a.w), x = (int)(px - (size_t)y * a.w);
-        DsVec<1> s, V[3];
+        LaneVec<1> s, V[3];
         s.v[0] = a.GL0[(size_t)k * hw + px] + reduce_t(a.GG1 + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
         const float* img = a.img[k];
 #pragma unroll

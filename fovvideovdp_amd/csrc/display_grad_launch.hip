@@ -15,10 +15,11 @@
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"
 #include "grad_common.hpp"
+#include "transpose_kernels.hpp"
 #include "display_grad_kernels.hpp"
 #include "grad_host.hpp"
 
-static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == DS_MAX_FL, "the ring reaches as far as the video backward's");
+static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == TRANSPOSE_MAX_FL, "the ring reaches as far as the video backward's");
 
 // the five parameters exist for fvvdp_display_photo_eotf's four models only
 static int check_display_model(const fvvdp_eotf* eotf) {
@@ -63,8 +64,8 @@ extern "C" int fvvdp_video_display_sums_workspace(int width, int height, size_t*
 
 template <int FL>
 static int launch_video_sums(const DisplayVideoSumsArgs& a, bool vec, hipStream_t st) {
-    constexpr int PXV = FL <= 16 ? 4 : 2;          // pixels per lane of the vector variant: the ring is FL x PX registers
-    const size_t HW = (size_t)a.HW;
+    constexpr int PXV = transpose_px(FL);
+    const size_t HW = (size_t)a.t.HW;
     const int blocks = (int)(((vec ? HW / PXV : HW) + 255) / 256);
     if (vec) hipLaunchKernelGGL((display_video_sums_kernel<FL, PXV>), dim3(blocks), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((display_video_sums_kernel<FL, 1>), dim3(blocks), dim3(256), 0, st, a);
@@ -89,18 +90,8 @@ extern "C" int fvvdp_video_display_sums(int width, int height, int n_frames, con
     if (frame_stride < HW) return grad_fail(FVVDP_EINVAL, "frame_stride %zu is below the frame size %zu", frame_stride, HW);
     if (C == 3 && chan_stride < HW) return grad_fail(FVVDP_EINVAL, "chan_stride %zu is below the frame size %zu", chan_stride, HW);
     GRAD_CHECK(check_display_model(eotf));
-    // the fold list: every head position exactly once, frames inside the clip, sorted by frame and then by position
-    bool seen[DS_MAX_FL] = {false};
-    for (int i = 0; i < fl; ++i) {
-        const int f = h_fold_frame[i], p = h_fold_pos[i];
-        if (f < 0 || f >= n_frames) return grad_fail(FVVDP_EINVAL, "fold list entry %d names frame %d outside [0, %d)", i, f, n_frames);
-        if (p < 0 || p >= fl || seen[p]) return grad_fail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
-        seen[p] = true;
-        if (i > 0 && (f < h_fold_frame[i - 1] || (f == h_fold_frame[i - 1] && p < h_fold_pos[i - 1])))
-            return grad_fail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
-    }
-    if (head_bytes < (size_t)fl * HW * sizeof(float))
-        return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
+    GRAD_CHECK(grad_verdict(transpose_check_fold(h_fold_frame, h_fold_pos, fl, n_frames, "frame")));
+    GRAD_CHECK(grad_verdict(transpose_check_head_bytes(head_bytes, fl, HW)));
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_head);
     if (ptrs % 4 != 0) return grad_fail(FVVDP_EINVAL, "device pointers must be aligned to 4 bytes");
     GRAD_CHECK(check_out_and_work(d_out, d_work, work_bytes, ((HW + 255) / 256) * DS_SUMS * sizeof(double)));
@@ -108,35 +99,17 @@ extern "C" int fvvdp_video_display_sums(int width, int height, int n_frames, con
 
     DisplayVideoSumsArgs a;
     memset(&a, 0, sizeof(a));
-    a.g0 = d_g0;
+    transpose_fill(a.t, d_g0, d_head, HW, n_frames, fl, h_taps, h_fold_frame, h_fold_pos);
     a.src = d_src;
-    a.head = d_head;
     a.partial = static_cast<double*>(d_work);
     a.chan_stride = C == 3 ? chan_stride : 0;
     a.frame_stride = frame_stride;
     a.C = C;
-    a.HW = (int)HW;
-    a.N = n_frames;
-    a.fl = fl;
     grad_fill_eotf(a.e, a.wgt, eotf, C, h_rgb2y);
-    for (int m = 0; m < fl; ++m) {                  // ring slot m of step p is position p + m: it receives tap fl - 1 - m
-        a.tapsT[m][0] = h_taps[fl - 1 - m];
-        a.tapsT[m][1] = h_taps[fl + fl - 1 - m];
-    }
-    for (int i = 0; i < DS_MAX_FL; ++i) {
-        a.fold_frame[i] = i < fl ? h_fold_frame[i] : -1;
-        a.fold_pos[i] = i < fl ? h_fold_pos[i] : 0;
-    }
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : (fl <= 32 ? 32 : 64));
-    const size_t pxv = FL <= 16 ? 4 : 2;
-    const bool vec = HW % pxv == 0 && frame_stride % pxv == 0 && a.chan_stride % pxv == 0 && ptrs % (4 * pxv) == 0;
+    const int FL = transpose_ring_length(fl, TRANSPOSE_MAX_FL);
+    const bool vec = transpose_vector_ok(FL, HW, frame_stride | a.chan_stride, ptrs);
     int blocks = 0;
-    switch (FL) {
-        case 8: blocks = launch_video_sums<8>(a, vec, st); break;
-        case 16: blocks = launch_video_sums<16>(a, vec, st); break;
-        case 32: blocks = launch_video_sums<32>(a, vec, st); break;
-        default: blocks = launch_video_sums<64>(a, vec, st); break;
-    }
+    transpose_dispatch<TRANSPOSE_MAX_FL>(FL, [&](auto c) { blocks = launch_video_sums<c.value>(a, vec, st); });
     GRAD_HIP_TRY(hipGetLastError());
     GRAD_HIP_TRY(finalize_launch(a.partial, d_out, 1, blocks, st));
     return FVVDP_OK;

@@ -10,6 +10,7 @@
 
 #include "grad_common.hpp"     // GradSweepArgs
 #include "ingest_host.hpp"     // the display block and the luminance weights
+#include "transpose_host.hpp"  // TransposeVerdict
 
 int fvvdp_fail_from(int code, const char* msg);      // fvvdp_hip.hip: sets the message of fvvdp_last_error
 // adj_sweep_kernel on `planes` planes of one level.  The kernel is defined in grad_launch.hip only, so is this function
@@ -24,6 +25,8 @@ static int grad_fail(int code, const char* fmt, ...) {
     va_end(ap);
     return fvvdp_fail_from(code, buf);
 }
+// the verdict of a check of transpose_host.hpp (host code without the library's message), for GRAD_CHECK
+static inline int grad_verdict(const TransposeVerdict& v) { return v.code == FVVDP_OK ? FVVDP_OK : grad_fail(v.code, "%s", v.msg); }
 
 #define GRAD_HIP_TRY(expr)                                                                                  \
     do {                                                                                                    \

@@ -15,8 +15,7 @@
 #include "device_common.hpp"
 #include "temporal_launch.hpp"
 #include "grad_common.hpp"
-#define VG_TRANSPOSE_ONLY          // VideoInputArgs, VgVec and their loads and stores; no kernel of the video backward
-#include "video_grad_kernels.hpp"
+#include "transpose_kernels.hpp"   // the shared transpose and VideoInputArgs; no kernel of the video backward
 #include "held_kernels.hpp"
 #include "grad_host.hpp"
 
@@ -67,7 +66,7 @@ void HELD_NAME(held_ingest)(int FL, bool vec, const HeldTemporalArgs& h, hipStre
 
 #if HELD_PART == 5
 static_assert(FVVDP_HELD_MAX_TAPS == 32, "ring lengths 8 / 16 / 32");
-static_assert(FVVDP_HELD_MAX_TAPS <= VG_MAX_FL, "VideoInputArgs::tapsT");
+static_assert(FVVDP_HELD_MAX_TAPS <= TRANSPOSE_MAX_FL, "TransposeArgs::tapsT");
 
 void held_ingest_u8(int, bool, const HeldTemporalArgs&, hipStream_t);
 void held_ingest_u16(int, bool, const HeldTemporalArgs&, hipStream_t);
@@ -163,18 +162,10 @@ extern "C" int fvvdp_temporal_channels_held(fvvdp_ctx* ctx, const fvvdp_held_str
 
 template <int FL, int ST>
 static void launch_input(const VideoInputHeldArgs& ia, bool vec, hipStream_t st) {
-    constexpr int PXV = FL <= 16 ? 4 : 2;          // video_input_kernel's rule: the ring is FL x PX registers
-    const size_t HW = (size_t)ia.a.HW;
+    constexpr int PXV = transpose_px(FL);
+    const size_t HW = (size_t)ia.a.t.HW;
     if (vec) hipLaunchKernelGGL((video_input_held_kernel<FL, PXV, ST>), dim3((unsigned int)((HW / PXV + 255) / 256)), dim3(256), 0, st, ia);
     else hipLaunchKernelGGL((video_input_held_kernel<FL, 1, ST>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
-}
-template <int ST>
-static void launch_input(int FL, const VideoInputHeldArgs& ia, bool vec, hipStream_t st) {
-    switch (FL) {
-        case 8: launch_input<8, ST>(ia, vec, st); break;
-        case 16: launch_input<16, ST>(ia, vec, st); break;
-        default: launch_input<32, ST>(ia, vec, st); break;
-    }
 }
 
 extern "C" int fvvdp_video_grad_input_held(int width, int height, int n_display, int n_source, const float* d_g0, const int32_t* h_map,
@@ -202,20 +193,10 @@ extern "C" int fvvdp_video_grad_input_held(int width, int height, int n_display,
         if (v > 0 && h_map[v] < h_map[v - 1])
             return grad_fail(FVVDP_EINVAL, "frame map must be non-decreasing (entry %d: %d after %d)", v, h_map[v], h_map[v - 1]);
     }
-    // the fold list: every head position exactly once, source frames inside the clip, sorted by frame and then by position
-    bool seen[FVVDP_HELD_MAX_TAPS] = {false};
-    for (int i = 0; i < fl; ++i) {
-        const int f = h_fold_frame[i], p = h_fold_pos[i];
-        if (f < 0 || f >= n_source) return grad_fail(FVVDP_EINVAL, "fold list entry %d names source frame %d outside [0, %d)", i, f, n_source);
-        if (p < 0 || p >= fl || seen[p]) return grad_fail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
-        seen[p] = true;
-        if (i > 0 && (f < h_fold_frame[i - 1] || (f == h_fold_frame[i - 1] && p < h_fold_pos[i - 1])))
-            return grad_fail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
-    }
+    GRAD_CHECK(grad_verdict(transpose_check_fold(h_fold_frame, h_fold_pos, fl, n_source, "source frame")));
     if (reinterpret_cast<uintptr_t>(d_head) % 256 != 0) return grad_fail(FVVDP_EINVAL, "side buffer must be 256-byte aligned");
     const size_t mb = FVVDP_HELD_MAP_BYTES(n_display);
-    if (head_bytes < mb + (size_t)fl * HW * sizeof(float))
-        return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, mb + (size_t)fl * HW * sizeof(float));
+    GRAD_CHECK(grad_verdict(transpose_check_head_bytes(head_bytes, fl, HW, mb)));
     const uintptr_t sptrs = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_grad);
     if (reinterpret_cast<uintptr_t>(d_g0) % 4 != 0 || sptrs % es != 0)
         return grad_fail(FVVDP_EINVAL, es == 4 ? "device pointers must be aligned to 4 bytes"
@@ -233,34 +214,24 @@ extern "C" int fvvdp_video_grad_input_held(int width, int height, int n_display,
     VideoInputHeldArgs ha;
     memset(&ha, 0, sizeof(ha));
     VideoInputArgs& ia = ha.a;
-    ia.g0 = d_g0;
+    transpose_fill(ia.t, d_g0, reinterpret_cast<float*>(static_cast<char*>(d_head) + mb), HW, n_display, fl, h_taps, h_fold_frame,
+                   h_fold_pos);
     ia.test = static_cast<const float*>(d_src);       // (16-bit samples: the kernel reads and writes them as such)
     ia.grad = static_cast<float*>(d_grad);
-    ia.head = reinterpret_cast<float*>(static_cast<char*>(d_head) + mb);
     ia.chan_stride = C == 3 ? chan_stride : 0;
     ia.frame_stride = frame_stride;
     ia.C = C;
-    ia.HW = (int)HW;
-    ia.N = n_display;
-    ia.fl = fl;
     grad_fill_eotf(ia.e, ia.wgt, eotf, C, h_rgb2y);
-    for (int m = 0; m < fl; ++m) {                  // ring slot m of step p is position p + m: it receives tap fl - 1 - m
-        ia.tapsT[m][0] = h_taps[fl - 1 - m];
-        ia.tapsT[m][1] = h_taps[fl + fl - 1 - m];
-    }
-    for (int i = 0; i < VG_MAX_FL; ++i) {
-        ia.fold_frame[i] = i < fl ? h_fold_frame[i] : -1;
-        ia.fold_pos[i] = i < fl ? h_fold_pos[i] : 0;
-    }
     ha.map = static_cast<const int*>(d_head);
     ha.n_source = n_source;
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : 32);
-    const size_t pxv = FL <= 16 ? 4 : 2;
-    const bool vec = HW % pxv == 0 && frame_stride % pxv == 0 && ia.chan_stride % pxv == 0 &&
-                     reinterpret_cast<uintptr_t>(d_g0) % (4 * pxv) == 0 && sptrs % (es * pxv) == 0;
-    if (dtype == FVVDP_F16) launch_input<SRC_F16>(FL, ha, vec, st);
-    else if (dtype == FVVDP_BF16) launch_input<SRC_BF16>(FL, ha, vec, st);
-    else launch_input<SRC_F32>(FL, ha, vec, st);
+    const int FL = transpose_ring_length(fl, FVVDP_HELD_MAX_TAPS);
+    // (the side buffer is 256-byte aligned and the map in front of it a multiple of 256 bytes)
+    const bool vec = transpose_vector_ok(FL, HW, frame_stride | ia.chan_stride, reinterpret_cast<uintptr_t>(d_g0), sptrs, es);
+    transpose_dispatch<FVVDP_HELD_MAX_TAPS>(FL, [&](auto c) {
+        if (dtype == FVVDP_F16) launch_input<c.value, SRC_F16>(ha, vec, st);
+        else if (dtype == FVVDP_BF16) launch_input<c.value, SRC_BF16>(ha, vec, st);
+        else launch_input<c.value, SRC_F32>(ha, vec, st);
+    });
     GRAD_HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }

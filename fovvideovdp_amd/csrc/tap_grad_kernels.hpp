@@ -30,42 +30,22 @@ struct TapGradArgs {
     int pos[TG_MAX_POS];    // [fl - 1 + n] luminance frame of every list entry
 };
 
-template <int PX>
-struct TgVec {
-    float v[PX];
-};
-template <int PX>
-__device__ __forceinline__ TgVec<PX> tg_load(const float* p, bool live) {
-    TgVec<PX> r;
-#pragma unroll
-    for (int i = 0; i < PX; ++i) r.v[i] = 0.0f;
-    if (live) {
-        if constexpr (PX == 4) {
-            const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-            r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-        } else {
-            r.v[0] = __builtin_nontemporal_load(p);
-        }
-    }
-    return r;
-}
-
 // what one output frame brings: the newest luminance sample of both clips and the four gradient planes
 template <int PX>
 struct TgStep {
-    TgVec<PX> vt, vr, gs, gt, hs, ht;
+    LaneVec<PX> vt, vr, gs, gt, hs, ht;
 };
 template <int PX, class POS>
 __device__ __forceinline__ TgStep<PX> tg_step(const TapGradArgs& a, POS pos, int q0, int t, size_t HW, size_t px, bool live) {
     TgStep<PX> s;
     const size_t o = (size_t)pos[q0 + t] * HW + px;
     const size_t og = (size_t)t * 2 * HW + px;
-    s.vt = tg_load<PX>(a.yt + o, live);
-    s.vr = tg_load<PX>(a.yr + o, live);
-    s.gs = tg_load<PX>(a.g0 + og, live);
-    s.gt = tg_load<PX>(a.g0 + og + HW, live);
-    s.hs = tg_load<PX>(a.g0r + og, live);
-    s.ht = tg_load<PX>(a.g0r + og + HW, live);
+    s.vt = lane_load<PX>(a.yt + o, live);
+    s.vr = lane_load<PX>(a.yr + o, live);
+    s.gs = lane_load<PX>(a.g0 + og, live);
+    s.gt = lane_load<PX>(a.g0 + og + HW, live);
+    s.hs = lane_load<PX>(a.g0r + og, live);
+    s.ht = lane_load<PX>(a.g0r + og + HW, live);
     return s;
 }
 
@@ -89,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void tap_grad_kernel(const TapGradArgs a) {
         const int q = q0 - m;
         const bool in = live && q >= 0;
         const size_t o = in ? (size_t)pos[q >= 0 ? q : 0] * HW + px : 0;
-        const TgVec<PX> vt = tg_load<PX>(a.yt + o, in), vr = tg_load<PX>(a.yr + o, in);
+        const LaneVec<PX> vt = lane_load<PX>(a.yt + o, in), vr = lane_load<PX>(a.yr + o, in);
 #pragma unroll
         for (int i = 0; i < PX; ++i) { rt[R - m][i] = vt.v[i]; rr[R - m][i] = vr.v[i]; }
     }

@@ -15,6 +15,7 @@
 #include "fvvdp_hip_taps.h"
 #include "device_common.hpp"
 #include "temporal_launch.hpp"
+#include "transpose_kernels.hpp"   // LaneVec
 #include "tap_grad_kernels.hpp"
 
 int fvvdp_fail_from(int code, const char* msg);      // fvvdp_hip.hip: sets the message of fvvdp_last_error

@@ -15,7 +15,6 @@
 //   video_input_kernel   dtest_c[j]   = w_c EOTF'(V_c[j]) sum_{p : idx[p] = j} A[p],  A[p] = sum_cc sum_k taps[cc][k] g0[p-(fl-1)+k][cc]
 #pragma once
 
-#ifndef VG_TRANSPOSE_ONLY      // (held_launch.hip takes the pieces of the temporal transpose below and none of these kernels)
 // ---- coefficients ---------------------------------------------------------------------------------------------------------
 struct VideoCoefArgs {
     const float* Q;         // Q_per_ch of the forward, [n_bands][2][N]
@@ -145,179 +144,46 @@ __global__ __launch_bounds__(256) void video_level0_kernel(const VideoLevel0Args
     a.g0[o] = a.GL0[o] + reduce_t(a.GG1 + (size_t)k * a.wc * a.hc, a.wc, a.hc, a.w, a.h, y, x);
 }
 
-#endif  // VG_TRANSPOSE_ONLY
-
 // ---- temporal transpose + display model: the mirror image of temporal_vec_kernel ---------------------------------------------
-// A lane owns PX consecutive pixels for the whole launch and walks the window-list positions p = 0 .. N + fl - 2 once.  Position
-// p collects taps[cc][k] g0[t][cc] from the output frames t = p - (fl - 1) + k, i.e. step t adds to the positions t .. t + fl - 1;
-// after step p nothing more arrives at position p.  The fl open positions live in a register ring that SHIFTS by one slot
-// per step: slot m holds position p + m, and the shift is free because the multiply-add that adds step p's term to slot m
-// writes its result to slot m - 1 (three-operand FMA) -- the loop over p is a plain loop, nothing is unrolled over time, and
-// the code stays small whatever FL.  tapsT[m] = taps[.][fl - 1 - m] (zero for m >= fl) is the tap slot m receives.
-// A finished position p < fl belongs to the head (the frames the temporal padding shows before frame 0): it goes to the side
-// buffer head[p]; a finished position p >= fl is the one streaming term of frame p - fl + 1.  Frame j = p - (fl - 1) is
-// complete after step p: its head positions (fold list: sorted by frame, then position -- a cursor walks it) are added in
-// ascending order, then the streaming term, then the display model's derivative -- a fixed order, no atomics.  A frame no
-// window shows (circular padding, N > fl: frame 0) sums nothing and gets exact zeros.
-#define VG_MAX_FL 64
-struct VideoInputArgs {
-    const float* g0;        // [N][2][HW]
-    const float* test;      // element (c, f, px) at c * chan_stride + f * frame_stride + px
-    float* grad;            // the same layout
-    float* head;            // [fl][HW]
-    size_t chan_stride, frame_stride;
-    int C, HW, N, fl;
-    EotfDev e;
-    float wgt[3];
-    float tapsT[VG_MAX_FL][2];      // {sustained, transient} tap of ring slot m
-    int fold_frame[VG_MAX_FL];      // [fl] sorted; padded with -1
-    int fold_pos[VG_MAX_FL];
-};
-
-template <int PX>
-struct VgVec {
-    float v[PX];
-};
-template <int PX>
-__device__ __forceinline__ VgVec<PX> vg_load(const float* p) {
-    VgVec<PX> r;
-    if constexpr (PX == 4) {
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else if constexpr (PX == 2) {
-        const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(p));
-        r.v[0] = t.x; r.v[1] = t.y;
-    } else {
-        r.v[0] = __builtin_nontemporal_load(p);
-    }
-    return r;
-}
-template <int PX>
-__device__ __forceinline__ void vg_store(float* p, const VgVec<PX>& r) {
-    if constexpr (PX == 4) __builtin_nontemporal_store(v4f{r.v[0], r.v[1], r.v[2], r.v[3]}, reinterpret_cast<v4f*>(p));
-    else if constexpr (PX == 2) __builtin_nontemporal_store(v2f{r.v[0], r.v[1]}, reinterpret_cast<v2f*>(p));
-    else __builtin_nontemporal_store(r.v[0], p);
-}
-
-// 16-bit forms for float16 / bfloat16 samples (ST = SRC_F16 / SRC_BF16): PX samples are 8 / 4 / 2 bytes, widened exactly on the
-// way in and rounded once (to nearest even, float16 subnormals kept) on the way out; the same non-temporal hints
-template <int PX, int ST>
-__device__ __forceinline__ VgVec<PX> vg_load16(const unsigned short* p) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    VgVec<PX> r;
-    if constexpr (PX == 4) {
-        const u2v t = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(p));
-        r.v[0] = half_widen<ST>(t.x); r.v[1] = half_widen<ST>(t.x >> 16); r.v[2] = half_widen<ST>(t.y); r.v[3] = half_widen<ST>(t.y >> 16);
-    } else if constexpr (PX == 2) {
-        const unsigned int t = __builtin_nontemporal_load(reinterpret_cast<const unsigned int*>(p));
-        r.v[0] = half_widen<ST>(t); r.v[1] = half_widen<ST>(t >> 16);
-    } else {
-        r.v[0] = half_widen<ST>(__builtin_nontemporal_load(p));
-    }
-    return r;
-}
-template <int PX, int ST>
-__device__ __forceinline__ void vg_store16(unsigned short* p, const VgVec<PX>& r) {
-    typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-    unsigned int h[PX];
-#pragma unroll
-    for (int i = 0; i < PX; ++i) h[i] = half_narrow<ST>(r.v[i]);
-    if constexpr (PX == 4) __builtin_nontemporal_store(u2v{h[0] | (h[1] << 16), h[2] | (h[3] << 16)}, reinterpret_cast<u2v*>(p));
-    else if constexpr (PX == 2) __builtin_nontemporal_store(h[0] | (h[1] << 16), reinterpret_cast<unsigned int*>(p));
-    else __builtin_nontemporal_store((unsigned short)h[0], p);
-}
-
-// FL: ring slots (fl rounded up to 8 / 16 / 32 / 64).  PX: pixels per lane (4 or 2: HW and the strides are multiples of PX and
-// the pointers PX-float aligned; 1: any size).  ST: the type of the caller's samples and gradient (SRC_F32; SRC_F16 / SRC_BF16:
-// `test` and `grad` point at 16-bit samples, PX-sample aligned); g0, head and all arithmetic are fp32 whatever ST.
+// The transpose of transpose_kernels.hpp (the walk, the ring, the head side buffer and the fold cursor are described there) with
+// the display model's derivative as its tail: grad_c[j] = w_c EOTF'(V_c[j]) s[j] (VideoInputArgs is defined there as well).
+// FL, PX: see TransposeRing.  ST: the type of the caller's samples and gradient (SRC_F32; SRC_F16 / SRC_BF16: `test` and `grad`
+// point at 16-bit samples, PX-sample aligned); g0, head and all arithmetic are fp32 whatever ST.
 template <int FL, int PX, int ST>
 __device__ __forceinline__ void video_input_body(const VideoInputArgs a) {
     const size_t px = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
-    if (px >= (size_t)a.HW) return;
-    // fold list and (long rings) taps straight from the kernel-argument segment: scalar loads, no copy of the block to scratch
-    typedef const int __attribute__((address_space(4)))* karg_int_p;
-    typedef const char __attribute__((address_space(4)))* karg_p;
-    const karg_p ka = (karg_p)__builtin_amdgcn_kernarg_segment_ptr();
-    const karg_int_p fold_frame = (karg_int_p)(ka + offsetof(VideoInputArgs, fold_frame));
-    const karg_int_p fold_pos = (karg_int_p)(ka + offsetof(VideoInputArgs, fold_pos));
-    float ring[FL - 1][PX];                     // before step p: slot m = position p + m (slot FL - 1 is still empty: not kept)
-#pragma unroll
-    for (int m = 0; m < FL - 1; ++m)
-#pragma unroll
-        for (int i = 0; i < PX; ++i) ring[m][i] = 0.0f;
-    int cur = 0;                                // cursor in the fold list (wave-uniform)
-    const int total = a.N + a.fl - 1;
-    const size_t HW = (size_t)a.HW;
+    if (px >= (size_t)a.t.HW) return;
+    TransposeRing<FL, PX> ring = transpose_ring<FL, PX>();
+    const size_t HW = (size_t)a.t.HW;
+    FoldCursor<PX> fold(a.t.head, HW, px, a.t.fl);
+    const int total = a.t.N + a.t.fl - 1;
     for (int p = 0; p < total; ++p) {
-        const int j = p - (a.fl - 1);           // the frame that is complete after this step
-        VgVec<PX> gs, gt;
-        if (p < a.N) {
-            gs = vg_load<PX>(a.g0 + (size_t)p * 2 * HW + px);
-            gt = vg_load<PX>(a.g0 + ((size_t)p * 2 + 1) * HW + px);
-        } else {                                // past the last output frame: the open positions only drain
-#pragma unroll
-            for (int i = 0; i < PX; ++i) gs.v[i] = gt.v[i] = 0.0f;
-        }
-        VgVec<PX> V[3];                         // the test samples of frame j, requested before the arithmetic
+        const int j = p - (a.t.fl - 1);         // the frame that is complete after this step
+        LaneVec<PX> gs, gt;
+        transpose_inputs<PX>(a.t.g0, p, a.t.N, HW, px, gs, gt);
+        LaneVec<PX> V[3];                       // the test samples of frame j, requested before the arithmetic
         if (j >= 0) {
             const size_t t = (size_t)j * a.frame_stride + px;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
                 if (c < a.C) {
-                    if constexpr (ST == SRC_F32) V[c] = vg_load<PX>(a.test + t + (size_t)c * a.chan_stride);
-                    else V[c] = vg_load16<PX, ST>(reinterpret_cast<const unsigned short*>(a.test) + t + (size_t)c * a.chan_stride);
+                    if constexpr (ST == SRC_F32) V[c] = lane_load<PX>(a.test + t + (size_t)c * a.chan_stride);
+                    else V[c] = lane_load16<PX, ST>(reinterpret_cast<const unsigned short*>(a.test) + t + (size_t)c * a.chan_stride);
                 }
         }
-        // taps: long rings re-read them in every step, TAPC at a time through a laundered pointer -- hoisted out of the loop,
-        // 2 FL scalar values would stay alive and spill (see temporal_ring_kernel)
-        karg_p tp = ka + offsetof(VideoInputArgs, tapsT);
-        if constexpr (FL > 8) asm volatile("" : "+s"(tp));
-        VgVec<PX> done;                         // position p
-#pragma unroll
-        for (int c = 0; c < FL / TAPC; ++c) {
-            karg_p tpc = tp + c * (8 * TAPC);
-            if constexpr (FL > 16) asm volatile("" : "+s"(tpc));       // (else the chunks' loads are merged back into one)
-            const vtapf tc = *(karg_taps_p)tpc;
-#pragma unroll
-            for (int kk = 0; kk < TAPC; ++kk) {
-                const int m = c * TAPC + kk;
-                const float fs = tc[2 * kk], ft = tc[2 * kk + 1];
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    const float old = m < FL - 1 ? ring[m][i] : 0.0f;
-                    float v = fmaf(fs, gs.v[i], fmaf(ft, gt.v[i], old));
-                    asm volatile("" : "+v"(v));             // pinned where it is produced: left alone, the compiler sinks the ring
-                                                            // updates below the branches that follow and keeps every tap alive
-                    if (m == 0) done.v[i] = v;              // position p: nothing more arrives
-                    else ring[m - 1][i] = v;                // the shift: slot m becomes slot m - 1 of the next step
-                }
-            }
-            if constexpr (FL > 8) __builtin_amdgcn_sched_barrier(0);      // one chunk of taps in scalar registers at a time
-        }
-        if (p < a.fl) vg_store<PX>(a.head + (size_t)p * HW + px, done);
+        const LaneVec<PX> done = transpose_step<FL, PX>(ring, gs, gt);
+        if (p < a.t.fl) lane_store<PX>(a.t.head + (size_t)p * HW + px, done);
         if (j >= 0) {
-            VgVec<PX> s;
-#pragma unroll
-            for (int i = 0; i < PX; ++i) s.v[i] = 0.0f;
-            while (cur < a.fl && fold_frame[cur] == j) {
-                const VgVec<PX> hd = vg_load<PX>(a.head + (size_t)fold_pos[cur] * HW + px);
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += hd.v[i];
-                ++cur;
-            }
-            if (j >= 1) {
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += done.v[i];
-            }
+            const LaneVec<PX> s = fold.frame_sum(j, done);
             const size_t o = (size_t)j * a.frame_stride + px;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 if (c < a.C) {
-                    VgVec<PX> r;
+                    LaneVec<PX> r;
 #pragma unroll
                     for (int i = 0; i < PX; ++i) r.v[i] = a.wgt[c] * eotf_grad(V[c].v[i], a.e) * s.v[i];
-                    if constexpr (ST == SRC_F32) vg_store<PX>(a.grad + o + (size_t)c * a.chan_stride, r);
-                    else vg_store16<PX, ST>(reinterpret_cast<unsigned short*>(a.grad) + o + (size_t)c * a.chan_stride, r);
+                    if constexpr (ST == SRC_F32) lane_store<PX>(a.grad + o + (size_t)c * a.chan_stride, r);
+                    else lane_store16<PX, ST>(reinterpret_cast<unsigned short*>(a.grad) + o + (size_t)c * a.chan_stride, r);
                 }
             }
         }

@@ -13,10 +13,11 @@
 #include "device_common.hpp"
 #include "temporal_kernels.hpp"
 #include "grad_common.hpp"
+#include "transpose_kernels.hpp"
 #include "video_grad_kernels.hpp"
 #include "grad_host.hpp"
 
-static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == VG_MAX_FL, "the header states the ring's reach");
+static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == TRANSPOSE_MAX_FL, "the header states the ring's reach");
 
 // n <= 16384: the 2n planes of a batch are one grid dimension (65535 at most); a context holds 128 frames anyway.
 // height <= 65535: the rows of level 0 are another (video_level0_kernel)
@@ -107,36 +108,19 @@ extern "C" int fvvdp_video_grad_frames(int width, int height, int n_bands, int n
     return FVVDP_OK;
 }
 
-template <int FL>
-static void launch_input(const VideoInputArgs& ia, bool vec, hipStream_t st) {
-    constexpr int PXV = FL <= 16 ? 4 : 2;          // pixels per lane of the vector variant: the ring is FL x PX registers
-    const size_t HW = (size_t)ia.HW;
-    if (vec) {
-        const unsigned int blocks = (unsigned int)((HW / PXV + 255) / 256);
-        hipLaunchKernelGGL((video_input_kernel<FL, PXV>), dim3(blocks), dim3(256), 0, st, ia);
-    } else {
-        hipLaunchKernelGGL((video_input_kernel<FL, 1>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
-    }
-}
-// float16 / bfloat16 samples and gradient: the same grids, the same pixels per lane
+// ST == SRC_F32: video_input_kernel; float16 / bfloat16 samples and gradient: video_input_half_kernel, the same grids and the
+// same pixels per lane
 template <int FL, int ST>
-static void launch_input_half(const VideoInputArgs& ia, bool vec, hipStream_t st) {
-    constexpr int PXV = FL <= 16 ? 4 : 2;
-    const size_t HW = (size_t)ia.HW;
-    if (vec) {
-        const unsigned int blocks = (unsigned int)((HW / PXV + 255) / 256);
-        hipLaunchKernelGGL((video_input_half_kernel<FL, PXV, ST>), dim3(blocks), dim3(256), 0, st, ia);
+static void launch_input(const VideoInputArgs& ia, bool vec, hipStream_t st) {
+    constexpr int PXV = transpose_px(FL);
+    const size_t HW = (size_t)ia.t.HW;
+    const dim3 grid((unsigned int)(((vec ? HW / PXV : HW) + 255) / 256)), block(256);
+    if constexpr (ST == SRC_F32) {
+        if (vec) hipLaunchKernelGGL((video_input_kernel<FL, PXV>), grid, block, 0, st, ia);
+        else hipLaunchKernelGGL((video_input_kernel<FL, 1>), grid, block, 0, st, ia);
     } else {
-        hipLaunchKernelGGL((video_input_half_kernel<FL, 1, ST>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
-    }
-}
-template <int ST>
-static void launch_input_half(int FL, const VideoInputArgs& ia, bool vec, hipStream_t st) {
-    switch (FL) {
-        case 8: launch_input_half<8, ST>(ia, vec, st); break;
-        case 16: launch_input_half<16, ST>(ia, vec, st); break;
-        case 32: launch_input_half<32, ST>(ia, vec, st); break;
-        default: launch_input_half<64, ST>(ia, vec, st); break;
+        if (vec) hipLaunchKernelGGL((video_input_half_kernel<FL, PXV, ST>), grid, block, 0, st, ia);
+        else hipLaunchKernelGGL((video_input_half_kernel<FL, 1, ST>), grid, block, 0, st, ia);
     }
 }
 
@@ -167,18 +151,8 @@ extern "C" int fvvdp_video_grad_input_st(int width, int height, int n_frames, co
     if (frame_stride < HW) return grad_fail(FVVDP_EINVAL, "frame_stride %zu is below the frame size %zu", frame_stride, HW);
     if (C == 3 && chan_stride < HW) return grad_fail(FVVDP_EINVAL, "chan_stride %zu is below the frame size %zu", chan_stride, HW);
     GRAD_CHECK(grad_check_closed_form(eotf));
-    // the fold list: every head position exactly once, frames inside the clip, sorted by frame and then by position
-    bool seen[VG_MAX_FL] = {false};
-    for (int i = 0; i < fl; ++i) {
-        const int f = h_fold_frame[i], p = h_fold_pos[i];
-        if (f < 0 || f >= n_frames) return grad_fail(FVVDP_EINVAL, "fold list entry %d names frame %d outside [0, %d)", i, f, n_frames);
-        if (p < 0 || p >= fl || seen[p]) return grad_fail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
-        seen[p] = true;
-        if (i > 0 && (f < h_fold_frame[i - 1] || (f == h_fold_frame[i - 1] && p < h_fold_pos[i - 1])))
-            return grad_fail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
-    }
-    if (head_bytes < (size_t)fl * HW * sizeof(float))
-        return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
+    GRAD_CHECK(grad_verdict(transpose_check_fold(h_fold_frame, h_fold_pos, fl, n_frames, "frame")));
+    GRAD_CHECK(grad_verdict(transpose_check_head_bytes(head_bytes, fl, HW)));
     // fp32 buffers of the backward, and the caller's samples and gradient (es bytes per sample)
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_head);
     const uintptr_t sptrs = reinterpret_cast<uintptr_t>(d_test) | reinterpret_cast<uintptr_t>(d_grad);
@@ -189,37 +163,20 @@ extern "C" int fvvdp_video_grad_input_st(int width, int height, int n_frames, co
 
     VideoInputArgs ia;
     memset(&ia, 0, sizeof(ia));
-    ia.g0 = d_g0;
+    transpose_fill(ia.t, d_g0, d_head, HW, n_frames, fl, h_taps, h_fold_frame, h_fold_pos);
     ia.test = static_cast<const float*>(d_test);       // (16-bit samples: the kernel reads and writes them as such)
     ia.grad = static_cast<float*>(d_grad);
-    ia.head = d_head;
     ia.chan_stride = C == 3 ? chan_stride : 0;
     ia.frame_stride = frame_stride;
     ia.C = C;
-    ia.HW = (int)HW;
-    ia.N = n_frames;
-    ia.fl = fl;
     grad_fill_eotf(ia.e, ia.wgt, eotf, C, h_rgb2y);
-    for (int m = 0; m < fl; ++m) {                  // ring slot m of step p is position p + m: it receives tap fl - 1 - m
-        ia.tapsT[m][0] = h_taps[fl - 1 - m];
-        ia.tapsT[m][1] = h_taps[fl + fl - 1 - m];
-    }
-    for (int i = 0; i < VG_MAX_FL; ++i) {
-        ia.fold_frame[i] = i < fl ? h_fold_frame[i] : -1;
-        ia.fold_pos[i] = i < fl ? h_fold_pos[i] : 0;
-    }
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : (fl <= 32 ? 32 : 64));
-    const size_t pxv = FL <= 16 ? 4 : 2;
-    const bool vec = HW % pxv == 0 && frame_stride % pxv == 0 && ia.chan_stride % pxv == 0 && ptrs % (4 * pxv) == 0 &&
-                     sptrs % (es * pxv) == 0;
-    if (dtype == FVVDP_F16) launch_input_half<SRC_F16>(FL, ia, vec, st);
-    else if (dtype == FVVDP_BF16) launch_input_half<SRC_BF16>(FL, ia, vec, st);
-    else switch (FL) {
-        case 8: launch_input<8>(ia, vec, st); break;
-        case 16: launch_input<16>(ia, vec, st); break;
-        case 32: launch_input<32>(ia, vec, st); break;
-        default: launch_input<64>(ia, vec, st); break;
-    }
+    const int FL = transpose_ring_length(fl, TRANSPOSE_MAX_FL);
+    const bool vec = transpose_vector_ok(FL, HW, frame_stride | ia.chan_stride, ptrs, sptrs, es);
+    transpose_dispatch<TRANSPOSE_MAX_FL>(FL, [&](auto c) {
+        if (dtype == FVVDP_F16) launch_input<c.value, SRC_F16>(ia, vec, st);
+        else if (dtype == FVVDP_BF16) launch_input<c.value, SRC_BF16>(ia, vec, st);
+        else launch_input<c.value, SRC_F32>(ia, vec, st);
+    });
     GRAD_HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }

@@ -274,116 +274,30 @@ __global__ __launch_bounds__(256) void yuvplanes_vec_kernel(const YuvPlanesArgs 
 }
 
 // ---- temporal transpose down to the luminance frames ------------------------------------------------------------------------
-// video_input_kernel (video_grad_kernels.hpp) without its display tail, in a global function of its own: a lane owns PX consecutive
-// pixels, walks the window-list positions p = 0 .. N + fl - 2 once with the fl open positions in a register ring that shifts by
-// one slot per step, sends finished head positions to the side buffer and, when frame j = p - (fl - 1) is complete, adds its head
-// positions in ascending order and then its streaming term: gL[j].  The same order of additions as there, no atomics.
-#define YG_MAX_FL 64
+// The transpose of transpose_kernels.hpp with a plain store as its tail: gL[j] = s[j], the sum video_input_kernel
+// (video_grad_kernels.hpp) forms before its display model, with the same order of additions.
 struct LumInputArgs {
-    const float* g0;        // [N][2][HW]
+    TransposeArgs t;        // g0, head, sizes, taps and fold list
     float* gL;              // [N][HW]
-    float* head;            // [fl][HW]
-    int HW, N, fl;
-    float tapsT[YG_MAX_FL][2];      // {sustained, transient} tap of ring slot m
-    int fold_frame[YG_MAX_FL];      // [fl] sorted; padded with -1
-    int fold_pos[YG_MAX_FL];
 };
+static_assert(offsetof(LumInputArgs, t) == 0, "transpose_step and FoldCursor read the start of the kernel-argument segment");
 
-template <int PX>
-struct YgVec {
-    float v[PX];
-};
-template <int PX>
-__device__ __forceinline__ YgVec<PX> yg_load(const float* p) {
-    YgVec<PX> r;
-    if constexpr (PX == 4) {
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(p));
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else if constexpr (PX == 2) {
-        const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(p));
-        r.v[0] = t.x; r.v[1] = t.y;
-    } else {
-        r.v[0] = __builtin_nontemporal_load(p);
-    }
-    return r;
-}
-template <int PX>
-__device__ __forceinline__ void yg_store(float* p, const YgVec<PX>& r) {
-    if constexpr (PX == 4) __builtin_nontemporal_store(v4f{r.v[0], r.v[1], r.v[2], r.v[3]}, reinterpret_cast<v4f*>(p));
-    else if constexpr (PX == 2) __builtin_nontemporal_store(v2f{r.v[0], r.v[1]}, reinterpret_cast<v2f*>(p));
-    else __builtin_nontemporal_store(r.v[0], p);
-}
-
-// FL: ring slots (fl rounded up to 8 / 16 / 32 / 64).  PX: pixels per lane (4 or 2: HW a multiple of PX and the pointers PX-float
-// aligned; 1: any size)
+// FL, PX: see TransposeRing
 template <int FL, int PX>
 __global__ __launch_bounds__(256) void video_lum_input_kernel(const LumInputArgs a) {
     const size_t px = ((size_t)blockIdx.x * 256 + threadIdx.x) * PX;
-    if (px >= (size_t)a.HW) return;
-    typedef const int __attribute__((address_space(4)))* karg_int_p;
-    typedef const char __attribute__((address_space(4)))* karg_p;
-    const karg_p ka = (karg_p)__builtin_amdgcn_kernarg_segment_ptr();
-    const karg_int_p fold_frame = (karg_int_p)(ka + offsetof(LumInputArgs, fold_frame));
-    const karg_int_p fold_pos = (karg_int_p)(ka + offsetof(LumInputArgs, fold_pos));
-    float ring[FL - 1][PX];                     // before step p: slot m = position p + m (slot FL - 1 is still empty: not kept)
-#pragma unroll
-    for (int m = 0; m < FL - 1; ++m)
-#pragma unroll
-        for (int i = 0; i < PX; ++i) ring[m][i] = 0.0f;
-    int cur = 0;                                // cursor in the fold list (wave-uniform)
-    const int total = a.N + a.fl - 1;
-    const size_t HW = (size_t)a.HW;
+    if (px >= (size_t)a.t.HW) return;
+    TransposeRing<FL, PX> ring = transpose_ring<FL, PX>();
+    const size_t HW = (size_t)a.t.HW;
+    FoldCursor<PX> fold(a.t.head, HW, px, a.t.fl);
+    const int total = a.t.N + a.t.fl - 1;
     for (int p = 0; p < total; ++p) {
-        const int j = p - (a.fl - 1);           // the frame that is complete after this step
-        YgVec<PX> gs, gt;
-        if (p < a.N) {
-            gs = yg_load<PX>(a.g0 + (size_t)p * 2 * HW + px);
-            gt = yg_load<PX>(a.g0 + ((size_t)p * 2 + 1) * HW + px);
-        } else {                                // past the last output frame: the open positions only drain
-#pragma unroll
-            for (int i = 0; i < PX; ++i) gs.v[i] = gt.v[i] = 0.0f;
-        }
-        // taps: long rings re-read them in every step, TAPC at a time through a laundered pointer (see video_input_kernel)
-        karg_p tp = ka + offsetof(LumInputArgs, tapsT);
-        if constexpr (FL > 8) asm volatile("" : "+s"(tp));
-        YgVec<PX> done;                         // position p
-#pragma unroll
-        for (int c = 0; c < FL / TAPC; ++c) {
-            karg_p tpc = tp + c * (8 * TAPC);
-            if constexpr (FL > 16) asm volatile("" : "+s"(tpc));
-            const vtapf tc = *(karg_taps_p)tpc;
-#pragma unroll
-            for (int kk = 0; kk < TAPC; ++kk) {
-                const int m = c * TAPC + kk;
-                const float fs = tc[2 * kk], ft = tc[2 * kk + 1];
-#pragma unroll
-                for (int i = 0; i < PX; ++i) {
-                    const float old = m < FL - 1 ? ring[m][i] : 0.0f;
-                    float v = fmaf(fs, gs.v[i], fmaf(ft, gt.v[i], old));
-                    asm volatile("" : "+v"(v));             // pinned where it is produced (see video_input_kernel)
-                    if (m == 0) done.v[i] = v;              // position p: nothing more arrives
-                    else ring[m - 1][i] = v;                // the shift: slot m becomes slot m - 1 of the next step
-                }
-            }
-            if constexpr (FL > 8) __builtin_amdgcn_sched_barrier(0);
-        }
-        if (p < a.fl) yg_store<PX>(a.head + (size_t)p * HW + px, done);
-        if (j >= 0) {
-            YgVec<PX> s;
-#pragma unroll
-            for (int i = 0; i < PX; ++i) s.v[i] = 0.0f;
-            while (cur < a.fl && fold_frame[cur] == j) {
-                const YgVec<PX> hd = yg_load<PX>(a.head + (size_t)fold_pos[cur] * HW + px);
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += hd.v[i];
-                ++cur;
-            }
-            if (j >= 1) {
-#pragma unroll
-                for (int i = 0; i < PX; ++i) s.v[i] += done.v[i];
-            }
-            yg_store<PX>(a.gL + (size_t)j * HW + px, s);
-        }
+        const int j = p - (a.t.fl - 1);         // the frame that is complete after this step
+        LaneVec<PX> gs, gt;
+        transpose_inputs<PX>(a.t.g0, p, a.t.N, HW, px, gs, gt);
+        const LaneVec<PX> done = transpose_step<FL, PX>(ring, gs, gt);
+        if (p < a.t.fl) lane_store<PX>(a.t.head + (size_t)p * HW + px, done);
+        if (j >= 0) lane_store<PX>(a.gL + (size_t)j * HW + px, fold.frame_sum(j, done));
     }
 }
 

@@ -13,10 +13,11 @@
 #include "device_common.hpp"
 #include "temporal_launch.hpp"     // fvvdp_ctx_ingest_begin
 #include "grad_common.hpp"
+#include "transpose_kernels.hpp"
 #include "yuv_grad_kernels.hpp"
 #include "grad_host.hpp"
 
-static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == YG_MAX_FL, "fvvdp_video_grad_luminance has the reach of fvvdp_video_grad_input");
+static_assert(FVVDP_VIDEO_GRAD_MAX_TAPS == TRANSPOSE_MAX_FL, "fvvdp_video_grad_luminance has the reach of fvvdp_video_grad_input");
 static_assert(FVVDP_YUV_GRAD_MAX_TAPS == 32, "YuvPlanesArgs::taps2");
 
 static int check_format(const fvvdp_yuv_format* fmt, int width, int height) {
@@ -119,8 +120,8 @@ extern "C" int fvvdp_temporal_channels_yuv_planes(fvvdp_ctx* ctx, const fvvdp_yu
 
 template <int FL>
 static void launch_lum_input(const LumInputArgs& ia, bool vec, hipStream_t st) {
-    constexpr int PXV = FL <= 16 ? 4 : 2;          // pixels per lane of the vector variant: the ring is FL x PX registers
-    const size_t HW = (size_t)ia.HW;
+    constexpr int PXV = transpose_px(FL);
+    const size_t HW = (size_t)ia.t.HW;
     if (vec) hipLaunchKernelGGL((video_lum_input_kernel<FL, PXV>), dim3((unsigned int)((HW / PXV + 255) / 256)), dim3(256), 0, st, ia);
     else hipLaunchKernelGGL((video_lum_input_kernel<FL, 1>), dim3((unsigned int)((HW + 255) / 256)), dim3(256), 0, st, ia);
 }
@@ -136,47 +137,19 @@ extern "C" int fvvdp_video_grad_luminance(int width, int height, int n_frames, c
     if (fl > FVVDP_VIDEO_GRAD_MAX_TAPS)
         return grad_fail(FVVDP_EUNSUPPORTED, "the video backward covers temporal filters of up to %d taps (256 frames per second); "
                                              "this one has %d", FVVDP_VIDEO_GRAD_MAX_TAPS, fl);
-    // the fold list: every head position exactly once, frames inside the clip, sorted by frame and then by position
-    bool seen[YG_MAX_FL] = {false};
-    for (int i = 0; i < fl; ++i) {
-        const int f = h_fold_frame[i], p = h_fold_pos[i];
-        if (f < 0 || f >= n_frames) return grad_fail(FVVDP_EINVAL, "fold list entry %d names frame %d outside [0, %d)", i, f, n_frames);
-        if (p < 0 || p >= fl || seen[p]) return grad_fail(FVVDP_EINVAL, "fold list entry %d: head position %d is outside [0, %d) or listed twice", i, p, fl);
-        seen[p] = true;
-        if (i > 0 && (f < h_fold_frame[i - 1] || (f == h_fold_frame[i - 1] && p < h_fold_pos[i - 1])))
-            return grad_fail(FVVDP_EINVAL, "fold list must be sorted by frame, then by position (entry %d)", i);
-    }
-    if (head_bytes < (size_t)fl * HW * sizeof(float))
-        return grad_fail(FVVDP_EINVAL, "side buffer of %zu bytes is below the %zu needed", head_bytes, (size_t)fl * HW * sizeof(float));
+    GRAD_CHECK(grad_verdict(transpose_check_fold(h_fold_frame, h_fold_pos, fl, n_frames, "frame")));
+    GRAD_CHECK(grad_verdict(transpose_check_head_bytes(head_bytes, fl, HW)));
     const uintptr_t ptrs = reinterpret_cast<uintptr_t>(d_g0) | reinterpret_cast<uintptr_t>(d_head) | reinterpret_cast<uintptr_t>(d_gL);
     if (ptrs % 4 != 0) return grad_fail(FVVDP_EINVAL, "device pointers must be aligned to 4 bytes");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
     LumInputArgs ia;
     memset(&ia, 0, sizeof(ia));
-    ia.g0 = d_g0;
+    transpose_fill(ia.t, d_g0, d_head, HW, n_frames, fl, h_taps, h_fold_frame, h_fold_pos);
     ia.gL = d_gL;
-    ia.head = d_head;
-    ia.HW = (int)HW;
-    ia.N = n_frames;
-    ia.fl = fl;
-    for (int m = 0; m < fl; ++m) {                  // ring slot m of step p is position p + m: it receives tap fl - 1 - m
-        ia.tapsT[m][0] = h_taps[fl - 1 - m];
-        ia.tapsT[m][1] = h_taps[fl + fl - 1 - m];
-    }
-    for (int i = 0; i < YG_MAX_FL; ++i) {
-        ia.fold_frame[i] = i < fl ? h_fold_frame[i] : -1;
-        ia.fold_pos[i] = i < fl ? h_fold_pos[i] : 0;
-    }
-    const int FL = fl <= 8 ? 8 : (fl <= 16 ? 16 : (fl <= 32 ? 32 : 64));
-    const size_t pxv = FL <= 16 ? 4 : 2;
-    const bool vec = HW % pxv == 0 && ptrs % (4 * pxv) == 0;
-    switch (FL) {
-        case 8: launch_lum_input<8>(ia, vec, st); break;
-        case 16: launch_lum_input<16>(ia, vec, st); break;
-        case 32: launch_lum_input<32>(ia, vec, st); break;
-        default: launch_lum_input<64>(ia, vec, st); break;
-    }
+    const int FL = transpose_ring_length(fl, TRANSPOSE_MAX_FL);
+    const bool vec = transpose_vector_ok(FL, HW, 0, ptrs);
+    transpose_dispatch<TRANSPOSE_MAX_FL>(FL, [&](auto c) { launch_lum_input<c.value>(ia, vec, st); });
     GRAD_HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }

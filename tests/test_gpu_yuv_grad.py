@@ -197,7 +197,7 @@ def test_unpack_adjoint_per_sample(css, H, W, model, form):
 # ---- 3. the luminance transpose ---------------------------------------------------------------------------------------------------
 LUM = [(8, 11, "replicate", 16, 8), (9, 12, "circular", 16, 8), (16, 5, "pingpong", 30, 20), (17, 20, "replicate", 30, 20),
        (32, 35, "circular", 16, 8), (33, 7, "pingpong", 16, 8), (64, 66, "replicate", 10, 6), (15, 19, "circular", 11, 7),
-       (30, 9, "pingpong", 9, 13)]
+       (30, 9, "pingpong", 9, 13), (6, 9, "replicate", 7, 5), (60, 5, "circular", 7, 5)]
 
 
 @pytest.mark.parametrize("fl,N,padding,W,H", LUM, ids=["fl%d-N%d-%s-%dx%d" % c for c in LUM])

@@ -315,11 +315,24 @@ def held_map_bytes(n_display):
     return (n_display * 4 + 255) // 256 * 256
 
 
+# include/fvvdp_hip_images_resize.h: still images whose stacks have image sizes of their own -- the resize fused into the still-image
+# ingest, and the level-0 step of the still-image backward that ends in luminance (bound by lib() as well)
+IMAGES_RESIZE_SYMBOLS = {
+    "fvvdp_images_channels_resized": (C.c_int, [C.c_void_p, C.POINTER(ResizeStream), C.POINTER(ResizeStream), C.c_int, C.c_int,
+                                                C.POINTER(Eotf), C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "fvvdp_images_grad_luminance_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "fvvdp_images_grad_luminance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(PoolParams), C.c_void_p,
+                                              C.c_int, C.c_int, C.c_void_p, C.POINTER(BandMaps), C.POINTER(C.c_void_p), C.c_void_p,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+RESIZE_MAX_AXIS = 32768                  # FVVDP_RESIZE_MAX_AXIS
+
+
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-five translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-six translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them;
     their launch plans and bounds are the host-only header pyramid_host.hpp, the strip constants pyramid_constants.hpp), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
@@ -328,8 +341,8 @@ def build(force=False, verbose=False):
     (param_launch.hip), the gradient with respect to the temporal taps (tap_grad_launch.hip), the sums for the gradient with
     respect to the display's photometry (display_grad_launch.hip), the gradients of the difference map (map_grad_launch.hip), the
     float YUV planes with their gradients (yuv_grad_launch.hip), the gradients of many tests with respect to their one reference
-    (tests_grad_launch.hip), the clips resized inside the ingest with the resize's adjoint (resize_launch.hip) and the clips with
-    held frames (held_launch.hip with -DHELD_PART=0..5: the ingest per sample type, then the C ABI with the backward's kernel) -- are
+    (tests_grad_launch.hip), the clips resized inside the ingest with the resize's adjoint (resize_launch.hip), the still images
+    resized inside their ingest (images_resize_launch.hip) and the clips with held frames (held_launch.hip with -DHELD_PART=0..5: the ingest per sample type, then the C ABI with the backward's kernel) -- are
     compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
@@ -337,7 +350,7 @@ def build(force=False, verbose=False):
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
                                                                                                                               "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h",
-                                                                                                                              "fvvdp_hip_resize.h", "fvvdp_hip_held.h")]
+                                                                                                                              "fvvdp_hip_resize.h", "fvvdp_hip_held.h", "fvvdp_hip_images_resize.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -386,6 +399,10 @@ def build(force=False, verbose=False):
     # (-DHELD_PART=0..4, new instantiations of the ring bodies of temporal_launch.hip), and the C ABI with the backward's kernel (5)
     units += [(os.path.join(csrc, "held_launch.hip"), ["-DHELD_PART=%d" % k], os.path.join(objdir, "held_part%d.o" % k))
               for k in range(6)]
+    # still images resized inside their ingest, and the level-0 step that ends in luminance (include/fvvdp_hip_images_resize.h).
+    # -ffp-contract=off as resize_launch.hip: the ingest evaluates the functions that unit's adjoint recomputes, and the two stacks
+    # are two copies of scalar code -- all must round alike
+    units += [(os.path.join(csrc, "images_resize_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "images_resize_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -415,7 +432,7 @@ def lib():
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
                 list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()) + \
-                list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()):
+                list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()) + list(IMAGES_RESIZE_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

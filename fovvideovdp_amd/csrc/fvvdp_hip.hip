@@ -642,6 +642,7 @@ int fvvdp_ctx_ingest_begin(fvvdp_ctx* c, const char* what, bool even_size, int c
     luminance_range(c, eotf, channels, h_rgb2y, h_taps, fl);
     b->W = c->W;
     b->H = c->H;
+    b->planes = c->P;
     b->out = level_addr(c, 0, slot0);
     b->e = make_eotf(eotf);
     b->scalar = c->env.temporal_scalar;

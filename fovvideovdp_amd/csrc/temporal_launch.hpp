@@ -22,6 +22,7 @@ static inline bool k1_ring64_ok(int dtype, int C, int eotf_kind) {
 // ingest that did not come through here would leave them dropped on the strength of an earlier call's range.
 struct IngestBegin {
     int W, H;              // the context's frame size
+    int planes;            // 4: a video context, 2: a still-image context
     L0Addr out;            // level 0 at slot0
     EotfDev e;             // the display block as the kernels take it (a table without a stated range: any value passes)
     bool scalar, debug;    // FVVDP_TEMPORAL_SCALAR, FVVDP_DEBUG_VARIANT

@@ -448,6 +448,56 @@ class fvvdp:
         return jod_video_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
                                  fixation_point)
 
+    def predict_images_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCHW",
+                               fixation_point=None):
+        """Extension: predict_images for a test and a reference stack that each have an image size of their OWN -- the outputs
+        of a super-resolution or down-scaling network, a render-resolution sweep of stills, images shown full screen.  `test` is
+        [B, C, h, w] and `reference` [B, C, h', w'] in `dim_order` (a B axis; no F axis, or F == 1), the same B and C (C = 1 or
+        3), each float32, or uint8 scaled by 1/255, on host or device, in any layout.  `resize_resolution=(width, height)` is the
+        size the metric judges at (default: the display geometry's resolution).  A stack of another size is resized inside the
+        ingest kernel with the arithmetic of torch.nn.functional.interpolate (`full_screen_resize`: "bilinear", "bicubic",
+        "nearest" or "area"; align_corners=False, no antialiasing); a stack that has the target size is read as it is, and
+        clipped like the other.  Per stack and target pixel: interpolate every channel, clip to [0, 1] (the clip belongs to the
+        resize: no range flags), display model, luminance.  No image at the target size is stored.  Returns (Q_JOD, stats):
+        Q_JOD a [B] device tensor, stats['Q_per_ch'] [B, bands, 2, 1] (numpy), stats['rho_band'], 'width' and 'height' at the
+        target size; no heat maps, whatever `heatmap` the metric has.  `fixation_point`: [x, y] or [B, 2] in target pixels for
+        a foveated metric.  Pair k's result does not depend on the batch, bit for bit.  When both stacks already have the target
+        size the call is predict_images's, unchanged.  Refused, each with a sentence and before any device work: an unknown
+        mode, half-precision, float64 or 16-bit samples, a look-up-table or user photometry, differing B or C, an F axis longer
+        than 1 (clips: predict_resized), a width or height outside 1 .. 32768, inputs that require grad."""
+        from .images_resize import predict_images_resized
+        return predict_images_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, fixation_point)
+
+    def jod_images_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCHW",
+                           fixation_point=None, wrt="test"):
+        """Extension: jod_images for stacks with image sizes of their own (see predict_images_resized for the resize), for losses
+        such as `10 - metric.jod_images_resized(net(x_small), ref_full).mean()`.  Returns [B] fp32 JODs on the metric's device;
+        under torch.no_grad() they equal predict_images_resized's bit for bit.  `wrt` as jod_images takes it.  "test" (default):
+        backward() puts grad[k] dJOD_k/dtest_k into the caller's `test` AT THE TEST'S OWN RESOLUTION, on host or device, whatever
+        its layout; the reference is a constant, and one that requires grad is refused.  "reference": the gradient goes into
+        `reference` at the reference's own resolution, and a test that requires grad is refused.  "both": one backward -- one
+        re-ingest and one map-writing pass per backward batch -- delivers both gradients to whichever of the two require grad;
+        the test gradient is bit-identical to wrt="test".  Anything else: ValueError.  A differentiated side is float32; a
+        float16 or bfloat16 tensor is upcast with torch's .float() inside autograd's view, so the gradient arrives in the
+        caller's dtype through torch's cast node (there are no half-precision kernels here); the constant side may be uint8.
+        The adjoint of the resize is one gather per sample in a fixed order (no atomics): the gradient does not depend on
+        `self.grad_batch`, on placement or on layout, and repeats bit for bit.  A sample gets an exact zero where every target
+        pixel it reaches is clipped or clamped by the display model, and where a downscale skips it; an identical pair resized
+        identically gives JOD == 10 and exact zeros.  When both stacks already have the target size the call is jod_images's.
+        Double backward is not supported."""
+        from .images_resize import jod_images_resized
+        return jod_images_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, fixation_point, wrt)
+
+    def predict_image_pairs_resized(self, pairs, full_screen_resize="bilinear", resize_resolution=None, dim_order="HWC",
+                                    fixation_points=None):
+        """Extension: predict_image_pairs for a list of (test, reference) whose two images may each have any size: a folder of
+        images of mixed sizes scored full screen.  The pairs are grouped by (test size, reference size, dtypes, C) and every
+        group is one predict_images_resized pass.  Returns [(Q_JOD, stats)] in input order, Q_JOD 0-d and Q_per_ch [bands, 2, 1];
+        row k equals the call on pair k alone, bit for bit.  `fixation_points`: None, or one [x, y] (or None) per pair in target
+        pixels.  Forward only."""
+        from .images_resize import predict_image_pairs_resized
+        return predict_image_pairs_resized(self, pairs, full_screen_resize, resize_resolution, dim_order, fixation_points)
+
     def predict_held(self, test, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None, test_frames=1,
                      reference_frames=1):
         """Extension: predict for a test and a reference clip that each have a frame COUNT of their own -- a 30 fps encode on a

@@ -157,6 +157,44 @@ class ImageSetup(_Setup):
         return self.launch(fix, b0, nb, maps.q_scratch, nb, 0, _ptr(maps.jod_scratch), maps)
 
 
+def image_strides(x):
+    """(image stride, plane stride) in elements of the stack [B, C, h, w]; an axis of size 1 has no stride to speak of: what a
+    dense stack would have."""
+    hw = x.shape[2] * x.shape[3]
+    ps = x.stride(1) if x.shape[1] > 1 else hw
+    return (x.stride(0) if x.shape[0] > 1 else x.shape[1] * ps), ps
+
+
+def image_resize_stream(x, b0=0):
+    """fvvdp_resize_stream of a device stack [B, C, h, w] (float32 or uint8; rows and planes dense) from image b0 on: image k is
+    the stream's frame k."""
+    fs, ps = image_strides(x)
+    return nat.ResizeStream(x.data_ptr() + b0 * fs * x.element_size(), nat.FVVDP_U8 if x.dtype is torch.uint8 else nat.FVVDP_F32,
+                            x.shape[1], x.shape[3], x.shape[2], fs, ps)
+
+
+class ResizedImageSetup(ImageSetup):
+    """ImageSetup for a pair of stacks with image sizes of their own (images_resize): t and r are [B, C, h, w] device tensors as
+    image_resize_stream takes them, mode the FVVDP_RESIZE_* code, size the target (width, height) -- self.W and self.H, the size
+    the pyramid runs at; the ingest is fvvdp_images_channels_resized.  launch, write_maps and forward_images are ImageSetup's."""
+
+    def __init__(self, metric, t, r, mode, size, prm=None, pp=None):
+        self.t, self.r, self.mode = t, r, mode
+        self.B, self.C = t.shape[0], t.shape[1]
+        self.W, self.H = size
+        self.n_bands, self.rho_band = metric._band_count(self.W, self.H)
+        self.dtype, self.e = metric._image_eotf(torch.float32)
+        self.w = metric._rgb2y()
+        self.batch = metric._batch_size(self.W, self.H, 2, self.B)
+        self._finish(metric, 2, prm, pp)
+
+    def ingest(self, lib, t, r, b0, nb):
+        """(no pointer table, so none is returned; no range flag -- the clip to [0, 1] belongs to the resize)"""
+        ts, rs = image_resize_stream(t, b0), image_resize_stream(r, b0)
+        nat.check(lib.fvvdp_images_channels_resized(self.ctx.handle, C.byref(ts), C.byref(rs), nb, self.mode, C.byref(self.e),
+                                                    nat.fptr(self.w), 0, self.stream))
+
+
 def forward_images(s, fix):
     """JOD [B] and Q_per_ch [n_bands, 2, B] on the device: the launches of predict_images, no flags read back, no heat maps."""
     Q = torch.zeros((s.n_bands, 2, s.B), dtype=torch.float32, device=s.metric.device)

@@ -112,28 +112,12 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
     const int xc0 = min(max(X0, 0), w - 1), xc1 = min(max(X1, 0), w - 1);
     const bool col1_ok = X1 < w;
 
-    const float K0 = 0.05f, K1 = 0.25f, K2 = 0.4f, K3 = 0.25f, K4 = 0.05f;
-    // ---- per-lane horizontal weights, level A -> B (column J) and B -> C (column K); see band_kernel ----------
-    float wq0 = K0, wq1 = K1, wq2 = K2, wq3 = K3, wq4 = K4;
-    if (J == 0) { wq2 += K1; wq3 += K0; wq0 = 0.0f; wq1 = 0.0f; }
-    if (J == wb - 1) {
-        const bool hodd = (h & 1) != 0;
-        if (w & 1) { wq3 = 0.0f; wq4 = 0.0f; if (hodd) { wq2 += K3; wq1 += K4; } else { wq2 += K4; } }
-        else { wq4 = 0.0f; if (hodd) { wq3 += K3; wq2 += K4; } else { wq3 += K4; } }
-    }
-    // taps of C column K at an even lane: B columns 2K-2 .. 2K+2 = lanes l-2, l-1, l, l+1, l+2
-    float uq0 = K0, uq1 = K1, uq2 = K2, uq3 = K3, uq4 = K4;
-    if (K == 0) { uq2 += K1; uq3 += K0; uq0 = 0.0f; uq1 = 0.0f; }
-    if (K == wc - 1) {
-        const bool hodd = (hb & 1) != 0;
-        if (wb & 1) { uq3 = 0.0f; uq4 = 0.0f; if (hodd) { uq2 += K3; uq1 += K4; } else { uq2 += K4; } }
-        else { uq4 = 0.0f; if (hodd) { uq3 += K3; uq2 += K4; } else { uq3 += K4; } }
-    }
-    // expand B -> A at columns X0 (even) / X1 (odd) from B columns J-1, J, J+1
-    const bool at_l = (J <= 0), at_r = (J >= wb - 1);
-    const float el = at_l ? 0.0f : 0.1f, er = at_r ? 0.0f : 0.1f;
-    const float ec = 0.8f + (at_l ? 0.1f : 0.0f) + (at_r ? 0.1f : 0.0f);
-    const float orr = at_r ? 0.0f : 0.5f, oc = at_r ? 1.0f : 0.5f;
+    // ---- per-lane horizontal weights (pyramid_walk.hpp): reduce level A -> B at column J and B -> C at column K (the taps of C
+    // column K at an even lane: B columns 2K-2 .. 2K+2 = lanes l-2, l-1, l, l+1, l+2); expand B -> A at columns X0 (even) / X1
+    // (odd) from B columns J-1, J, J+1
+    const ReduceW rq = lane_reduce_weights(J, wb, w, h);
+    const ReduceW ru = lane_reduce_weights(K, wc, wb, hb);
+    const ExpandW ex = lane_expand_weights(J, wb);
     // expand C -> B at column J from C columns K-1, K, K+1 = lanes l-2, l, l+2 (every lane of a pair holds C[K])
     const bool k_l = (K <= 0), k_r = (K >= wc - 1);
     const float fl = (jeven && !k_l) ? 0.1f : 0.0f;
@@ -151,13 +135,7 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
     const __amdgpu_buffer_rsrc_t Ga_rsrc = level_rsrc(const_cast<float*>(Ga), (unsigned int)(h * w * P) * 4u);   // <= 133 MB per frame
     const unsigned int col0_b = (unsigned int)xc0 * (P * 4u), col1_b = (unsigned int)xc1 * (P * 4u);
     const unsigned int row_b = (unsigned int)w * (P * 4u);
-    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) {
-        int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);   // symmetric padding (fvvdp_lpyr_dec.py:190-195)
-        rr = min(max(rr, 0), h - 1);
-        const unsigned int so = (unsigned int)rr * row_b;
-        p0 = ld_px_buf<P>(Ga_rsrc, col0_b, so);
-        p1 = ld_px_buf<P>(Ga_rsrc, col1_b, so);
-    };
+    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) { load_row_pair<P>(Ga_rsrc, col0_b, col1_b, row_b, h, r, p0, p1); };
 
 
     // Level-A rows live in an 8-slot register ring: row r of the chunk sits in slot r & 7, a step's window is slots
@@ -166,30 +144,7 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
     // (a 5-row window that is shifted costs 24 v_mov_b64 per stage; the kernel's arithmetic is as long as its data flow).
     Px<P> S[8][2];
     auto coarse_step = [&](auto base) -> Px<P> {          // level-B row from the 5-row window of level A at slot `base`
-        constexpr int B = decltype(base)::value;
-        Px<P>(&W0)[2] = S[(B + 0) & 7]; Px<P>(&W1)[2] = S[(B + 1) & 7]; Px<P>(&W2)[2] = S[(B + 2) & 7];
-        Px<P>(&W3)[2] = S[(B + 3) & 7]; Px<P>(&W4)[2] = S[(B + 4) & 7];
-        Px<P> c, va, vb;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f a0 = W0[0].h[k] * K0;
-            a0 = pfma(W1[0].h[k], K1, a0);
-            a0 = pfma(W2[0].h[k], K2, a0);
-            a0 = pfma(W3[0].h[k], K3, a0);
-            va.h[k] = pfma(W4[0].h[k], K4, a0);
-            v2f b0 = W0[1].h[k] * K0;
-            b0 = pfma(W1[1].h[k], K1, b0);
-            b0 = pfma(W2[1].h[k], K2, b0);
-            b0 = pfma(W3[1].h[k], K3, b0);
-            vb.h[k] = pfma(W4[1].h[k], K4, b0);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f acc = va.h[k] * wq2;
-            acc = pfma(vb.h[k], wq3, acc);
-            c.h[k] = dpp_reduce_taps(acc, va.h[k], vb.h[k], wq0, wq1, wq4);
-        }
-        return c;
+        return reduce5_ring<P, decltype(base)::value>(S, rq.q0, rq.q1, rq.q2, rq.q3, rq.q4);
     };
     float accA[2] = {0.0f, 0.0f}, accB[2] = {0.0f, 0.0f};
     const float lg_base = a.lg_gain;
@@ -225,24 +180,11 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
         const float vm = valid ? 1.0f : 0.0f;
         const float lcn = lg_bm[band] - llb;
         if constexpr (HP == 2) {
-            // beta * log2 D = beta*p*(ldiff + S') - beta*log2(1 + 2^(q*(lmin + S''))), S' = slog + lcn + lg_base, S'' = slog +
-            // lcn + lg_mask: the constant factors are folded into fused multiply-adds (2 packed operations fewer per pixel
-            // than the literal form; it differs from it by the rounding of the products only)
             const v2f sl = v2f{slog0, slog1};
-            const v2f A = pfma(sl, pb, splat(fmaf(lcn, pb, pb_base)));        // beta*p*(slog + lcn + lg_base)
-            const v2f lsm = sl + splat(lcn + lg_mask);
-            const v2f ldiff = v2f{fast_log2(fabsf(d[0].x - d[0].y)), fast_log2(fabsf(d[1].x - d[1].y))};
-            const v2f lmin = v2f{fast_log2(fminf(fabsf(d[0].x), fabsf(d[0].y))), fast_log2(fminf(fabsf(d[1].x), fabsf(d[1].y)))};
-            const v2f ldb = pfma(ldiff, pb, A);                                // beta * p * (ldiff + S')
-            const v2f lm = (lmin + lsm) * v2f{a.q0, a.q1};
-            const v2f one_mq = v2f{fast_exp2(lm.x), fast_exp2(lm.y)} + splat(1.0f);
-            const v2f tb = pfma(v2f{fast_log2(one_mq.x), fast_log2(one_mq.y)}, -a.beta, ldb);
-            const v2f bl = v2f{fminf(tb.x, b_dmax), fminf(tb.y, b_dmax)};      // D <= d_max
-            const v2f term = v2f{fast_exp2(bl.x), fast_exp2(bl.y)};
-            const v2f av = __builtin_elementwise_fma(term, splat(vm), v2f{acc[0], acc[1]});
-            acc[0] = av.x;
-            acc[1] = av.y;
+            v2f bl;
+            PYRAMID_MASK_POOL_VIDEO(sl, fmaf(lcn, pb, pb_base), lcn + lg_mask, d[0], d[1], pb, a.q0, a.q1, a.beta, b_dmax, vm, acc, bl);
         } else {
+            // one channel: a kept copy, see pyramid_walk.hpp
             const float dT = d[0].x, dR = d[0].y;
             const float ls = slog0 + lcn;
             const float ld = a.p * (fast_log2(fabsf(dT - dR)) + (ls + lg_base));
@@ -256,23 +198,8 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
     auto band_a_rows = [&](auto base, int c, const Px<P>& Bm1, const Px<P>& B0, const Px<P>& Bp1) {
         constexpr int B = decltype(base)::value;
         Px<P>(&W0)[2] = S[(B + 0) & 7]; Px<P>(&W1)[2] = S[(B + 1) & 7];
-        Px<P> x00, x01, x10, x11, evE, evO;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f t = Bm1.h[k] * 0.1f;
-            t = pfma(B0.h[k], 0.8f, t);
-            evE.h[k] = pfma(Bp1.h[k], 0.1f, t);
-            evO.h[k] = pfma(Bp1.h[k], 0.5f, B0.h[k] * 0.5f);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            x00.h[k] = evE.h[k] * ec;
-            x01.h[k] = evE.h[k] * oc;
-            dpp_expand_taps(evE.h[k], el, er, orr, x00.h[k], x01.h[k]);
-            x10.h[k] = evO.h[k] * ec;
-            x11.h[k] = evO.h[k] * oc;
-            dpp_expand_taps(evO.h[k], el, er, orr, x10.h[k], x11.h[k]);
-        }
+        Px<P> x00, x01, x10, x11;
+        PYRAMID_EXPAND_ROWS(HP, Bm1, B0, Bp1, ex.el, ex.er, ex.ec, ex.orr, ex.oc, x00, x01, x10, x11);
         const bool row1_ok = (2 * c + 1) < h;
         tail(W0[0], x00, owned, 0, accA);
         tail(W0[1], x01, owned && col1_ok, 0, accA);
@@ -359,12 +286,12 @@ __device__ __forceinline__ void band2_item(const Band2Args& a, const int strip, 
         Px<P> Cn;
 #pragma unroll
         for (int q = 0; q < HP; ++q) {
-            v2f v = R[0].h[q] * K0;
-            v = pfma(R[1].h[q], K1, v);
-            v = pfma(R[2].h[q], K2, v);
-            v = pfma(R[3].h[q], K3, v);
-            v = pfma(R[4].h[q], K4, v);
-            Cn.h[q] = dpp_reduce5_pair(v * uq2, v, uq0, uq1, uq3, uq4);
+            v2f v = R[0].h[q] * 0.05f;
+            v = pfma(R[1].h[q], 0.25f, v);
+            v = pfma(R[2].h[q], 0.4f, v);
+            v = pfma(R[3].h[q], 0.25f, v);
+            v = pfma(R[4].h[q], 0.05f, v);
+            Cn.h[q] = dpp_reduce5_pair(v * ru.q2, v, ru.q0, ru.q1, ru.q3, ru.q4);
         }
         st_px(Gc_rsrc, (k >= ka && k < kb && owned && jeven && K < wc) ? (unsigned int)(k * wc + K) * (P * 4u) : FVVDP_NO_STORE, Cn);
         CH[0] = CH[1];
@@ -460,7 +387,8 @@ __global__ __launch_bounds__(64 * BAND2_WPB_MAX, BAND2_LB) void band2_kernel(con
         int v = (int)blockIdx.x, nb = first;
         tall = v < first;
         if (!tall) { v -= first; nb = (int)gridDim.x - first; }
-        // XCD-aware work order within a phase
+        // XCD-aware work order within a phase: xcd_work_order's expression (pyramid_walk.hpp) on the phase's own index and
+        // count, kept as a copy -- through the function the scalar registers of all four instantiations were renamed
         const int q8 = nb >> 3, r8 = nb & 7, x = v & 7;
         bid = x * q8 + min(x, r8) + (v >> 3);
     }

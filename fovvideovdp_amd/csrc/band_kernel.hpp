@@ -21,23 +21,6 @@ struct Px {                 // one pixel: P/2 (test, ref) pairs
     v2f h[P / 2];
 };
 
-template <int P>
-__device__ __forceinline__ Px<P> ld_px(const float* p);
-template <>
-__device__ __forceinline__ Px<4> ld_px<4>(const float* p) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    Px<4> r;
-    r.h[0] = v2f{t.x, t.y};
-    r.h[1] = v2f{t.z, t.w};
-    return r;
-}
-template <>
-__device__ __forceinline__ Px<2> ld_px<2>(const float* p) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    Px<2> r;
-    r.h[0] = v2f{t.x, t.y};
-    return r;
-}
 // Loads through a buffer resource: voff = the lane's byte offset (vector register), soff = a wave-uniform byte offset (scalar
 // register) -- the address needs no vector arithmetic.
 template <int P>
@@ -109,6 +92,8 @@ __device__ __forceinline__ void dpp_expand_taps(v2f e, float el, float er, float
     even = v2f{ex, ey};
     odd = v2f{ox, oy};
 }
+
+#include "pyramid_walk.hpp"   // the row walk shared with band2_kernel, multigaze_kernel and multitest_kernel
 
 // Layout of a band's slice of the CSF table (foveated mode): [rho interval][ecc][Y] of float4 records, the ecc rows padded
 // from 32 to FOV_ROW entries and every rho plane by 8 more.  ds_read_b128 serves a wave in four 16-lane groups and a group
@@ -255,37 +240,9 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
     const int xc0 = min(max(X0, 0), w - 1), xc1 = min(max(X1, 0), w - 1);
     const bool col1_ok = X1 < w;
 
-    // horizontal 5-tap weights of this lane's coarse column incl. the reference's edge fix-ups
-    // (gausspyr_reduce, fvvdp_lpyr_dec.py:198-205; the right-edge branch is selected by the parity of the ROW
-    // count, :202, reproduced here on purpose).  Taps: E[l-1], O[l-1], E[l], O[l], E[l+1]  (E/O = even/odd fine
-    // column of a lane); taps falling outside the image get weight 0 and their fix-up is folded into the
-    // in-range taps.
-    const float K0 = 0.05f, K1 = 0.25f, K2 = 0.4f, K3 = 0.25f, K4 = 0.05f;
-    float wq0 = K0, wq1 = K1, wq2 = K2, wq3 = K3, wq4 = K4;
-    if (J == 0) {
-        wq2 += K1;
-        wq3 += K0;
-        wq0 = 0.0f;
-        wq1 = 0.0f;
-    }
-    if (J == wc - 1) {
-        const bool hodd = (h & 1) != 0;
-        if (w & 1) {   // own columns: X0 = w-1 (tap 2), X1 = w (outside)
-            wq3 = 0.0f;
-            wq4 = 0.0f;
-            if (hodd) { wq2 += K3; wq1 += K4; } else { wq2 += K4; }
-        } else {       // own columns: w-2 (tap 2), w-1 (tap 3); tap 4 = column w is outside
-            wq4 = 0.0f;
-            if (hodd) { wq3 += K3; wq2 += K4; } else { wq3 += K4; }
-        }
-    }
-    // horizontal expand weights (2K = .1 .8 .1 / .5 .5, gausspyr_expand fvvdp_lpyr_dec.py:126-142,233); a
-    // neighbour outside the coarse row is the clamped (own) column, so its weight moves to the centre tap
-    const bool at_l = (J <= 0), at_r = (J >= wc - 1);
-    const float el = at_l ? 0.0f : 0.1f, er = at_r ? 0.0f : 0.1f;
-    const float ec = 0.8f + (at_l ? 0.1f : 0.0f) + (at_r ? 0.1f : 0.0f);
-    const float orr = at_r ? 0.0f : 0.5f;
-    const float oc = at_r ? 1.0f : 0.5f;
+    // horizontal reduce and expand weights of this lane's coarse column (pyramid_walk.hpp)
+    const ReduceW rq = lane_reduce_weights(J, wc, w, h);
+    const ExpandW ex = lane_expand_weights(J, wc);
 
     const float* Gf = l0_frame(a.F, frame);
     float* Gc = a.Gc + (size_t)frame * hc * wc * P;
@@ -296,13 +253,7 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
     const __amdgpu_buffer_rsrc_t Gf_rsrc = level_rsrc(const_cast<float*>(Gf), (unsigned int)(h * w * P) * 4u);    // <= 133 MB per frame
     const unsigned int col0_b = (unsigned int)xc0 * (P * 4u), col1_b = (unsigned int)xc1 * (P * 4u);
     const unsigned int row_b = (unsigned int)w * (P * 4u);
-    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) {
-        int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);   // symmetric padding (fvvdp_lpyr_dec.py:190-195)
-        rr = min(max(rr, 0), h - 1);
-        const unsigned int so = (unsigned int)rr * row_b;
-        p0 = ld_px_buf<P>(Gf_rsrc, col0_b, so);
-        p1 = ld_px_buf<P>(Gf_rsrc, col1_b, so);
-    };
+    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) { load_row_pair<P>(Gf_rsrc, col0_b, col1_b, row_b, h, r, p0, p1); };
 
     // The 5-row window of the vertical filter plus the two rows in flight for the next step live in a ring of 8 row slots
     // that is never moved: fine row r sits in slot (r - (2*ca - 4)) mod 8, and the main loop below is unrolled over the 4
@@ -313,28 +264,7 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
 
     // one coarse row from the window that starts in slot S0: vertical 5-tap in registers, horizontal 5-tap across lanes
     auto coarse_step = [&](auto S0) -> Px<P> {
-        constexpr int s0 = decltype(S0)::value;
-        Px<P> c, va, vb;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f a0 = R[s0][0].h[k] * K0;
-            a0 = pfma(R[(s0 + 1) & 7][0].h[k], K1, a0);
-            a0 = pfma(R[(s0 + 2) & 7][0].h[k], K2, a0);
-            a0 = pfma(R[(s0 + 3) & 7][0].h[k], K3, a0);
-            va.h[k] = pfma(R[(s0 + 4) & 7][0].h[k], K4, a0);
-            v2f b0 = R[s0][1].h[k] * K0;
-            b0 = pfma(R[(s0 + 1) & 7][1].h[k], K1, b0);
-            b0 = pfma(R[(s0 + 2) & 7][1].h[k], K2, b0);
-            b0 = pfma(R[(s0 + 3) & 7][1].h[k], K3, b0);
-            vb.h[k] = pfma(R[(s0 + 4) & 7][1].h[k], K4, b0);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f acc = va.h[k] * wq2;
-            acc = pfma(vb.h[k], wq3, acc);
-            c.h[k] = dpp_reduce_taps(acc, va.h[k], vb.h[k], wq0, wq1, wq4);
-        }
-        return c;
+        return reduce5_ring<P, decltype(S0)::value>(R, rq.q0, rq.q1, rq.q2, rq.q3, rq.q4);
     };
 
     // ---- prologue: coarse rows ca-1 and ca --------------------------------------------------------------
@@ -484,28 +414,16 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         }
         const float vm = valid ? 1.0f : 0.0f;
         const float lcn = lg_bm - llb;                                   // log2(m / lb)
-        // D = |T'-R'|^p / (1 + (k*min(|T'|,|R'|))^q), T' = T*S   (fvvdp.py:585-595), in the log2 domain.
-        // Video: the two temporal channels are carried as one (sustained, transient) pair through packed fp32 ops;
-        // only the transcendentals are per component.
+        // masking and pooling in the log2 domain (pyramid_walk.hpp)
         float ldd_dbg[2] = {0.0f, 0.0f};
         if constexpr (HP == 2) {
             const v2f sl = v2f{slog[0], slog[1]};
-            const v2f A = pfma(sl, pb, splat(fmaf(lcn, pb, pb_base)));   // beta * p * log2(S * m / lb)
-            const v2f lsm = sl + splat(lcn + lg_mask);                   // log2(k * S * m / lb)
-            const v2f ldiff = v2f{fast_log2(fabsf(d[0].x - d[0].y)), fast_log2(fabsf(d[1].x - d[1].y))};
-            const v2f lmin = v2f{fast_log2(fminf(fabsf(d[0].x), fabsf(d[0].y))), fast_log2(fminf(fabsf(d[1].x), fabsf(d[1].y)))};
-            const v2f ldb = pfma(ldiff, pb, A);                           // beta * p * (log2|T'-R'|)
-            const v2f lm = (lmin + lsm) * v2f{a.q0, a.q1};
-            const v2f one_mq = v2f{fast_exp2(lm.x), fast_exp2(lm.y)} + splat(1.0f);
-            const v2f tb = pfma(v2f{fast_log2(one_mq.x), fast_log2(one_mq.y)}, -a.beta, ldb);   // beta * log2 D
-            const v2f bl = v2f{fminf(tb.x, b_dmax), fminf(tb.y, b_dmax)};                      // D <= d_max
-            const v2f term = v2f{fast_exp2(bl.x), fast_exp2(bl.y)};      // D^beta for the spatial pooling (fvvdp.py:467,607)
-            const v2f av = __builtin_elementwise_fma(term, splat(vm), v2f{acc[0], acc[1]});
-            acc[0] = av.x;
-            acc[1] = av.y;
+            v2f bl;
+            PYRAMID_MASK_POOL_VIDEO(sl, fmaf(lcn, pb, pb_base), lcn + lg_mask, d[0], d[1], pb, a.q0, a.q1, a.beta, b_dmax, vm, acc, bl);
             ldd_dbg[0] = bl.x * inv_beta;
             ldd_dbg[1] = bl.y * inv_beta;
         } else {
+            // one channel: a kept copy, see pyramid_walk.hpp
             const float dT = d[0].x, dR = d[0].y;
             const float ls = slog[0] + lcn;
             const float ld = a.p * (fast_log2(fabsf(dT - dR)) + (ls + lg_base));
@@ -599,20 +517,10 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         const float lcn = lg_bm - q.llb;
         if constexpr (HP == 2) {
             const v2f sl = v2f{s0, s1};
-            const v2f A = pfma(sl, pb, splat(fmaf(lcn, pb, pb_base)));
-            const v2f lsm = sl + splat(lcn + lg_mask);
-            const v2f ldiff = v2f{fast_log2(fabsf(q.d[0].x - q.d[0].y)), fast_log2(fabsf(q.d[1].x - q.d[1].y))};
-            const v2f lmin = v2f{fast_log2(fminf(fabsf(q.d[0].x), fabsf(q.d[0].y))), fast_log2(fminf(fabsf(q.d[1].x), fabsf(q.d[1].y)))};
-            const v2f ldb = pfma(ldiff, pb, A);
-            const v2f lm = (lmin + lsm) * v2f{a.q0, a.q1};
-            const v2f one_mq = v2f{fast_exp2(lm.x), fast_exp2(lm.y)} + splat(1.0f);
-            const v2f tb = pfma(v2f{fast_log2(one_mq.x), fast_log2(one_mq.y)}, -a.beta, ldb);
-            const v2f bl = v2f{fminf(tb.x, b_dmax), fminf(tb.y, b_dmax)};
-            const v2f term = v2f{fast_exp2(bl.x), fast_exp2(bl.y)};
-            const v2f av = __builtin_elementwise_fma(term, splat(vm), v2f{acc[0], acc[1]});
-            acc[0] = av.x;
-            acc[1] = av.y;
+            v2f bl;
+            PYRAMID_MASK_POOL_VIDEO(sl, fmaf(lcn, pb, pb_base), lcn + lg_mask, q.d[0], q.d[1], pb, a.q0, a.q1, a.beta, b_dmax, vm, acc, bl);
         } else {
+            // one channel: a kept copy, see pyramid_walk.hpp
             const float dT = q.d[0].x, dR = q.d[0].y;
             const float ls = s0 + lcn;
             const float ld = a.p * (fast_log2(fabsf(dT - dR)) + (ls + lg_base));
@@ -663,24 +571,7 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         Px<P> Gp1 = has_next ? cN : G0;       // index clamp of the expand (fvvdp_lpyr_dec.py:134,138)
         st_px(Gc_rsrc, (has_next && (c + 1) < cb && active) ? (unsigned int)((c + 1) * wc + J) * (P * 4u) : FVVDP_NO_STORE, cN);
         Px<P> x00, x01, x10, x11;             // expanded level at (row 2c|2c+1, col X0|X1)
-        Px<P> evE, evO;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            // vertical expand on the coarse column: even fine row 2c (.1 .8 .1), odd fine row 2c+1 (.5 .5)
-            v2f t = Gm1.h[k] * 0.1f;
-            t = pfma(G0.h[k], 0.8f, t);
-            evE.h[k] = pfma(Gp1.h[k], 0.1f, t);
-            evO.h[k] = pfma(Gp1.h[k], 0.5f, G0.h[k] * 0.5f);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            x00.h[k] = evE.h[k] * ec;
-            x01.h[k] = evE.h[k] * oc;
-            dpp_expand_taps(evE.h[k], el, er, orr, x00.h[k], x01.h[k]);
-            x10.h[k] = evO.h[k] * ec;
-            x11.h[k] = evO.h[k] * oc;
-            dpp_expand_taps(evO.h[k], el, er, orr, x10.h[k], x11.h[k]);
-        }
+        PYRAMID_EXPAND_ROWS(HP, Gm1, G0, Gp1, ex.el, ex.er, ex.ec, ex.orr, ex.oc, x00, x01, x10, x11);
         const bool row1_ok = (2 * c + 1) < h;
         float vy0 = 0.0f, vy1 = 0.0f;        // vertical view angle of the two fine rows (foveated)
         if constexpr (FOV) {
@@ -746,15 +637,7 @@ __device__ __forceinline__ void band_item(const BandArgs& a, const int strip, co
         Gm1 = G0;
         G0 = Gp1;
     };
-    for (int c = ca; c < cb; c += 4) {        // wave-uniform trip count
-        step(integral_constant<int, 0>(), c);
-        if (c + 1 >= cb) break;
-        step(integral_constant<int, 1>(), c + 1);
-        if (c + 2 >= cb) break;
-        step(integral_constant<int, 2>(), c + 2);
-        if (c + 3 >= cb) break;
-        step(integral_constant<int, 3>(), c + 3);
-    }
+    PYRAMID_WALK_STEPS(step, ca, cb);
 
     const float s0 = wave_sum(acc[0]);
     const float s1 = wave_sum(acc[1]);
@@ -816,8 +699,7 @@ __global__ __launch_bounds__(FOVM ? 64 * FOV_WPB : 64, FOVM ? (FOVM == 1 ? FOV_M
     // which share their 4+4 halo columns, run on the same XCD at about the same time and hit in its L2.
     int bid;
     {
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;
-        bid = x * q8 + min(x, r8) + (blockIdx.x >> 3);
+        bid = xcd_work_order(blockIdx.x, (int)gridDim.x);
         // the wave number is the same in all lanes: say so, otherwise every quantity derived from the work item (rows,
         // loop counter, row addresses, the store descriptor) lives in vector registers and is recomputed by the VALU
         if constexpr (FOV) bid = bid * WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));

@@ -7,8 +7,8 @@
 //   gaze-invariant: row loads, reduce, expand, the coarse-level store, the contrast differences and their clamp, log2(L_bkg),
 //                   the Y axis of the CSF query, the rho-map record, the logs of |T - R| and min(|T|, |R|);
 //   per gaze:       eccentricity -> ecc axis of the query -> the four cells of the LUT slice -> interp3 -> the masking tail.
-// multigaze_kernel walks the level exactly as band_item does (same strips, chunks, lanes, row ring, LDS tables, FOV_WPB waves
-// per workgroup) and evaluates the first kind once, the second once per gaze g of the group into that gaze's acc[g][2].
+// multigaze_kernel walks the level with band_item's own walk (pyramid_walk.hpp: weights, row loads, reduce, expand, step driver;
+// same strips, chunks, lanes, row ring, LDS tables, FOV_WPB waves per workgroup) and evaluates the first kind once, the second once per gaze g of the group into that gaze's acc[g][2].
 //
 // Bit identity with band_kernel<P, false, 1> run once per gaze is the contract (tests/test_gpu_gazes.py).  A gaze's
 // accumulators see the same adds in the same order (pixels (2c, X0), (2c, X1), (2c+1, X0), (2c+1, X1) of every step), so its
@@ -56,31 +56,9 @@ __device__ __forceinline__ void multigaze_item(const MultiGazeArgs& ga, const in
     const int xc0 = min(max(X0, 0), w - 1), xc1 = min(max(X1, 0), w - 1);
     const bool col1_ok = X1 < w;
 
-    // reduce / expand weights of this lane's column: band_item, same expressions
-    const float K0 = 0.05f, K1 = 0.25f, K2 = 0.4f, K3 = 0.25f, K4 = 0.05f;
-    float wq0 = K0, wq1 = K1, wq2 = K2, wq3 = K3, wq4 = K4;
-    if (J == 0) {
-        wq2 += K1;
-        wq3 += K0;
-        wq0 = 0.0f;
-        wq1 = 0.0f;
-    }
-    if (J == wc - 1) {
-        const bool hodd = (h & 1) != 0;
-        if (w & 1) {
-            wq3 = 0.0f;
-            wq4 = 0.0f;
-            if (hodd) { wq2 += K3; wq1 += K4; } else { wq2 += K4; }
-        } else {
-            wq4 = 0.0f;
-            if (hodd) { wq3 += K3; wq2 += K4; } else { wq3 += K4; }
-        }
-    }
-    const bool at_l = (J <= 0), at_r = (J >= wc - 1);
-    const float el = at_l ? 0.0f : 0.1f, er = at_r ? 0.0f : 0.1f;
-    const float ec = 0.8f + (at_l ? 0.1f : 0.0f) + (at_r ? 0.1f : 0.0f);
-    const float orr = at_r ? 0.0f : 0.5f;
-    const float oc = at_r ? 1.0f : 0.5f;
+    // reduce / expand weights of this lane's column (pyramid_walk.hpp, as every pyramid kernel)
+    const ReduceW rq = lane_reduce_weights(J, wc, w, h);
+    const ExpandW ex = lane_expand_weights(J, wc);
 
     const float* Gf = l0_frame(a.F, frame);
     float* Gc = a.Gc + (size_t)frame * hc * wc * P;
@@ -89,39 +67,12 @@ __device__ __forceinline__ void multigaze_item(const MultiGazeArgs& ga, const in
     const unsigned int col0_b = (unsigned int)xc0 * (P * 4u), col1_b = (unsigned int)xc1 * (P * 4u);
     const unsigned int row_b = (unsigned int)w * (P * 4u);
     const bool may_store = active && ga.store_coarse != 0;
-    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) {
-        int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);
-        rr = min(max(rr, 0), h - 1);
-        const unsigned int so = (unsigned int)rr * row_b;
-        p0 = ld_px_buf<P>(Gf_rsrc, col0_b, so);
-        p1 = ld_px_buf<P>(Gf_rsrc, col1_b, so);
-    };
+    auto load_row = [&](int r, Px<P>& p0, Px<P>& p1) { load_row_pair<P>(Gf_rsrc, col0_b, col1_b, row_b, h, r, p0, p1); };
 
-    Px<P> R[8][2];                  // the 8-slot row ring of band_item
+    Px<P> R[8][2];                  // the 8-slot row ring (see band_item)
     using std::integral_constant;
     auto coarse_step = [&](auto S0) -> Px<P> {
-        constexpr int s0 = decltype(S0)::value;
-        Px<P> c, va, vb;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f a0 = R[s0][0].h[k] * K0;
-            a0 = pfma(R[(s0 + 1) & 7][0].h[k], K1, a0);
-            a0 = pfma(R[(s0 + 2) & 7][0].h[k], K2, a0);
-            a0 = pfma(R[(s0 + 3) & 7][0].h[k], K3, a0);
-            va.h[k] = pfma(R[(s0 + 4) & 7][0].h[k], K4, a0);
-            v2f b0 = R[s0][1].h[k] * K0;
-            b0 = pfma(R[(s0 + 1) & 7][1].h[k], K1, b0);
-            b0 = pfma(R[(s0 + 2) & 7][1].h[k], K2, b0);
-            b0 = pfma(R[(s0 + 3) & 7][1].h[k], K3, b0);
-            vb.h[k] = pfma(R[(s0 + 4) & 7][1].h[k], K4, b0);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f acc = va.h[k] * wq2;
-            acc = pfma(vb.h[k], wq3, acc);
-            c.h[k] = dpp_reduce_taps(acc, va.h[k], vb.h[k], wq0, wq1, wq4);
-        }
-        return c;
+        return reduce5_ring<P, decltype(S0)::value>(R, rq.q0, rq.q1, rq.q2, rq.q3, rq.q4);
     };
 
     // ---- prologue: coarse rows ca-1 and ca
@@ -236,17 +187,12 @@ __device__ __forceinline__ void multigaze_item(const MultiGazeArgs& ga, const in
             const v2f sl = v2f{s0, s1};
             const v2f A = pfma(sl, pb, splat(q.cA));
             const v2f lsm = sl + splat(q.cL);
-            const v2f ldb = pfma(v2f{q.ldiff[0], q.ldiff[1]}, pb, A);
-            const v2f lm = (v2f{q.lmin[0], q.lmin[1]} + lsm) * v2f{a.q0, a.q1};
-            const v2f one_mq = v2f{fast_exp2(lm.x), fast_exp2(lm.y)} + splat(1.0f);
-            const v2f tb = pfma(v2f{fast_log2(one_mq.x), fast_log2(one_mq.y)}, -a.beta, ldb);
-            const v2f bl = v2f{fminf(tb.x, b_dmax), fminf(tb.y, b_dmax)};
-            const v2f term = v2f{fast_exp2(bl.x), fast_exp2(bl.y)};
-            const v2f av = __builtin_elementwise_fma(term, splat(vm), v2f{ac[0], ac[1]});
-            ac[0] = av.x;
-            ac[1] = av.y;
+            const v2f ldiff = v2f{q.ldiff[0], q.ldiff[1]}, lmin = v2f{q.lmin[0], q.lmin[1]};
+            v2f bl;
+            PYRAMID_MASK_POOL_PAIR(A, lsm, ldiff, lmin, pb, a.q0, a.q1, a.beta, b_dmax, vm, ac, bl);
         } else {
             (void)s1;
+            // one channel: a kept copy, see pyramid_walk.hpp
             const float ls = s0 + q.lcn;
             const float mq = fast_exp2(a.q0 * (q.lmin[0] + (ls + lg_mask)));
             // band_item: ld = p * (...); ldd = fminf(ld - log2(1 + mq), lg_dmax), the product fused into the difference
@@ -271,23 +217,7 @@ __device__ __forceinline__ void multigaze_item(const MultiGazeArgs& ga, const in
         Px<P> Gp1 = has_next ? cN : G0;
         st_px(Gc_rsrc, (has_next && (c + 1) < cb && may_store) ? (unsigned int)((c + 1) * wc + J) * (P * 4u) : FVVDP_NO_STORE, cN);
         Px<P> x00, x01, x10, x11;
-        Px<P> evE, evO;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f t = Gm1.h[k] * 0.1f;
-            t = pfma(G0.h[k], 0.8f, t);
-            evE.h[k] = pfma(Gp1.h[k], 0.1f, t);
-            evO.h[k] = pfma(Gp1.h[k], 0.5f, G0.h[k] * 0.5f);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            x00.h[k] = evE.h[k] * ec;
-            x01.h[k] = evE.h[k] * oc;
-            dpp_expand_taps(evE.h[k], el, er, orr, x00.h[k], x01.h[k]);
-            x10.h[k] = evO.h[k] * ec;
-            x11.h[k] = evO.h[k] * oc;
-            dpp_expand_taps(evO.h[k], el, er, orr, x10.h[k], x11.h[k]);
-        }
+        PYRAMID_EXPAND_ROWS(HP, Gm1, G0, Gp1, ex.el, ex.er, ex.ec, ex.orr, ex.oc, x00, x01, x10, x11);
         const bool row1_ok = (2 * c + 1) < h;
         const float* s_vy = reinterpret_cast<const float*>(s_lut_dyn + FOV_PLANE * a.rw);
         const float vy0 = s_vy[2 * c];
@@ -323,15 +253,7 @@ __device__ __forceinline__ void multigaze_item(const MultiGazeArgs& ga, const in
         Gm1 = G0;
         G0 = Gp1;
     };
-    for (int c = ca; c < cb; c += 4) {
-        step(integral_constant<int, 0>(), c);
-        if (c + 1 >= cb) break;
-        step(integral_constant<int, 1>(), c + 1);
-        if (c + 2 >= cb) break;
-        step(integral_constant<int, 2>(), c + 2);
-        if (c + 3 >= cb) break;
-        step(integral_constant<int, 3>(), c + 3);
-    }
+    PYRAMID_WALK_STEPS(step, ca, cb);
 
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
@@ -354,8 +276,7 @@ __global__ __launch_bounds__(64 * FOV_WPB, MG_MINW) void multigaze_kernel(const 
     const int lane = (int)(threadIdx.x & 63);
     int bid;
     {
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;      // XCD-aware work order, as band_kernel
-        bid = x * q8 + min(x, r8) + (blockIdx.x >> 3);
+        bid = xcd_work_order(blockIdx.x, (int)gridDim.x);
         bid = bid * FOV_WPB + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     }
     const bool wave_has_work = bid < a.n_items;

@@ -12,7 +12,8 @@
 //   per stream:     row loads, reduce, expand, the coarse-level store, the contrast difference g - e and its upper clamp;
 //   reference only: L_bkg and its clamp, cmax * L_bkg, log2(L_bkg), the look-up of the 1-D CSF table for both temporal
 //                   channels, and every term of the log-domain tail that does not involve the test.
-// multitest_kernel walks the level exactly as band_item does (same strips, chunks, lanes, row ring, single-wave workgroups) over
+// multitest_kernel walks the level with band_item's own walk (pyramid_walk.hpp: weights, reduce, expand, step driver, the
+// two-channel tail; same strips, chunks, lanes, row ring, single-wave workgroups) over
 // the NQ quads at once and evaluates the reference-only part once per pixel; per test it runs that stream's contrast difference
 // and the masking / pooling tail into the test's own acc[2].
 //
@@ -76,31 +77,9 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
     const int xc0 = min(max(X0, 0), w - 1), xc1 = min(max(X1, 0), w - 1);
     const bool col1_ok = X1 < w;
 
-    // reduce / expand weights of this lane's column: band_item, same expressions
-    const float K0 = 0.05f, K1 = 0.25f, K2 = 0.4f, K3 = 0.25f, K4 = 0.05f;
-    float wq0 = K0, wq1 = K1, wq2 = K2, wq3 = K3, wq4 = K4;
-    if (J == 0) {
-        wq2 += K1;
-        wq3 += K0;
-        wq0 = 0.0f;
-        wq1 = 0.0f;
-    }
-    if (J == wc - 1) {
-        const bool hodd = (h & 1) != 0;
-        if (w & 1) {
-            wq3 = 0.0f;
-            wq4 = 0.0f;
-            if (hodd) { wq2 += K3; wq1 += K4; } else { wq2 += K4; }
-        } else {
-            wq4 = 0.0f;
-            if (hodd) { wq3 += K3; wq2 += K4; } else { wq3 += K4; }
-        }
-    }
-    const bool at_l = (J <= 0), at_r = (J >= wc - 1);
-    const float el = at_l ? 0.0f : 0.1f, er = at_r ? 0.0f : 0.1f;
-    const float ec = 0.8f + (at_l ? 0.1f : 0.0f) + (at_r ? 0.1f : 0.0f);
-    const float orr = at_r ? 0.0f : 0.5f;
-    const float oc = at_r ? 1.0f : 0.5f;
+    // reduce / expand weights of this lane's column (pyramid_walk.hpp, as every pyramid kernel)
+    const ReduceW rq = lane_reduce_weights(J, wc, w, h);
+    const ExpandW ex = lane_expand_weights(J, wc);
 
     __amdgpu_buffer_rsrc_t Gf_rsrc[NQ], Gc_rsrc[NQ];
     bool may_store[NQ];
@@ -120,9 +99,7 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
     using std::integral_constant;
     auto load_row = [&](int r, auto SLOT) {
         constexpr int s = decltype(SLOT)::value;
-        int rr = r < 0 ? -1 - r : (r >= h ? 2 * h - 1 - r : r);
-        rr = min(max(rr, 0), h - 1);
-        const unsigned int so = (unsigned int)rr * row_b;
+        const unsigned int so = (unsigned int)reflect_row(r, h) * row_b;      // one row offset for all quads
 #pragma unroll
         for (int j = 0; j < NQ; ++j) {
             R[j][s][0] = ld_px_buf<P>(Gf_rsrc[j], col0_b, so);
@@ -130,28 +107,7 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
         }
     };
     auto coarse_step = [&](const int j, auto S0) -> Px<P> {
-        constexpr int s0 = decltype(S0)::value;
-        Px<P> c, va, vb;
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f a0 = R[j][s0][0].h[k] * K0;
-            a0 = pfma(R[j][(s0 + 1) & 7][0].h[k], K1, a0);
-            a0 = pfma(R[j][(s0 + 2) & 7][0].h[k], K2, a0);
-            a0 = pfma(R[j][(s0 + 3) & 7][0].h[k], K3, a0);
-            va.h[k] = pfma(R[j][(s0 + 4) & 7][0].h[k], K4, a0);
-            v2f b0 = R[j][s0][1].h[k] * K0;
-            b0 = pfma(R[j][(s0 + 1) & 7][1].h[k], K1, b0);
-            b0 = pfma(R[j][(s0 + 2) & 7][1].h[k], K2, b0);
-            b0 = pfma(R[j][(s0 + 3) & 7][1].h[k], K3, b0);
-            vb.h[k] = pfma(R[j][(s0 + 4) & 7][1].h[k], K4, b0);
-        }
-#pragma unroll
-        for (int k = 0; k < HP; ++k) {
-            v2f acc = va.h[k] * wq2;
-            acc = pfma(vb.h[k], wq3, acc);
-            c.h[k] = dpp_reduce_taps(acc, va.h[k], vb.h[k], wq0, wq1, wq4);
-        }
-        return c;
+        return reduce5_ring<P, decltype(S0)::value>(R[j], rq.q0, rq.q1, rq.q2, rq.q3, rq.q4);
     };
 
     // ---- prologue: coarse rows ca-1 and ca of every quad
@@ -224,15 +180,8 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
         const v2f ldiff = v2f{fast_log2(fabsf(dT.x - q.dR.x)), fast_log2(fabsf(dT.y - q.dR.y))};
         const v2f lmin = v2f{fast_log2(fminf(fabsf(dT.x), fabsf(q.dR.x))), fast_log2(fminf(fabsf(dT.y), fabsf(q.dR.y)))};
         const float vm = valid ? 1.0f : 0.0f;
-        const v2f ldb = pfma(ldiff, pb, q.A);
-        const v2f lm = (lmin + q.lsm) * v2f{a.q0, a.q1};
-        const v2f one_mq = v2f{fast_exp2(lm.x), fast_exp2(lm.y)} + splat(1.0f);
-        const v2f tb = pfma(v2f{fast_log2(one_mq.x), fast_log2(one_mq.y)}, -a.beta, ldb);
-        const v2f bl = v2f{fminf(tb.x, b_dmax), fminf(tb.y, b_dmax)};
-        const v2f term = v2f{fast_exp2(bl.x), fast_exp2(bl.y)};
-        const v2f av = __builtin_elementwise_fma(term, splat(vm), v2f{ac[0], ac[1]});
-        ac[0] = av.x;
-        ac[1] = av.y;
+        v2f bl;
+        PYRAMID_MASK_POOL_PAIR(q.A, q.lsm, ldiff, lmin, pb, a.q0, a.q1, a.beta, b_dmax, vm, ac, bl);
     };
     // one band pixel of every quad: g[j] the level value, e[j] the expanded coarse level
     auto band_px = [&](const Px<P> (&g)[NQ], const Px<P> (&e)[NQ], bool valid, auto COL) {
@@ -259,23 +208,7 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
             const Px<P> cN = coarse_step(j, integral_constant<int, s0>());
             Gp1[j] = has_next ? cN : G0[j];
             st_px(Gc_rsrc[j], (has_next && (c + 1) < cb && may_store[j]) ? (unsigned int)((c + 1) * wc + J) * (P * 4u) : FVVDP_NO_STORE, cN);
-            Px<P> evE, evO;
-#pragma unroll
-            for (int k = 0; k < HP; ++k) {
-                v2f t = Gm1[j].h[k] * 0.1f;
-                t = pfma(G0[j].h[k], 0.8f, t);
-                evE.h[k] = pfma(Gp1[j].h[k], 0.1f, t);
-                evO.h[k] = pfma(Gp1[j].h[k], 0.5f, G0[j].h[k] * 0.5f);
-            }
-#pragma unroll
-            for (int k = 0; k < HP; ++k) {
-                x00[j].h[k] = evE.h[k] * ec;
-                x01[j].h[k] = evE.h[k] * oc;
-                dpp_expand_taps(evE.h[k], el, er, orr, x00[j].h[k], x01[j].h[k]);
-                x10[j].h[k] = evO.h[k] * ec;
-                x11[j].h[k] = evO.h[k] * oc;
-                dpp_expand_taps(evO.h[k], el, er, orr, x10[j].h[k], x11[j].h[k]);
-            }
+            PYRAMID_EXPAND_ROWS(HP, Gm1[j], G0[j], Gp1[j], ex.el, ex.er, ex.ec, ex.orr, ex.oc, x00[j], x01[j], x10[j], x11[j]);
         }
         const bool row1_ok = (2 * c + 1) < h;
         Px<P> w00[NQ], w01[NQ], w10[NQ], w11[NQ];
@@ -296,15 +229,7 @@ __device__ __forceinline__ void multitest_item(const MultiTestArgs& ma, const in
             G0[j] = Gp1[j];
         }
     };
-    for (int c = ca; c < cb; c += 4) {
-        step(integral_constant<int, 0>(), c);
-        if (c + 1 >= cb) break;
-        step(integral_constant<int, 1>(), c + 1);
-        if (c + 2 >= cb) break;
-        step(integral_constant<int, 2>(), c + 2);
-        if (c + 3 >= cb) break;
-        step(integral_constant<int, 3>(), c + 3);
-    }
+    PYRAMID_WALK_STEPS(step, ca, cb);
 
     // the partial sums of every test into its own row, where band_kernel puts them
     const size_t o_blk = ((size_t)frame * (a.n_strips * a.n_chunks) + blk) * 2;
@@ -346,8 +271,7 @@ __global__ __launch_bounds__(64, mt_minw<NQ>()) void multitest_kernel(const Mult
     const int lane = (int)threadIdx.x;
     int bid;
     {
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7;      // XCD-aware work order, as band_kernel
-        bid = x * q8 + min(x, r8) + (blockIdx.x >> 3);
+        bid = xcd_work_order(blockIdx.x, (int)gridDim.x);
     }
     const int strip = bid % a.n_strips;
     bid /= a.n_strips;

@@ -327,12 +327,29 @@ IMAGES_RESIZE_SYMBOLS = {
 }
 RESIZE_MAX_AXIS = 32768                  # FVVDP_RESIZE_MAX_AXIS
 
+# include/fvvdp_hip_resize_held.h: clips whose streams have frame sizes and frame counts of their own -- the resizing ingest with a
+# window list per stream, and the resize's adjoint behind the transpose of the hold (bound by lib() as well)
+RESIZE_HELD_SYMBOLS = {
+    "fvvdp_temporal_channels_resized_held": (C.c_int, [C.c_void_p, C.POINTER(ResizeStream), C.POINTER(ResizeStream), C.c_int, C.c_int,
+                                                       C.c_int, C.POINTER(Eotf), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                                       C.c_void_p]),
+    "fvvdp_resize_grad_held": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(ResizeStream),
+                                         C.c_void_p, C.c_int, C.POINTER(Eotf), C.POINTER(C.c_float), C.c_void_p, C.c_size_t,
+                                         C.c_void_p]),
+}
+
+
+def resize_grad_held_table_bytes(width, height, n_source):
+    """FVVDP_RESIZE_GRAD_HELD_TABLE_BYTES"""
+    return ((2 * (width + height) + n_source + 1) * 4 + 255) // 256 * 256
+
 
 _lib = None
 
 
 def build(force=False, verbose=False):
-    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-six translation units -- the band /
+    """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-seven translation units -- the band /
     pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them;
     their launch plans and bounds are the host-only header pyramid_host.hpp, the strip constants pyramid_constants.hpp), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
@@ -342,7 +359,7 @@ def build(force=False, verbose=False):
     respect to the display's photometry (display_grad_launch.hip), the gradients of the difference map (map_grad_launch.hip), the
     float YUV planes with their gradients (yuv_grad_launch.hip), the gradients of many tests with respect to their one reference
     (tests_grad_launch.hip), the clips resized inside the ingest with the resize's adjoint (resize_launch.hip), the still images
-    resized inside their ingest (images_resize_launch.hip) and the clips with held frames (held_launch.hip with -DHELD_PART=0..5: the ingest per sample type, then the C ABI with the backward's kernel) -- are
+    resized inside their ingest (images_resize_launch.hip), the resized clips shown through frame maps (resize_held_launch.hip) and the clips with held frames (held_launch.hip with -DHELD_PART=0..5: the ingest per sample type, then the C ABI with the backward's kernel) -- are
     compiled concurrently and linked into one shared library."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc) if not f.startswith("_")] + [os.path.join(INCLUDE_DIR, h) for h in ("fvvdp_hip.h", "fvvdp_hip_images.h", "fvvdp_hip_grad.h",
@@ -350,7 +367,8 @@ def build(force=False, verbose=False):
                                                                                                                               "fvvdp_hip_ref_grad.h", "fvvdp_hip_params.h", "fvvdp_hip_taps.h",
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
                                                                                                                               "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h",
-                                                                                                                              "fvvdp_hip_resize.h", "fvvdp_hip_held.h", "fvvdp_hip_images_resize.h")]
+                                                                                                                              "fvvdp_hip_resize.h", "fvvdp_hip_held.h", "fvvdp_hip_images_resize.h",
+                                                                                                                              "fvvdp_hip_resize_held.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -403,6 +421,9 @@ def build(force=False, verbose=False):
     # -ffp-contract=off as resize_launch.hip: the ingest evaluates the functions that unit's adjoint recomputes, and the two stacks
     # are two copies of scalar code -- all must round alike
     units += [(os.path.join(csrc, "images_resize_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "images_resize_launch.o"))]
+    # clips resized inside the ingest AND shown through frame maps (include/fvvdp_hip_resize_held.h): the hold variants of
+    # resize_launch.hip's kernels.  -ffp-contract=off as that unit: a reused luminance must be the value the unit beside it computes
+    units += [(os.path.join(csrc, "resize_held_launch.hip"), ["-ffp-contract=off"], os.path.join(objdir, "resize_held_launch.o"))]
     procs = []
     for src, extra, obj in units:
         cmd = [hipcc] + flags + extra + ["-c", src, "-o", obj]
@@ -432,7 +453,8 @@ def lib():
                 list(REF_GRAD_SYMBOLS.items()) + list(PARAM_SYMBOLS.items()) + list(TAP_SYMBOLS.items()) + \
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
                 list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()) + \
-                list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()) + list(IMAGES_RESIZE_SYMBOLS.items()):
+                list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()) + list(IMAGES_RESIZE_SYMBOLS.items()) + \
+                list(RESIZE_HELD_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -414,7 +414,7 @@ class fvvdp:
                              fixation_point, full_screen_resize)
 
     def predict_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCFHW",
-                        frames_per_second=30, fixation_point=None):
+                        frames_per_second=30, fixation_point=None, test_frames=1, reference_frames=1):
         """Extension: predict for a test and a reference clip that each have a frame size of their OWN -- a bitrate-ladder rung,
         a render-resolution sweep or a super-resolution output shown full screen.  Both clips have the same frame and channel
         counts (C = 1 or 3) and are float32, or uint8 scaled by 1/255, on host or device, in any `dim_order` predict takes.
@@ -428,13 +428,21 @@ class fvvdp:
         absolute), every temporal padding, foveated or not (`fixation_point` in target pixels), clips of at least 2 frames,
         temporal filters of up to 32 taps (120 frames per second).  Refused, each with a sentence and before any device work: an
         unknown mode, half-precision, float64 or 16-bit samples, a look-up-table or user photometry, differing frame or channel
-        counts, longer filters, single images."""
+        counts, longer filters, single images.
+        `test_frames` / `reference_frames` (predict_held's keywords, with predict_held's meaning: an int k -- display frame v
+        shows frame v // k -- or a non-decreasing integer sequence with one entry per display frame) give each stream a frame
+        COUNT of its own as well: a rung at half the resolution AND half the rate.  The result equals predict_resized on
+        test.index_select(frames, m_t) and reference.index_select(frames, m_r) bit for bit (JOD and Q_per_ch), no expanded clip
+        is made, and a held frame is interpolated and sent through the display model once.  `frames_per_second`, the temporal
+        padding and `fixation_point` then refer to display frames, and stats['N_frames'] is their count (at least 2; a stream
+        may have a single frame).  Map errors are predict_held's ValueErrors.  Left at 1, or with identity maps on equal frame
+        counts, the call is the one described above; non-trivial maps on two clips of the target size are predict_held's."""
         from .resize_grad import predict_resized
         return predict_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
-                               fixation_point)
+                               fixation_point, test_frames, reference_frames)
 
     def jod_video_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCFHW",
-                          frames_per_second=30, fixation_point=None):
+                          frames_per_second=30, fixation_point=None, test_frames=1, reference_frames=1):
         """Extension: jod_video for clips with frame sizes of their own (see predict_resized for the resize), for losses such as
         `10 - metric.jod_video_resized(net(x_small), ref_full, frames_per_second=30)`.  Returns the JOD as a 0-d fp32 tensor on the
         metric's device; under torch.no_grad() it equals predict_resized's bit for bit.  When `test` (float32) requires grad,
@@ -443,10 +451,16 @@ class fvvdp:
         `self.grad_batch` and repeats bit for bit.  A sample gets an exact zero where every target pixel it reaches is clipped or
         clamped by the display model, where a downscale skips it, and in a frame no temporal window shows.  The reference (float32
         or uint8) is a constant; one that requires grad is refused.  When both clips already have the target size the call is
-        jod_video's.  Double backward is not supported."""
+        jod_video's.  Double backward is not supported.
+        `test_frames` / `reference_frames`: as predict_resized takes them, for losses such as
+        `10 - metric.jod_video_resized(net(x_540p30), ref_2160p60, frames_per_second=60, test_frames=2)`.  The JOD has
+        predict_resized's bits, and backward() puts the adjoint of exactly that function -- hold, resize, clip -- into the
+        caller's tensor at the test's own resolution AND own frame count: the luminance gradient is summed over the display
+        frames that show a source frame (ascending, no atomics) before the resize's adjoint runs once per source frame.  A
+        frame no display frame shows gets exact zeros."""
         from .resize_grad import jod_video_resized
         return jod_video_resized(self, test, reference, full_screen_resize, resize_resolution, dim_order, frames_per_second,
-                                 fixation_point)
+                                 fixation_point, test_frames, reference_frames)
 
     def predict_images_resized(self, test, reference, full_screen_resize="bilinear", resize_resolution=None, dim_order="BCHW",
                                fixation_point=None):

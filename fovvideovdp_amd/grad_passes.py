@@ -332,6 +332,27 @@ class ResizedClipSetup(ClipSetup):
                                                       nat.fptr(self.taps), self.fl, nb, 0, self.stream))
 
 
+class ResizedHeldClipSetup(ResizedClipSetup):
+    """ResizedClipSetup for a pair of clips with frame sizes AND frame counts of their own (resize_grad, with test_frames= /
+    reference_frames=): t and r are [C, F_s, h, w] device tensors, m_t and m_r the frame maps (int32 [N]: display frame -> source
+    frame).  As in HeldClipSetup self.N is the number of DISPLAY frames, at whose rate the window list, the schedule and the gaze
+    run; the ingest is fvvdp_temporal_channels_resized_held on the window list sent through each stream's map."""
+
+    def __init__(self, metric, t, fps, r, mode, size, m_t, m_r, prm=None, pp=None):
+        self.t, self.r, self.mode, self.C = t, r, mode, t.shape[0]
+        self.m_t, self.m_r = np.ascontiguousarray(m_t, dtype=np.int32), np.ascontiguousarray(m_r, dtype=np.int32)
+        self._clip(metric, len(self.m_t), size[0], size[1], fps, 4, torch.float32, prm=prm, pp=pp)
+        self.idx_t, self.idx_r = self.m_t[self.widx], self.m_r[self.widx]      # the per-stream lists handed to the ingest
+
+    def ingest(self, lib, t, r, b0, nb, oob):
+        i32p = C.POINTER(C.c_int32)
+        it, ir = self.window(b0, nb, self.idx_t), self.window(b0, nb, self.idx_r)
+        ts, rs = resize_stream(t), resize_stream(r)
+        nat.check(lib.fvvdp_temporal_channels_resized_held(self.ctx.handle, C.byref(ts), C.byref(rs), t.shape[1], r.shape[1], self.mode,
+                                                           C.byref(self.e), nat.fptr(self.w), it.ctypes.data_as(i32p),
+                                                           ir.ctypes.data_as(i32p), nat.fptr(self.taps), self.fl, nb, 0, self.stream))
+
+
 def held_stream(x):
     """fvvdp_held_stream of a device clip [1, C, F, H, W] whose frames are dense (H x W contiguous; held.dense_planar)."""
     return nat.HeldStream(x.data_ptr(), *held_strides(x), x.shape[2])

@@ -162,6 +162,16 @@ MULTITEST_SYMBOLS = {
 }
 TESTS_GROUP_MAX = 3                      # FVVDP_TESTS_GROUP_MAX
 
+# include/fvvdp_hip_tests_fov.h: many test clips against one reference under a gaze (bound by lib() as well)
+TESTS_FOV_SYMBOLS = {
+    "fvvdp_tests_fov_covered": (C.c_int, [C.c_void_p, C.POINTER(Geom), C.POINTER(C.c_int), C.c_void_p]),
+    "fvvdp_bands_forward_tests_fov": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                                C.POINTER(Geom), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fvvdp_bands_forward_tests_fov_pool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                                     C.POINTER(Geom), C.c_void_p, C.c_size_t, C.POINTER(PoolParams), C.c_void_p,
+                                                     C.c_void_p]),
+}
+
 # include/fvvdp_hip_gaze_grad.h: gradients of the video JOD under many gaze traces (bound by lib() as well)
 GAZE_GRAD_SYMBOLS = {
     "fvvdp_gaze_grad_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
@@ -350,7 +360,7 @@ _lib = None
 
 def build(force=False, verbose=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU).  Twenty-seven translation units -- the band /
-    pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests pass of fvvdp_hip_tests.h among them;
+    pooling / side-metric kernels with the C ABI (the many-gazes pass of fvvdp_hip_gaze.h and the many-tests passes of fvvdp_hip_tests.h and fvvdp_hip_tests_fov.h among them;
     their launch plans and bounds are the host-only header pyramid_host.hpp, the strip constants pyramid_constants.hpp), the temporal kernels once
     per sample type (temporal_launch.hip with -DK1_PART=0..5: uint8, uint16, float32, planar YUV with the dispatcher, float16, bfloat16), the batched still-image ingest (still_launch.hip), the still-image gradients (grad_launch.hip), the
     video gradients (video_grad_launch.hip), the video gradients under many gazes (gaze_grad_launch.hip), the gradients with
@@ -368,7 +378,7 @@ def build(force=False, verbose=False):
                                                                                                                               "fvvdp_hip_display.h", "fvvdp_hip_half.h", "fvvdp_hip_diffmap.h",
                                                                                                                               "fvvdp_hip_yuv_grad.h", "fvvdp_hip_tests.h", "fvvdp_hip_tests_grad.h",
                                                                                                                               "fvvdp_hip_resize.h", "fvvdp_hip_held.h", "fvvdp_hip_images_resize.h",
-                                                                                                                              "fvvdp_hip_resize_held.h")]
+                                                                                                                              "fvvdp_hip_resize_held.h", "fvvdp_hip_tests_fov.h")]
     if not force and os.path.isfile(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -454,7 +464,7 @@ def lib():
                 list(DISPLAY_SYMBOLS.items()) + list(HALF_SYMBOLS.items()) + list(DIFFMAP_SYMBOLS.items()) + \
                 list(YUV_GRAD_SYMBOLS.items()) + list(MULTITEST_SYMBOLS.items()) + list(TESTS_GRAD_SYMBOLS.items()) + \
                 list(RESIZE_SYMBOLS.items()) + list(HELD_SYMBOLS.items()) + list(IMAGES_RESIZE_SYMBOLS.items()) + \
-                list(RESIZE_HELD_SYMBOLS.items()):
+                list(RESIZE_HELD_SYMBOLS.items()) + list(TESTS_FOV_SYMBOLS.items()):
             fn = getattr(L, name)        # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -24,6 +24,7 @@
 #include "fvvdp_hip_images.h"
 #include "fvvdp_hip_gaze.h"
 #include "fvvdp_hip_tests.h"
+#include "fvvdp_hip_tests_fov.h"
 #include "fvvdp_hip_ref_grad.h"
 #include "fvvdp_hip_params.h"
 #include "fvvdp_hip_diffmap.h"
@@ -67,6 +68,7 @@ int fvvdp_fail_from(int code, const char* msg) { return fail(code, "%s", msg); }
 #include "aux_kernels.hpp"
 #include "multigaze_kernel.hpp"
 #include "multitest_kernel.hpp"
+#include "multitest_fov_kernel.hpp"
 #include "still_kernels.hpp"
 #include "psnr_kernel.hpp"
 #include "resize_kernels.hpp"
@@ -93,7 +95,7 @@ struct CtxEnv {
     bool debug_variant = false;   // FVVDP_DEBUG_VARIANT=1: print which kernel variants are launched (tests)
     int gaze_group = 0;           // FVVDP_GAZE_GROUP=1 / 2 / 4 / 8: largest gaze group of one multigaze_kernel launch (tests, A/B runs)
     int band_cr = 0;              // FVVDP_BAND_CR=n >= 2: chunk height (coarse rows) of every one-level launch instead of chunking()'s (tests, A/B runs)
-    int tests_group = 0;          // FVVDP_TESTS_GROUP=1 / 2 / 3: most quads of one multitest_kernel launch (tests, A/B runs)
+    int tests_group = 0;          // FVVDP_TESTS_GROUP=1 / 2 / 3: most quads of one multitest_kernel / multitest_fov_kernel launch (tests, A/B runs)
     bool yuv_general = false;     // FVVDP_YUV_GENERAL_MATRIX=1: YUV ingest with the nine-term colour matrix also where it has the ITU shape (tests)
 };
 static CtxEnv read_env() {
@@ -1642,6 +1644,58 @@ extern "C" int fvvdp_tests_workspace(int width, int height, int n_bands, int n_t
     return FVVDP_OK;
 }
 
+// ---- what the two many-tests passes share (plain: multitest_kernel; under a gaze: multitest_fov_kernel) -----------------------
+// most quads of one pyramid launch: FVVDP_TESTS_GROUP_MAX, or the cap of FVVDP_TESTS_GROUP
+static int tests_group_max(const fvvdp_ctx* c, int n_quads) {
+    int group_max = FVVDP_TESTS_GROUP_MAX;
+    if (c->env.tests_group >= 1 && c->env.tests_group < group_max) group_max = c->env.tests_group;
+    if (group_max < 2 && n_quads > 1) group_max = 2;         // a group is the reference's quad and at least one other
+    return group_max;
+}
+
+// The launch groups of one level: the reference's quad (slot 0 of the group) and the next group_max - 1 of the quads
+// 0 .. ref_quad - 1; the first group writes the reference's next level and evaluates the test that shares its quad.  Fills
+// qslot[], store[] and row[] of the launch block m (MultiTestArgs, MultiTestFovArgs) and calls launch(nq, rx, q0) per group.
+template <class Args, class Launch>
+static void walk_test_groups(Args& m, int n, int n_tests, int group_max, size_t row, Launch&& launch) {
+    const int ref_quad = n_tests / 2;                        // the last of the ceil((n_tests + 1) / 2) quads
+    const bool ref_shared = (n_tests & 1) != 0;              // the last test sits in (x, z) of the reference's quad
+    int q0 = 0;
+    bool first = true;
+    do {
+        const int others = std::min(group_max - 1, ref_quad - q0);
+        m.qslot[0] = ref_quad * n;
+        m.store[0] = first ? 1 : 0;
+        m.row[0] = (long long)(n_tests - 1) * (long long)row;               // read by the RX instantiations only
+        m.row[1] = 0;
+        for (int j = 1; j <= others; ++j) {
+            const int q = q0 + j - 1;
+            m.qslot[j] = q * n;
+            m.store[j] = 1;
+            m.row[2 * j] = (long long)(2 * q) * (long long)row;
+            m.row[2 * j + 1] = (long long)(2 * q + 1) * (long long)row;
+        }
+        launch(1 + others, first && ref_shared, q0);
+        q0 += others;
+        first = false;
+    } while (q0 < ref_quad);
+}
+
+// finalisation of every test (the test on grid axis y) and, when the batch completes the clip, the pooling kernel once per test
+static void finish_tests_pass(fvvdp_ctx* c, GazeFinalizeArgs& fa, const float* work, size_t row, int n, int n_tests, float* d_Q,
+                              int q_stride, int q_col0, const fvvdp_pool_params* pool, float* d_jod, hipStream_t st) {
+    const long long q_stride_t = (long long)c->n_bands * 2 * q_stride;
+    fill_finalize(fa.f, c, work, d_Q, n, q_stride, q_col0);
+    fa.partial_stride = (long long)row;
+    fa.q_stride_g = q_stride_t;
+    {
+        Timed tm(c, 1 + c->n_bands, st);
+        hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_tests), dim3(64), 0, st, fa);
+    }
+    if (pool && q_col0 + n == q_stride)              // the pooling kernel of fvvdp_bands_forward_pool, once per test
+        launch_pool_rows(d_Q, q_stride_t, n_tests, c->n_bands, q_stride, pool, d_jod, st);
+}
+
 template <bool SPLIT>
 static void launch_multitest(const MultiTestArgs& m, int nq, bool rx, hipStream_t st) {
     const dim3 grid(m.b.n_items), block(64);
@@ -1672,11 +1726,7 @@ static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q
     CHECK_TRY(check_workspace(d_work, work_bytes, (size_t)n_tests * row * sizeof(float), "tests", n_tests, n));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     float* work = reinterpret_cast<float*>(d_work);
-    int group_max = FVVDP_TESTS_GROUP_MAX;
-    if (c->env.tests_group >= 1 && c->env.tests_group < group_max) group_max = c->env.tests_group;
-    if (group_max < 2 && n_quads > 1) group_max = 2;         // a group is the reference's quad and at least one other
-    const int ref_quad = n_quads - 1;
-    const bool ref_shared = (n_tests & 1) != 0;              // the last test sits in (x, z) of the reference's quad
+    const int group_max = tests_group_max(c, n_quads);
     GazeFinalizeArgs fa;
     memset(&fa, 0, sizeof(fa));
     MultiTestArgs m[FVVDP_MAX_BANDS];
@@ -1711,44 +1761,15 @@ static int bands_forward_tests_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q
     }
     for (int b = 0; b < c->n_bands; ++b) {
         Timed tm(c, 1 + b, st);
-        // groups: the reference's quad (slot 0 of the group) and the next group_max - 1 of the quads 0 .. ref_quad - 1; the first
-        // group writes the reference's next level and evaluates the test that shares its quad
-        int q0 = 0;
-        bool first = true;
-        do {
-            const int others = std::min(group_max - 1, ref_quad - q0);
-            const int nq = 1 + others;
-            const bool rx = first && ref_shared;
-            m[b].qslot[0] = ref_quad * n;
-            m[b].store[0] = first ? 1 : 0;
-            m[b].row[0] = (long long)(n_tests - 1) * (long long)row;        // read by the RX instantiations only
-            m[b].row[1] = 0;
-            for (int j = 1; j <= others; ++j) {
-                const int q = q0 + j - 1;
-                m[b].qslot[j] = q * n;
-                m[b].store[j] = 1;
-                m[b].row[2 * j] = (long long)(2 * q) * (long long)row;
-                m[b].row[2 * j + 1] = (long long)(2 * q + 1) * (long long)row;
-            }
+        walk_test_groups(m[b], n, n_tests, group_max, row, [&](int nq, bool rx, int q0) {
             if (c->env.debug_variant)
                 fprintf(stderr, "fvvdp: level %d: multitest_kernel<%d, %s>, n %d, quads %d.., n_strips %d, n_chunks %d, cr %d, store_ref %d, walk %d\n",
                         b, nq, rx ? "true" : "false", n, q0, m[b].b.n_strips, m[b].b.n_chunks, m[b].b.cr, m[b].store[0], mode[b]);
             if (mode[b] == 2) launch_multitest<true>(m[b], nq, rx, st);
             else launch_multitest<false>(m[b], nq, rx, st);
-            q0 += others;
-            first = false;
-        } while (q0 < ref_quad);
+        });
     }
-    const long long q_stride_t = (long long)c->n_bands * 2 * q_stride;
-    fill_finalize(fa.f, c, work, d_Q, n, q_stride, q_col0);
-    fa.partial_stride = (long long)row;
-    fa.q_stride_g = q_stride_t;
-    {
-        Timed tm(c, 1 + c->n_bands, st);
-        hipLaunchKernelGGL(finalize_gazes_kernel, dim3(c->n_bands * 2 * n, n_tests), dim3(64), 0, st, fa);
-    }
-    if (pool && q_col0 + n == q_stride)              // the pooling kernel of fvvdp_bands_forward_pool, once per test
-        launch_pool_rows(d_Q, q_stride_t, n_tests, c->n_bands, q_stride, pool, d_jod, st);
+    finish_tests_pass(c, fa, work, row, n, n_tests, d_Q, q_stride, q_col0, pool, d_jod, st);
     HIP_TRY(hipGetLastError());
     return FVVDP_OK;
 }
@@ -1762,6 +1783,108 @@ extern "C" int fvvdp_bands_forward_tests_pool(fvvdp_ctx* c, int n, int n_tests, 
                                               size_t work_bytes, const fvvdp_pool_params* pool, float* d_jod, void* stream) {
     if (!pool) return fail(FVVDP_EINVAL, "null argument");
     return bands_forward_tests_core(c, n, n_tests, d_Q, q_stride, q_col0, d_work, work_bytes, pool, d_jod, stream);
+}
+
+// ---- many tests per reference under a gaze (include/fvvdp_hip_tests_fov.h) -------------------------------------------------
+static void launch_multitest_fov(const MultiTestFovArgs& m, int nq, bool rx, hipStream_t st) {
+    const dim3 grid((m.b.n_items + FOV_WPB - 1) / FOV_WPB), block(64 * FOV_WPB);
+    // dynamic LDS as band_kernel<4, false, 1>: the band's LUT slice, then the vertical view angle of every band row
+    const size_t lds = (size_t)FOV_PLANE * m.b.rw * sizeof(float4) + (size_t)m.b.h * sizeof(float);
+    if (nq == 3 && rx) hipLaunchKernelGGL((multitest_fov_kernel<3, true>), grid, block, lds, st, m);
+    else if (nq == 3) hipLaunchKernelGGL((multitest_fov_kernel<3, false>), grid, block, lds, st, m);
+    else if (nq == 2 && rx) hipLaunchKernelGGL((multitest_fov_kernel<2, true>), grid, block, lds, st, m);
+    else if (nq == 2) hipLaunchKernelGGL((multitest_fov_kernel<2, false>), grid, block, lds, st, m);
+    else hipLaunchKernelGGL((multitest_fov_kernel<1, true>), grid, block, lds, st, m);
+}
+
+// the state a context needs for the foveated many-tests pass, whatever the call's other arguments
+static int check_tests_fov_context(const fvvdp_ctx* c) {
+    if (c->P != 4) return fail(FVVDP_EINVAL, "a still-image context (2 planes): the tests pass covers video contexts (4 planes)");
+    if (!(c->lut3_set[0] && c->lut3_set[1]))
+        return fail(FVVDP_EINVAL, "the context is not foveated (fvvdp_ctx_set_csf_3d not called): the plain tests pass is fvvdp_bands_forward_tests");
+    if (c->maps_set) return fail(FVVDP_EINVAL, "view maps of a user geometry are set: the foveated tests pass covers the stock geometry only");
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_tests_fov_covered(fvvdp_ctx* c, const fvvdp_geom* geom, int* covered, void* stream) {
+    if (!c || !geom || !covered) return fail(FVVDP_EINVAL, "null argument");
+    CHECK_TRY(check_tests_fov_context(c));
+    CHECK_TRY(build_sublut(c, geom, reinterpret_cast<hipStream_t>(stream)));
+    *covered = 1;
+    for (int b = 0; b < c->n_bands; ++b) {
+        BandArgs a;
+        fill_band_args(c, b, 0, 1, true, geom, a);
+        if (band_fovm(a, false, true) != 1) *covered = 0;
+    }
+    return FVVDP_OK;
+}
+
+static int bands_forward_tests_fov_core(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, const float* h_fixation,
+                                        const fvvdp_geom* geom, void* d_work, size_t work_bytes, const fvvdp_pool_params* pool,
+                                        float* d_jod, void* stream) {
+    if (!c || !d_Q || !h_fixation || !d_work) return fail(FVVDP_EINVAL, "null argument");
+    if (!geom) return fail(FVVDP_EINVAL, "null argument: the foveated tests pass needs the display geometry");
+    CHECK_TRY(check_pool_request(pool, d_jod));
+    if (n_tests < 1) return fail(FVVDP_EINVAL, "n_tests must be >= 1, got %d", n_tests);
+    if (n < 1) return fail(FVVDP_EINVAL, "n must be >= 1, got %d", n);
+    const int n_quads = n_tests / 2 + 1;                     // ceil((n_tests + 1) / 2): streams 0 .. n_tests, two per quad
+    if ((long long)n_quads * n > c->max_frames)
+        return fail(FVVDP_EINVAL, "%d tests x %d frames need %d x %d frame slots, the context has max_frames=%d", n_tests, n, n_quads, n,
+                    c->max_frames);
+    CHECK_TRY(check_q_columns(n, q_stride, q_col0));
+    CHECK_TRY(check_tests_fov_context(c));
+    // fvvdp_tests_workspace's rows: per band the larger of the one-level and the two-level bound, so they hold the one-level walk
+    size_t off[FVVDP_MAX_BANDS];
+    const size_t row = tests_row_floats(c->W, c->H, c->n_bands, n, off);
+    CHECK_TRY(check_workspace(d_work, work_bytes, (size_t)n_tests * row * sizeof(float), "tests", n_tests, n));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // the slices' sizes are build_sublut's result (on a new geometry it synchronises, allocates, uploads the slices and launches
+    // fov_rho_map_kernel); every refusal below still comes before the first pyramid launch and before the gaze upload
+    CHECK_TRY(build_sublut(c, geom, st));
+    float* work = reinterpret_cast<float*>(d_work);
+    const int group_max = tests_group_max(c, n_quads);
+    GazeFinalizeArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    MultiTestFovArgs m[FVVDP_MAX_BANDS];
+    for (int b = 0; b < c->n_bands; ++b) {
+        memset(&m[b], 0, sizeof(m[b]));
+        fill_band_args(c, b, 0, n, true, geom, m[b].b);
+        if (band_fovm(m[b].b, false, true) != 1)
+            return fail(FVVDP_EUNSUPPORTED, "band %d: its slice of the CSF table (%d rho intervals) does not fit the LDS: the foveated tests "
+                        "pass has no variant for it (fvvdp_tests_fov_covered), use fvvdp_bands_forward per test", b, m[b].b.rw);
+        const int nblk = m[b].b.n_strips * m[b].b.n_chunks;
+        CHECK_TRY(check_plan_fits((size_t)n * nblk * 2, (b + 1 < c->n_bands ? off[b + 1] : row) - off[b]));
+        m[b].b.n_items = nblk * n;
+        m[b].partial = work + off[b];
+        record_band(fa.f, c, b, nblk, (long long)off[b]);
+    }
+    // stream-ordered after the kernels of the previous call that still read d_fix (see bands_forward_core)
+    HIP_TRY(hipMemcpyAsync(c->d_fix, h_fixation, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
+    for (int b = 0; b < c->n_bands; ++b) {
+        Timed tm(c, 1 + b, st);
+        walk_test_groups(m[b], n, n_tests, group_max, row, [&](int nq, bool rx, int q0) {
+            if (c->env.debug_variant)
+                fprintf(stderr, "fvvdp: level %d: multitest_fov_kernel<%d, %s>, n %d, quads %d.., n_strips %d, n_chunks %d, cr %d, rw %d, lut_lds %d, store_ref %d\n",
+                        b, nq, rx ? "true" : "false", n, q0, m[b].b.n_strips, m[b].b.n_chunks, m[b].b.cr, m[b].b.rw, m[b].b.lut_lds, m[b].store[0]);
+            launch_multitest_fov(m[b], nq, rx, st);
+        });
+    }
+    finish_tests_pass(c, fa, work, row, n, n_tests, d_Q, q_stride, q_col0, pool, d_jod, st);
+    HIP_TRY(hipGetLastError());
+    return FVVDP_OK;
+}
+
+extern "C" int fvvdp_bands_forward_tests_fov(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0, const float* h_fixation,
+                                             const fvvdp_geom* geom, void* d_work, size_t work_bytes, void* stream) {
+    return bands_forward_tests_fov_core(c, n, n_tests, d_Q, q_stride, q_col0, h_fixation, geom, d_work, work_bytes, nullptr, nullptr,
+                                        stream);
+}
+
+extern "C" int fvvdp_bands_forward_tests_fov_pool(fvvdp_ctx* c, int n, int n_tests, float* d_Q, int q_stride, int q_col0,
+                                                  const float* h_fixation, const fvvdp_geom* geom, void* d_work, size_t work_bytes,
+                                                  const fvvdp_pool_params* pool, float* d_jod, void* stream) {
+    if (!pool) return fail(FVVDP_EINVAL, "null argument");
+    return bands_forward_tests_fov_core(c, n, n_tests, d_Q, q_stride, q_col0, h_fixation, geom, d_work, work_bytes, pool, d_jod, stream);
 }
 
 // ---- placement of level 0, at context creation ------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// The pyramid row walk shared by the four fused pyramid kernels (band_kernel, band2_kernel, multigaze_kernel, multitest_kernel).
+// The pyramid row walk shared by the five fused pyramid kernels (band_kernel, band2_kernel, multigaze_kernel, multitest_kernel,
+// multitest_fov_kernel).
 // Device only.  Included by band_kernel.hpp after its building blocks (Px, ld_px_buf, dpp_reduce_taps, dpp_expand_taps).
 #pragma once
 // ------------------------------------------------------------------------------------------------------------
@@ -9,7 +10,8 @@
 // (tests/test_gpu_gazes.py, tests/test_gpu_multitest.py): they get the same values because they run the same code.
 //
 // The rule of this file: sharing a piece may not change a single instruction of any of the 34 kernel instantiations that use it
-// (tests/test_pyramid_walk_cpu.py guards the registers; the comparison itself is the disassembly per kernel).  What that takes:
+// (tests/test_pyramid_walk_cpu.py guards the registers; the comparison itself is the disassembly per kernel), nor of the five of
+// multitest_fov_kernel (tests/test_tests_fov_cpu.py).  What that takes:
 //   - Contraction is lexical: a function is compiled under the setting where it is WRITTEN.  band_item and band2_item
 //     are compiled with floating-point contraction on, multigaze_item and multitest_item with it off.  Every function
 //     here switches it off and spells each fused multiply-add as pfma / fmaf / __builtin_elementwise_fma; no a * b + c

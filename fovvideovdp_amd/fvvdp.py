@@ -617,6 +617,28 @@ class fvvdp:
         from .multitest import predict_tests
         return predict_tests(self, tests, reference, dim_order, frames_per_second, fixation_point)
 
+    def predict_tests_foveated(self, tests, reference, dim_order="BCFHW", frames_per_second=0, fixation_point=None):
+        """Extension: predict_tests for a foveated metric -- T foveated variants of ONE reference under the same gaze trace in
+        one pass: a foveated renderer at several shading rates, a foveated codec at several bitrates.  `tests` as predict_tests
+        takes them; `fixation_point`: None (the centre), [x, y] or [N_frames, 2] in frame pixels, as predict takes it.  Returns
+        (Q_JOD, stats): Q_JOD a [T] fp32 device tensor, stats['Q_per_ch'] [T, bands, 2, frames] (numpy), the other keys as predict
+        makes them, and stats['shared_pass'].  Row k is bit-identical to
+        predict(tests[k], reference, dim_order, frames_per_second, fixation_point=fixation_point) on this metric, whatever the
+        other tests are, however many there are and in whatever order, whatever `batch_frames` is.  The ingest is predict_tests'
+        (the reference once per pair of tests); the pyramid pass evaluates what depends on the reference and the gaze only
+        (its own pyramid, L_bkg, the eccentricity, the cell of the CSF table and its 3-D interpolation) once per group of up to
+        five tests (include/fvvdp_hip_tests_fov.h).  Accepted: what predict_tests accepts (uint8 / uint16 / float32 / float16 /
+        bfloat16 arrays, C = 1 or 3, host or device, any `dim_order`, every temporal padding, passes under
+        `self.tests_scratch_bytes`); one out-of-range warning per call.  Refused, each with a sentence and before any device
+        work: a metric that is not foveated (predict_tests), a heat-map metric, a user display_geometry class, source objects and
+        YUV frame sources, a single frame, tests whose shape or dtype differs from the reference's, inputs that require grad, a
+        `fixation_point` of another shape, float input behind a user photometry class.  Coverage: the shared pass needs every
+        band's slice of the CSF table in the LDS (stats['shared_pass'] True).  Where a band's does not fit (every band of
+        standard_hmd or htc_vive_pro, band 0 of a 2160-row frame on sdr_4k_30) the whole call is the loop of
+        predict(..., sync=False) with one host synchronisation: same bits, no gain, stats['shared_pass'] False."""
+        from .tests_fov import predict_tests_foveated
+        return predict_tests_foveated(self, tests, reference, dim_order, frames_per_second, fixation_point)
+
     def jod_gazes(self, test, reference, fixation_points, dim_order="BCFHW", frames_per_second=0):
         """Extension: the JODs of one clip under G gaze traces as a differentiable [G] fp32 tensor on the metric's device, for
         losses over a gaze distribution such as `(10 - metric.jod_gazes(x, ref, grid, frames_per_second=30)).mean()` or the

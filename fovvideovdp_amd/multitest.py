@@ -56,13 +56,22 @@ def predict_tests(metric, tests, reference, dim_order="BCFHW", frames_per_second
     """fvvdp.predict_tests (see there)."""
     if metric.foveated or fixation_point is not None:
         raise RuntimeError("predict_tests covers the non-foveated metric (no fixation_point): for a foveated metric call predict() "
-                           "once per test")
+                           "once per test, or predict_tests_foveated()")
+    streams, width, height, N = clip_arguments("predict_tests", metric, tests, reference, dim_order, frames_per_second)
+    metric._check_device()
+    with torch.cuda.device(metric.device):
+        return _on_device(metric, streams, dim_order, frames_per_second, width, height, N)
+
+
+def clip_arguments(name, metric, tests, reference, dim_order, frames_per_second):
+    """The checks on the clips of predict_tests and of predict_tests_foveated (`name`, for the sentences), all before any device
+    work.  Returns (streams, width, height, N): the T tests and then the reference, as tensors where they came."""
     if metric.do_heatmap:
-        raise RuntimeError("predict_tests makes no heat maps: build the metric without heatmap=, or call predict() per test")
+        raise RuntimeError("%s makes no heat maps: build the metric without heatmap=, or call predict() per test" % name)
     if _is_source_object(reference) or _is_source_object(tests) or \
             (isinstance(tests, (list, tuple)) and any(_is_source_object(t) for t in tests)):
-        raise RuntimeError("predict_tests takes arrays or tensors: a fvvdp_video_source object or a YUV frame source goes through "
-                           "predict_video_source(), one test per call")
+        raise RuntimeError("%s takes arrays or tensors: a fvvdp_video_source object or a YUV frame source goes through "
+                           "predict_video_source(), one test per call" % name)
     if not isinstance(tests, (list, tuple)) or len(tests) < 1:
         raise RuntimeError("tests must be a list or tuple of at least one clip, each shaped like the reference")
     as_tensor = fvvdp_video_source_array._as_tensor
@@ -82,22 +91,25 @@ def predict_tests(metric, tests, reference, dim_order="BCFHW", frames_per_second
                                    display_photometry=metric.display_photometry, color_space_name=metric.color_space)
     height, width, N = vs0.get_video_size()
     if N < 2:
-        raise RuntimeError("predict_tests needs clips of at least 2 frames: for a single frame use predict_images() with the "
-                           "reference repeated")
+        raise RuntimeError("%s needs clips of at least 2 frames: for a single frame use predict_images() with the "
+                           "reference repeated" % name)
     if vs0.test_video.shape[0] != 1:
         raise RuntimeError("Only batch size 1 is supported (as in the reference's sliding-window code)")
-    metric._check_device()
-    with torch.cuda.device(metric.device):
-        return _on_device(metric, streams, dim_order, frames_per_second, width, height, N)
+    return streams, width, height, N
 
 
-def _on_device(metric, streams, dim_order, fps, width, height, N):
+def _on_device(metric, streams, dim_order, fps, width, height, N, gaze=None, name="predict_tests"):
+    """The device part of predict_tests and, with the fp32 [N, 2] trace `gaze`, of predict_tests_foveated (`name`, for the
+    sentence).  Returns (JOD [T], stats), or None where the pass under a gaze does not cover the context (launch_passes)."""
     dev, T = metric.device, len(streams) - 1
     h2d = sum(s.numel() * s.element_size() for s in streams if s.device != dev)
     # every clip crosses to the device once, the reference included, and lies there as the ingest kernels read it
     streams = [reshuffle_dims(s.to(dev), in_dims=dim_order, out_dims="BCFHW").contiguous() for s in streams]
-    res, pl = launch_passes(metric, streams, fps, width, height, N, "predict_tests needs a display model the ingest kernels "
-                            "evaluate (float input behind a user photometry class goes through predict(), one test per call)")
+    res, pl = launch_passes(metric, streams, fps, width, height, N, "%s needs a display model the ingest kernels "
+                            "evaluate (float input behind a user photometry class goes through predict(), one test per call)" % name,
+                            gaze)
+    if res is None:
+        return None
     n_bands, nq = pl.n_bands, pl.n_bands * 2 * N
     metric.last_h2d_bytes = h2d
     res_h = metric._to_host(res)                          # the one host synchronisation of the call
@@ -108,11 +120,14 @@ def _on_device(metric, streams, dim_order, fps, width, height, N):
     return res[T * nq + 1:], stats
 
 
-def launch_passes(metric, streams, fps, width, height, N, refusal):
+def launch_passes(metric, streams, fps, width, height, N, refusal, gaze=None):
     """The launches of predict_tests for the T + 1 contiguous [1, C, N, H, W] device clips `streams` (the tests, then the
-    reference): the one launch loop of predict_tests and of tests_grad.jod_tests.  Returns (res, plan): res the device tensor
-    Q_per_ch [T][bands][2][N] | range flag | JOD [T], nothing of it read back; plan the clip plan of the call.  `refusal`: the
-    sentence for a source whose display model the ingest kernels do not evaluate."""
+    reference): the one launch loop of predict_tests, of tests_grad.jod_tests and of tests_fov.predict_tests_foveated.  Returns
+    (res, plan): res the device tensor Q_per_ch [T][bands][2][N] | range flag | JOD [T], nothing of it read back; plan the clip
+    plan of the call.  `refusal`: the sentence for a source whose display model the ingest kernels do not evaluate.  `gaze`: None,
+    or the fp32 [N, 2] gaze trace of a foveated metric with the stock geometry -- the pyramid pass is then that of
+    include/fvvdp_hip_tests_fov.h, and res is None (nothing ingested, no pyramid launch) where that pass does not cover the
+    context."""
     dev, T = metric.device, len(streams) - 1
 
     def source(a, b):
@@ -134,14 +149,25 @@ def launch_passes(metric, streams, fps, width, height, N, refusal):
         budget = min(96e9, 0.4 * torch.cuda.get_device_properties(dev).total_memory)
     max_quads = max(1, int(budget // (pl.batch * per_frame)))
     per_pass = T if T // 2 + 1 <= max_quads else max(1, 2 * max_quads - 1)
+    fov = None
+    if gaze is not None:
+        fov = (gaze, metric._geom_struct())
+        # asked of the context of the first (largest) pass, before anything is ingested
+        ctx = metric._context(width, height, pl.n_bands, pl.planes, (min(per_pass, T) // 2 + 1) * pl.batch, pl.rho_band)
+        covered = C.c_int(0)
+        nat.check(nat.lib().fvvdp_tests_fov_covered(ctx.handle, C.byref(fov[1]), C.byref(covered),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        if not covered.value:
+            return None, pl
     for k0 in range(0, T, per_pass):
         ks = list(range(k0, min(k0 + per_pass, T)))
-        _one_pass(metric, pl, source, ks, T, res[k0 * nq:(k0 + len(ks)) * nq], oob, res[T * nq + 1 + k0:], width, height, N)
+        _one_pass(metric, pl, source, ks, T, res[k0 * nq:(k0 + len(ks)) * nq], oob, res[T * nq + 1 + k0:], width, height, N, fov)
     return res, pl
 
 
-def _one_pass(metric, pl, source, ks, ref, Q, oob, jod, width, height, N):
-    """Tests `ks` (indices into the stream list) against stream `ref`: Q [len(ks)][bands][2][N] and jod [len(ks)] are written."""
+def _one_pass(metric, pl, source, ks, ref, Q, oob, jod, width, height, N, fov=None):
+    """Tests `ks` (indices into the stream list) against stream `ref`: Q [len(ks)][bands][2][N] and jod [len(ks)] are written.
+    `fov`: None, or (gaze [N, 2], geometry struct) for the pass under a gaze."""
     dev, lib, t = metric.device, nat.lib(), len(ks)
     qp = quad_plan(t, max(pl.schedule))
     local = ks + [ref]                                    # stream number of the pass -> stream of the call
@@ -157,11 +183,15 @@ def _one_pass(metric, pl, source, ks, ref, Q, oob, jod, width, height, N):
         idx = np.ascontiguousarray(pl.widx[b0:b0 + fl - 1 + nb])
         for q, feed in enumerate(feeders):
             feed(ctx, idx, pl.taps, fl, nb, oob, stream, slot0=q * nb)
-        if b0 + nb == N:
-            nat.check(lib.fvvdp_bands_forward_tests_pool(ctx.handle, nb, t, C.c_void_p(Q.data_ptr()), N, b0,
-                                                         C.c_void_p(work.data_ptr()), nbytes.value, C.byref(pp),
-                                                         C.c_void_p(jod.data_ptr()), stream))
+        last = b0 + nb == N                               # the batch that completes the clip also pools
+        args = (ctx.handle, nb, t, C.c_void_p(Q.data_ptr()), N, b0)
+        if fov is not None:                               # the batch's rows of the gaze trace, then the geometry
+            fxa = np.ascontiguousarray(fov[0][b0:b0 + nb], dtype=np.float32)
+            args += (nat.fptr(fxa), C.byref(fov[1]))
+        args += (C.c_void_p(work.data_ptr()), nbytes.value)
+        args += (C.byref(pp), C.c_void_p(jod.data_ptr()), stream) if last else (stream,)
+        if fov is None:
+            nat.check(lib.fvvdp_bands_forward_tests_pool(*args) if last else lib.fvvdp_bands_forward_tests(*args))
         else:
-            nat.check(lib.fvvdp_bands_forward_tests(ctx.handle, nb, t, C.c_void_p(Q.data_ptr()), N, b0,
-                                                    C.c_void_p(work.data_ptr()), nbytes.value, stream))
+            nat.check(lib.fvvdp_bands_forward_tests_fov_pool(*args) if last else lib.fvvdp_bands_forward_tests_fov(*args))
         b0 += nb
